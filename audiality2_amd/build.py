@@ -95,7 +95,9 @@ def build_walk(force=False, engine=None):
     """INTEGRATION.md option C: liba2amd_walk.so, the engine's voice walk with the short cut for
     sleeping voices.  Compiled against the ENGINE's internal headers (src/internals.h), so it
     is built where the engine's source tree is (A2_ENGINE_SRC, default /root/reference) and for
-    that engine version; elsewhere the library built before travels as it is."""
+    that engine version; elsewhere the library built before travels as it is.  A copy is kept
+    under oracle/_ref/ (where what is built from the engine's tree goes, git-ignored), and a
+    tree without the engine's sources takes that copy when its own is missing or stale."""
     engine = engine or os.environ.get("A2_ENGINE_SRC", "/root/reference")
     out = os.path.join(HERE, "liba2amd_walk.so")
     src = os.path.join(HERE, "csrc", "a2amd_walk.c")
@@ -105,7 +107,10 @@ def build_walk(force=False, engine=None):
            os.path.join(ROOT, "include", "a2amd_plugin.h")]
     flags = ["-O2", "-Wall", "-fPIC", "-shared"]
     want = source_hash(own, flags)
+    kept = os.path.join(ROOT, "oracle", "_ref", "liba2amd_walk.so")
     if not (os.path.exists(os.path.join(engine, "src", "internals.h")) and shutil.which("cmake")):
+        if (not os.path.exists(out) or _stale(out, want)) and not _stale(kept, want):
+            shutil.copyfile(kept, out)
         if os.path.exists(out) and _stale(out, want):
             raise RuntimeError(f"{out} was not built from this tree's a2amd_walk.c (stamp {stamped_hash(out)}, "
                                f"sources {want}) and the engine's source tree ({engine}) is not here to rebuild it")
@@ -122,6 +127,9 @@ def build_walk(force=False, engine=None):
                        ["-I" + os.path.join(engine, d) for d in ("include", "src", "src/units", "src/drivers")] +
                        ["-o", out, src, "-L" + HERE, "-la2amd_units", "-la2amd", "-ldl", "-lpthread", "-Wl,-rpath,$ORIGIN"],
                        check=True)
+    if stamped_hash(kept) != want or stamped_hash(kept, ENGMARK) != weng:
+        os.makedirs(os.path.dirname(kept), exist_ok=True)
+        shutil.copyfile(out, kept)
     return out
 
 

@@ -26,7 +26,11 @@ the partials are summed with ONE RCCL reduce (int32, wrap-around sum => exact
 in any order), and rank 0 runs the root chain (panmix must see the sum,
 SURVEY.md 8e).
 
-Prints one JSON line (rank 0).  Extra objects: "roofline" (the dominant kernel
+Prints one JSON line (rank 0).  A plain run sets up, warms up, times --steps steps and
+prints the line (metric, value, unit, ms_per_step, ...); --dump-outputs DIR also writes
+the master bus of the last timed step to DIR/master_bus.npy (float64, exact).  Everything
+else is measured and checked with --full only - the golden parity gate, and the extra
+objects: "roofline" (the dominant kernel
 against the HBM roofline, timed with HIP events on the launch stream),
 "roofline_valu" (the same kernel against the integer-VALU issue rate, from the
 PMC instruction counts under profiles/), "realtime" (measured per-fragment round
@@ -129,16 +133,18 @@ def contract_line(full):
     if isinstance(full.get("parity"), dict):
         line["parity"] = _pick(full["parity"], ("golden_steps_compared", "timed_steps_covered_by_golden",
                                                 "golden_fragments_compared"))
-    rf = full.get("roofline") or {}
-    line["roofline"] = _pick(rf, ("bound", "kernel", "avg_launch_ms", "launches_timed", "algorithmic_bytes_per_launch",
-                                  "achieved", "peak", "unit", "frac", "traffic_over_algorithmic", "binding_roofline"))
-    line["roofline"]["traffic"] = rf.get("traffic")
-    ts = rf.get("traffic_source") or {}
-    line["roofline"]["traffic_file"] = ts.get("file")
-    line["roofline"]["traffic_stale"] = ts.get("stale")
-    rv = full.get("roofline_valu") or {}
-    line["roofline_valu"] = _pick(rv, ("bound", "kernel", "achieved", "peak", "unit", "frac", "frac_of_nominal",
-                                       "valu_insts_per_voice_fragment"))
+    if isinstance(full.get("roofline"), dict):
+        rf = full["roofline"]
+        line["roofline"] = _pick(rf, ("bound", "kernel", "avg_launch_ms", "launches_timed", "algorithmic_bytes_per_launch",
+                                      "achieved", "peak", "unit", "frac", "traffic_over_algorithmic", "binding_roofline"))
+        line["roofline"]["traffic"] = rf.get("traffic")
+        ts = rf.get("traffic_source") or {}
+        line["roofline"]["traffic_file"] = ts.get("file")
+        line["roofline"]["traffic_stale"] = ts.get("stale")
+    if isinstance(full.get("roofline_valu"), dict):
+        rv = full["roofline_valu"]
+        line["roofline_valu"] = _pick(rv, ("bound", "kernel", "achieved", "peak", "unit", "frac", "frac_of_nominal",
+                                           "valu_insts_per_voice_fragment"))
     if isinstance(full.get("cpu_baseline"), dict):
         cb = full["cpu_baseline"]
         line["cpu_baseline"] = _pick(cb, ("value", "unit", "cores", "kind", "single_thread_value", "host_cores"))
@@ -216,6 +222,21 @@ def emit(full):
     s = json.dumps(contract_line(full))
     assert len(s) <= LINE_LIMIT, len(s)
     print(s, flush=True)
+
+
+DUMP_LIMIT = 64 << 20       # bytes of --dump-outputs in all
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: every array as DIR/<name>.npy in float64 (the int32 audio exactly); an array past the
+    limit is cut to a fixed, seeded sample of its frames (the same frames in every run)."""
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.asarray(a, dtype=np.float64)
+        if a.nbytes > DUMP_LIMIT // len(arrays):
+            keep = DUMP_LIMIT // len(arrays) // (a.itemsize * a.shape[0])
+            a = a[:, np.sort(np.random.default_rng(0).choice(a.shape[1], keep, replace=False))]
+        np.save(os.path.join(d, name + ".npy"), a)
 
 
 class Stats(ctypes.Structure):
@@ -683,12 +704,13 @@ def golden_steps(voices, chain, groups, B, tree=0, private=None):
     return len(np.load(path)) // B if os.path.exists(path) else 0
 
 
-def measure_single(audiality2_amd, cfg, B, steps, warmup, device=0, with_realtime=True):
-    """One config at N=1: returns the dict of measured figures."""
+def measure_single(audiality2_amd, cfg, B, steps, warmup, device=0, with_realtime=True, full=True):
+    """One config at N=1: returns the dict of measured figures ("output": the last timed step's
+    master bus).  full=False: the timed steps alone - no golden gate, no profiled pass."""
     import gc
     import torch
     r = Runner(audiality2_amd, cfg["voices"], cfg["chain"], cfg["groups"], B, device, tree=cfg.get("tree", 0), private=cfg.get("private"))
-    gsteps = golden_steps(cfg["voices"], cfg["chain"], cfg["groups"], B, cfg.get("tree", 0), cfg.get("private"))
+    gsteps = golden_steps(cfg["voices"], cfg["chain"], cfg["groups"], B, cfg.get("tree", 0), cfg.get("private")) if full else 0
     r.keep_upto = gsteps
     r.run(1)                        # step 0: voices are born
     r.run(warmup)
@@ -700,24 +722,27 @@ def measure_single(audiality2_amd, cfg, B, steps, warmup, device=0, with_realtim
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     gc.enable()
+    last = r.last.copy()
+    res = {"voices": cfg["voices"], "chain": cfg["chain"], "groups": cfg["groups"], "private": cfg.get("private"), "seconds": dt,
+           "value": float(cfg["voices"]) * B * 64 * steps / dt, "ms_per_step": dt / steps * 1e3, "output": last}
+    if not full:
+        r.close()
+        return res
     total_steps = 1 + warmup + steps
     compared, ok = check_golden(r, total_steps)
     if ok is False and os.environ.get("A2AMD_DEBUG"):
         print("bench.py: ablation run (A2AMD_DEBUG set): output differs from the golden, number is NOT a result", file=sys.stderr)
     elif ok is False:
         raise SystemExit("bench.py: GPU render differs from the oracle golden; refusing to report a number")
-    last = r.last.copy()
     # steady state beyond the golden: the scene is stationary, so every later step must
     # stay within the level of the verified ones (catches silence, runaway, stuck output)
     peak_ref = max((int(np.abs(a).max()) for a in r.kept.values()), default=None)
     leaf_ms, all_ms, nprof = r.profile(min(steps, 32))
-    res = {"voices": cfg["voices"], "chain": cfg["chain"], "groups": cfg["groups"], "private": cfg.get("private"), "seconds": dt,
-           "value": float(cfg["voices"]) * B * 64 * steps / dt, "ms_per_step": dt / steps * 1e3,
-           "leaf_ms": leaf_ms, "all_ms": all_ms, "launches_timed": nprof,
-           "golden_steps_compared": compared, "parity_vs_golden": ok,
-           "timed_steps_covered_by_golden": max(0, min(compared, total_steps) - 1 - warmup),
-           "last_step_peak": int(np.abs(last).max()), "golden_peak": peak_ref,
-           "last_step_nonzero": bool(last.any())}
+    res.update({"leaf_ms": leaf_ms, "all_ms": all_ms, "launches_timed": nprof,
+                "golden_steps_compared": compared, "parity_vs_golden": ok,
+                "timed_steps_covered_by_golden": max(0, min(compared, total_steps) - 1 - warmup),
+                "last_step_peak": int(np.abs(last).max()), "golden_peak": peak_ref,
+                "last_step_nonzero": bool(last.any())})
     if with_realtime:
         res["realtime"] = r.realtime()
     r.close()
@@ -856,10 +881,15 @@ def main():
     ap.add_argument("--batch", type=int, default=256, help="fragments per step (256 = 341 ms of audio)")
     ap.add_argument("--reduce-group", type=int, default=8,
                     help="N>1: steps whose root-bus partials are summed by one collective")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the configs[1] / configs[2] extra keys")
-    ap.add_argument("--no-realtime", action="store_true")
-    ap.add_argument("--no-engine", action="store_true", help="skip the engine-in-the-loop (a2_Run) object")
+    ap.add_argument("--full", action="store_true",
+                    help="also the golden parity gate, roofline / roofline_valu (a profiled pass), realtime, the other "
+                         "configs, max_realtime_voices, cpu_baseline and engine_in_loop; a plain run times the steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's master bus to DIR/master_bus.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip cpu_baseline")
+    ap.add_argument("--no-extra", action="store_true", help="--full: skip the configs[1] / configs[2] extra keys")
+    ap.add_argument("--no-realtime", action="store_true", help="--full: skip the realtime objects")
+    ap.add_argument("--no-engine", action="store_true", help="--full: skip the engine-in-the-loop (a2_Run) object")
     args = ap.parse_args()
 
     cfg = dict(CONFIGS[args.config])
@@ -894,8 +924,10 @@ def main():
 
     if not multi:
         res = measure_single(audiality2_amd, cfg, B, args.steps, args.warmup, local_rank,
-                             with_realtime=not args.no_realtime)
-        roof, valu = roofline_objects(res, B)
+                             with_realtime=not args.no_realtime, full=args.full)
+        output = res.pop("output")
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"master_bus": output})
         line = {
             "metric": "voice-samples/sec + max realtime voices @48kHz",
             "value": res["value"], "unit": "voice-samples/s", "n_gpus": 1, "steps": args.steps,
@@ -908,11 +940,19 @@ def main():
                                        "ROOT|READBACK|ASYNC) + a2amd_collect() of the previous step into host "
                                        "buffers (double-buffered); every step's master bus reaches the host"},
             "realtime_factor": res["value"] / (cfg["voices"] * 48000.0),
+        }
+        if not args.full:
+            sys.stdout.flush()
+            ctypes.CDLL(None).fflush(None)
+            emit(line)
+            return
+        roof, valu = roofline_objects(res, B)
+        line.update({
             "parity_vs_golden": res["parity_vs_golden"],
             "parity": {k: res[k] for k in ("golden_steps_compared", "timed_steps_covered_by_golden",
                                            "last_step_peak", "golden_peak", "last_step_nonzero")},
             "roofline": roof, "roofline_valu": valu,
-        }
+        })
         if "realtime" in res:
             line["realtime"] = res["realtime"]
         if not args.no_extra and not custom and args.config == 3:
@@ -1002,14 +1042,17 @@ def main():
         dist.all_reduce(token)
         torch.cuda.synchronize()
 
-    def timed_job(cfg, steps, warmup):
-        """A Runner of its own RCCL communicator, born, warmed up and timed: (runner, seconds)."""
+    def timed_job(cfg, steps, warmup, full=True):
+        """A Runner of its own RCCL communicator, born, warmed up and timed: (runner, seconds).
+        full=False: no steps kept for the golden gate."""
         r = Runner(audiality2_amd, cfg["voices"], cfg["chain"], cfg["groups"], B, local_rank, world=world, rank=rank,
                    tree=cfg.get("tree", 0))
         r.keep_upto = 1 if os.path.exists(golden_path(cfg["voices"] * world, cfg["chain"], cfg["groups"] * world,
                                                       cfg.get("tree", 0))) else 0
         if world == 1 and not cfg.get("tree"):      # (A2AMD_BENCH_FORCE_DIST=1: the single-GPU golden, every step)
             r.keep_upto = golden_steps(cfg["voices"], cfg["chain"], cfg["groups"], B)
+        if not full:
+            r.keep_upto = 0
         lib = r.lib
         lib.a2amd_dist_unique_id.argtypes = [ctypes.c_void_p]
         lib.a2amd_dist_init.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int]
@@ -1038,22 +1081,19 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         return r, float(t.item())
 
-    r, dt = timed_job(cfg, args.steps, args.warmup)
-    leaf_ms, all_ms, nprof = r.profile(min(args.steps, 16))
-    last = r.last
-    # a realtime driver's view at N > 1: one 64-frame fragment per render - every fragment pays the reduce
-    fence()
-    frag_rt = None if args.no_realtime else r.realtime(200)
-    fence()
+    r, dt = timed_job(cfg, args.steps, args.warmup, full=args.full)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"master_bus": r.last})
+    if args.full:
+        leaf_ms, all_ms, nprof = r.profile(min(args.steps, 16))
+        last = r.last
+        # a realtime driver's view at N > 1: one 64-frame fragment per render - every fragment pays the reduce
+        fence()
+        frag_rt = None if args.no_realtime else r.realtime(200)
+        fence()
     line = None
     if rank == 0:
-        compared, ok = check_golden(r, 1 + args.warmup + args.steps)
-        if ok is False:
-            raise SystemExit("bench.py: the ranks' summed render differs from the oracle golden; refusing to report a number")
         value = float(cfg["voices"]) * world * B * 64 * args.steps / dt
-        res = {"chain": cfg["chain"], "voices": cfg["voices"], "groups": cfg["groups"],
-               "leaf_ms": leaf_ms, "all_ms": all_ms, "launches_timed": nprof}
-        roof, valu = roofline_objects(res, B)
         line = {
             "metric": "voice-samples/sec + max realtime voices @48kHz",
             "value": value, "unit": "voice-samples/s", "n_gpus": world, "steps": args.steps,
@@ -1068,6 +1108,15 @@ def main():
                                        "SUBTREES|ROOT|READBACK|ASYNC); rank 0: a2amd_collect() of the previous "
                                        "step into host buffers"},
             "realtime_factor": value / (cfg["voices"] * world * 48000.0),
+        }
+    if rank == 0 and args.full:
+        compared, ok = check_golden(r, 1 + args.warmup + args.steps)
+        if ok is False:
+            raise SystemExit("bench.py: the ranks' summed render differs from the oracle golden; refusing to report a number")
+        res = {"chain": cfg["chain"], "voices": cfg["voices"], "groups": cfg["groups"],
+               "leaf_ms": leaf_ms, "all_ms": all_ms, "launches_timed": nprof}
+        roof, valu = roofline_objects(res, B)
+        line.update({
             "parity_vs_golden": ok,
             "parity": {"golden_fragments_compared": min(B, 64) if compared else 0,
                        "what": "the first fragments of step 0 of the WHOLE job's audio (all ranks' subtrees summed by "
@@ -1076,14 +1125,14 @@ def main():
             if compared else None,
             "roofline": roof, "roofline_valu": valu,
             "output_check": {"peak": int(np.abs(last).max()), "nonzero": bool(last.any())},
-        }
+        })
         if frag_rt:
             frag_rt["scope"] = ("rank 0's side of one 64-frame fragment at N = %d: a2amd_fragment_repeat(64, 1) + a2amd_render(ALL), "
                                 "synchronous - records up, this rank's subtrees, the ncclReduce of the root bus (once per "
                                 "fragment in this mode), root chain, master bus back; the other ranks run the same loop" % world)
             line["fragment_roundtrip_with_reduce"] = frag_rt
     r.be.close()
-    if args.config == 3 and not custom and not args.no_extra:
+    if args.full and args.config == 3 and not custom and not args.no_extra:
         # BASELINE configs[4] in the same launch: one top-level group of 128 sub-groups x 256
         # wtosc->filter12->panmix voices per rank - at --gpus 8 that IS configs[4] - the ranks' root-bus
         # partials summed by the same reduce, the whole job's audio gated on the oracle golden of this rank count
@@ -1103,7 +1152,7 @@ def main():
                 "kernel": "k_leaf_oscfiltpan", "avg_launch_ms": leaf4, "all_kernels_ms_per_step": all4}}
         r4.be.close()
     dist.destroy_process_group()
-    if rank == 0 and not args.no_engine and args.config == 3 and not custom:
+    if rank == 0 and args.full and not args.no_engine and args.config == 3 and not custom:
         # The north star's claim - 256k voices in realtime on 8 GPUs - as the ENGINE sees it: ONE engine state whose
         # voice tree the drop-in spreads over this run's N GPUs (A2AMD_DEVICES=N: top-level subtrees per GPU, the
         # root-bus partials exchanged per batch, root chain on device 0), a2_Run(4096) throughput and a2_Run(64)
@@ -1115,7 +1164,7 @@ def main():
         rt = eil.get("max_realtime_voices_one_engine_state", {})
         line["max_realtime_voices"] = {"n_gpus": world, "units": rt.get("units"), "units+walk": rt.get("units+walk"),
                                        "what": rt.get("what")}
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         # (one rank's share of the job on this box's host cores; the other ranks are done)
         line["cpu_baseline"] = cpu_baseline(cfg["voices"], cfg["chain"], cfg["groups"])
         line["cpu_baseline"]["sample"] += "; one rank's share of the job (%d of %d voices)" % (cfg["voices"], cfg["voices"] * world)

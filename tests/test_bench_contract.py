@@ -4,9 +4,10 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
-from conftest import ROOT
+from conftest import ROOT, fnv1a_fragments
 
 REQUIRED = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
             "vs_baseline", "dtype", "data", "config", "roofline", "roofline_valu"}
@@ -16,7 +17,7 @@ REQUIRED = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step
 def test_bench_prints_one_contract_line():
     """Default run = BASELINE configs[3] at full size, every step's audio delivered to
     the host, the steps the oracle golden covers compared hash by hash."""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "6", "--warmup", "3",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "6", "--warmup", "3", "--full",
                         "--no-cpu-baseline", "--no-engine"], capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip().startswith("{")]
@@ -52,7 +53,7 @@ def test_bench_line_is_alone_on_stdout_under_torchrun():
     stdout (bench.py points fd 1 at stderr until it prints it)."""
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
                         "--master-addr", "127.0.0.1", "--master-port", "29541", os.path.join(ROOT, "bench.py"),
-                        "--gpus", "1", "--steps", "4", "--warmup", "2", "--no-cpu-baseline", "--config", "1"],
+                        "--gpus", "1", "--steps", "4", "--warmup", "2", "--full", "--no-cpu-baseline", "--config", "1"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT,
                        env=dict(os.environ, A2AMD_BENCH_FORCE_DIST="1"))
     assert r.returncode == 0, r.stderr[-2000:]
@@ -61,6 +62,37 @@ def test_bench_line_is_alone_on_stdout_under_torchrun():
     assert len(lines[0]) < 4096, len(lines[0])
     d = json.loads(lines[0])
     assert REQUIRED <= set(d) and d["n_gpus"] == 1 and d["value"] > 0
+
+
+PLAIN = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+         "vs_baseline", "dtype", "data", "config"}
+
+
+@pytest.mark.gpu
+def test_plain_bench_run_times_the_steps_and_dumps_the_last_one(tmp_path):
+    """A plain run (no --full) times exactly --steps steps and prints the contract line without the --full objects;
+    --dump-outputs writes the last timed step's master bus, which is the oracle golden's step for step."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=900, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip().startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert PLAIN <= set(d), PLAIN - set(d)
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["value"] > 0
+    assert d["unit"] == "voice-samples/s" and d["dtype"] == "int32" and d["higher_is_better"] is True
+    assert not {"roofline", "roofline_valu", "cpu_baseline", "engine_in_loop", "other_configs", "realtime"} & set(d)
+    # the value is the timed steps' voice-samples over their time
+    B = d["config"]["fragments_per_step"]
+    assert d["value"] == pytest.approx(65536 * B * 64 * 3 / (d["ms_per_step"] * 3e-3), rel=1e-4)
+    out = np.load(os.path.join(str(tmp_path), "master_bus.npy"))
+    assert out.dtype == np.float64 and out.shape == (2, B * 64) and out.any()
+    pcm = out.astype(np.int32)
+    assert np.array_equal(pcm.astype(np.float64), out)
+    # step 0 + 1 warm-up + 3 timed: the last timed step is step 4
+    import bench
+    gold = np.load(bench.golden_path(65536, "osc2-pan", 256))
+    assert np.array_equal(fnv1a_fragments(pcm), gold[4 * B:5 * B])
 
 
 def test_bench_refuses_without_gpu():

@@ -5,7 +5,7 @@ O=gpurun_out/filt_sweep; mkdir -p $O; : > $O/sweep.jsonl
 for lib in tools/ubench/variants/liba2amd_W*.so; do
   tag=$(basename $lib .so | sed 's/liba2amd_//')
   for fvpw in ${FVPWS:-32 48 64}; do
-    out=$(A2AMD_LIB=$PWD/$lib A2AMD_FVPW=$fvpw python bench.py --config ${CFG:-2} --steps 20 --warmup 3 --no-extra --no-cpu-baseline --no-engine --no-realtime 2>&1 | tail -n 1)
+    out=$(A2AMD_LIB=$PWD/$lib A2AMD_FVPW=$fvpw python bench.py --config ${CFG:-2} --steps 20 --warmup 3 --full --no-extra --no-cpu-baseline --no-engine --no-realtime 2>&1 | tail -n 1)
     echo "$out" | python -c "
 import json,sys
 try:

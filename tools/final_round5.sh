@@ -5,7 +5,7 @@ REPO=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$REPO/gpurun_out/round5_final
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-python $REPO/bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err
+python $REPO/bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
 cd $REPO
 O=$OUT/final_soak_2.txt; : > $O
 run() { echo "== $*" >> $O; "$@" 2>&1 | tail -3 >> $O; }

@@ -4,7 +4,7 @@ cd "$(dirname "$0")/.."
 O=gpurun_out/o2_sweep; mkdir -p $O; : > $O/sweep.jsonl
 run() { # tag, env...
   local tag=$1; shift
-  out=$(env "$@" python bench.py --config 3 --steps 12 --warmup 3 --no-extra --no-cpu-baseline --no-engine --no-realtime 2>&1 | tail -n 1)
+  out=$(env "$@" python bench.py --config 3 --steps 12 --warmup 3 --full --no-extra --no-cpu-baseline --no-engine --no-realtime 2>&1 | tail -n 1)
   echo "$out" | python -c "
 import json,sys
 try:

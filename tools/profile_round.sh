@@ -7,7 +7,7 @@ REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$REPO/gpurun_out/round
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-B="python $REPO/bench.py"
+B="python $REPO/bench.py --full"
 
 # 1. the bench line (default = BASELINE configs[1]) twice, and its kernel trace
 $B > $OUT/bench_default.json 2> $OUT/bench_default.err

@@ -7,7 +7,7 @@ REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$REPO/gpurun_out/round2
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-B="python $REPO/bench.py"
+B="python $REPO/bench.py --full"
 QUICK=${1:-}
 
 # 1. the bench line (default = BASELINE configs[3], configs[1]/[2] as extra keys), and the

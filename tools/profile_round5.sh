@@ -7,7 +7,7 @@ REPO=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$REPO/gpurun_out/round5
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-B="python $REPO/bench.py"
+B="python $REPO/bench.py --full"
 
 # 1. the bench line, and the kernel trace of the same command (without the engine / CPU legs)
 $B > $OUT/bench_default.json 2> $OUT/bench_default.err

@@ -1,7 +1,7 @@
 #!/bin/bash
 # configs[1]: where a 69-74 us step goes (graph or plain launches; the stream's timeline), and the filter kernel's cycle counters
 cd $GRAFT_REPO_ROOT; O=gpurun_out/r03g; mkdir -p $O
-for e in "X=1" "A2AMD_NO_GRAPH=1"; do env $e python bench.py --config 1 --steps 400 --warmup 20 --no-extra --no-cpu-baseline --no-engine --no-realtime 2>/dev/null | tail -n 1 | python -c "
+for e in "X=1" "A2AMD_NO_GRAPH=1"; do env $e python bench.py --config 1 --steps 400 --warmup 20 --full --no-extra --no-cpu-baseline --no-engine --no-realtime 2>/dev/null | tail -n 1 | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); print('$e', d['value'], d['ms_per_step'], d['roofline']['all_kernels_ms_per_step'], d['parity_vs_golden'])"; done
 A2AMD_LIB=$PWD/tools/ubench/variants/liba2amd_prof.so python bench.py --config 2 --steps 12 --warmup 4 --no-extra --no-cpu-baseline --no-engine --no-realtime 2>&1 | grep "^block" | tail -n 34 > $O/filt_prof.txt; cat $O/filt_prof.txt
 cd /tmp && export TMPDIR=/tmp && rm -rf /tmp/tr && rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d /tmp/tr -- python $GRAFT_REPO_ROOT/bench.py --config 1 --steps 60 --warmup 20 --no-extra --no-cpu-baseline --no-engine --no-realtime > /tmp/tr.log 2>&1
