@@ -217,12 +217,44 @@ struct A2DParams {
 	int32_t        *fmstate;	// [fm slot][A2D_FMSTATE]
 	const uint32_t *fmsine;		// 2048 x {s[i], s[i+1]-s[i]} packed 16:16, fm.c:493-501
 	int32_t *xio;			// xinsert client slots: [slot]{ tap[batch][ch][64], inject[batch][ch][64] }
+	const uint32_t *nseed;		// [fragment][nnoise]: the engine's RNG word in front of a noise oscillator's default window, where
+					// the batch has device-seeded fragments (a2amd_fragment_repeat_noise; k_noise_seeds), or null
+	const int32_t  *nslot;		// [unit]: the oscillator's column of nseed + 1 (0: none; only read where nseed is set)
+	int32_t         nnoise;
 	int32_t         nfrags;
 	int32_t         samplerate;
 	int32_t         debug;		// A2AMD_DEBUG ablation bits (perf experiments only)
 	uint8_t         fragframes[A2D_MAXBATCH];
 	uint16_t        fragstart[A2D_MAXBATCH];	// frames before each fragment
 };
+
+// A noise oscillator's default window - a fragment without records for its voice - takes the engine's RNG word from
+// the batch's seed table (a window the engine called for carries an R_NOISESEED record instead).
+// Invariant (the host's: a2amd_fragment_repeat_noise, upload()): in a batch with nseed set, a noise oscillator meets a
+// fragment without records for its voice only inside a stretch that lists it - every other window of a noise oscillator
+// is one the engine called for - so the cell read here was written by the seed pass.  nslot is cleared for every such
+// batch before the pass fills it in: an oscillator without a column in THIS batch reads 0 and keeps its seed.
+#ifdef __HIPCC__
+static inline __host__ __device__ bool a2d_noise_seed(const A2DParams &p, int f, int ui, unsigned *seed)
+{
+	if(!p.nseed)
+		return false;
+	const int k = p.nslot[ui];
+	if(k <= 0 || k > p.nnoise)
+		return false;
+	*seed = p.nseed[(size_t)f * (size_t)p.nnoise + (size_t)(k - 1)];
+	return true;
+}
+#endif
+
+// a2amd_noise.hip: the seed pass.  One settled noise oscillator of a stretch of device-seeded fragments, in walk order:
+// phase and increment as the stretch finds them, its unit, its column of the batch's seed table.
+struct A2DNoiseOsc { uint32_t ph_lo, ph_hi, dphase; int32_t unit, slot, pad[3]; };
+// seed[(f0 + j) * stride + osc[k].slot] = 'start' advanced by the draws of all n oscillators over fragments [0, j) of the
+// stretch and of oscillators < k in fragment j (count fragments of 'frames' frames each); nslot[osc[k].unit] = slot + 1.
+// seed holds seed_words words, nslot nunits entries: an entry that would land outside is dropped.
+int a2d_launch_noise_seeds(const A2DNoiseOsc *osc, int n, uint32_t start, int f0, int count, unsigned frames,
+		uint32_t *seed, int stride, size_t seed_words, int32_t *nslot, int nunits, void *stream);
 
 // a2amd_vm.hip: the count pass (emit = 0) or the emit pass of the VM kernel
 int a2d_launch_vm(const A2DVmParams &vp, int emit, void *stream);

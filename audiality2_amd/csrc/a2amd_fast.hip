@@ -1690,8 +1690,19 @@ DEV void recs_body(const A2DParams *__restrict__ pp, const int *__restrict__ lis
 				if((int)A2D_RFRAG(head) != f || rc >= re) {
 					// no records in this fragment: the engine called Process(0, frames)
 					// once on every unit (core.c:1875-1876)
-					if(active)
+					if(active) {
+						// (a noise oscillator's default window: a device-seeded fragment - the batch's seed table)
+						if(p.nseed) {
+#pragma unroll
+							for(int o = 0; o < NOSC; ++o)
+								if(os[o].mode == A2D_OSC_NOISE) {
+									unsigned sd;
+									if(a2d_noise_seed(p, f, rdl(uu[o], v), &sd))
+										os[o].seed = sd;
+								}
+						}
 						window(0, n);
+					}
 				} else {
 					do {
 						const int value = cur.y;

@@ -108,6 +108,7 @@ void a2amd_close(a2amd_ctx *c)
 		hipEventDestroy(c->grp_ev);
 	hipFree(c->d_voices.d); hipFree(c->d_vext.d); hipFree(c->d_udesc.d); hipFree(c->d_ustate.d); hipFree(c->d_ustage.d);
 	hipFree(c->d_vactive.d); hipFree(c->d_runs.d); hipFree(c->d_recs.d);
+	hipFree(c->d_nseed.d); hipFree(c->d_nslot.d);
 	hipFree(c->d_win.d); hipFree(c->d_wext.d); hipFree(c->d_wscr.d); hipFree(c->d_wrc.d); hipFree(c->d_widx.d); hipFree(c->d_wtop);
 	if(c->h_wtop)
 		hipHostFree(c->h_wtop);
@@ -453,6 +454,7 @@ int a2amd_fragment(a2amd_ctx *c, unsigned frames)
 	if(!c->nfrags)
 		c->vm.batch_time = c->walk_time;	// (the device VM's clock, a2amd_vm.cpp)
 	c->cur_frag = c->nfrags++;
+	c->walk_serial = c->serial_base + c->cur_frag;	// (a2amd_fragment_repeat[_noise] put it back)
 	c->fragframes[c->cur_frag] = frames;
 	c->fragbase[c->cur_frag] = 0;
 	c->frag_open = true;
@@ -489,15 +491,122 @@ int a2amd_fragment_repeat(a2amd_ctx *c, unsigned frames, unsigned count)
 	if(c->n_clients)
 		return c->fail(A2AMD_EUNSUPPORTED, "fragment_repeat with clients on %d xinsert / xsink / xsource "
 				"unit(s): their callbacks need every window", c->n_clients);
+	const long long walked = c->walk_serial;
 	for(unsigned i = 0; i < count; ++i) {
-		if(int r = a2amd_fragment(c, frames))
+		if(int r = a2amd_fragment(c, frames)) {
+			c->walk_serial = walked;
 			return r;
+		}
 		// every live voice gets the default window: nothing to record, but
 		// tell close_fragment() that nobody was skipped
 		c->frag_open = false;
 		c->walk_time += frames;
 		c->prev_frames = frames;
 	}
+	c->walk_serial = walked;
+	return A2AMD_OK;
+}
+
+// ---- the engine's noise generator in closed form ---------------------------------------
+// a2_Noise: s = s * 1566083941 + 1.  n steps of an affine map are one affine map; squaring it bit by
+// bit of n: (A, C) o (A, C) = (A * A, A * C + C) mod 2^32.
+uint32_t a2amd_noise_jump(uint32_t state, uint64_t draws)
+{
+	uint32_t a = 1566083941u, k = 1u;
+	for(; draws; draws >>= 1) {
+		if(draws & 1)
+			state = a * state + k;
+		k = a * k + k;
+		a = a * a;
+	}
+	return state;
+}
+
+// wtosc_noise, wtosc.c:140-145: a frame draws when the increment is at least 2^23 or its step carries
+// into bit 23 of the phase - over a window, a difference of two quotients
+uint64_t a2amd_noise_draws(uint64_t phase, uint32_t dphase, unsigned frames)
+{
+	if(dphase >= (1u << 23))
+		return frames;
+	return ((phase + (uint64_t)frames * dphase) >> 23) - (phase >> 23);
+}
+
+int a2amd_fragment_repeat_noise(a2amd_ctx *c, unsigned frames, unsigned count, uint32_t *noisestate)
+{
+	if(!noisestate)
+		return c->fail(A2AMD_EINVAL, "fragment_repeat_noise: no noise state");
+	if(c->comm || c->dist_local)
+		return c->fail(A2AMD_EUNSUPPORTED, "fragment_repeat_noise in a distributed or grouped context: one generator, "
+				"several contexts, no defined order");
+	if(c->n_cutoff_ramps)
+		return c->fail(A2AMD_EUNSUPPORTED, "fragment_repeat_noise with %d cutoff ramps in flight", c->n_cutoff_ramps);
+	if(c->n_clients)
+		return c->fail(A2AMD_EUNSUPPORTED, "fragment_repeat_noise with clients on %d xinsert / xsink / xsource "
+				"unit(s): their callbacks need every window", c->n_clients);
+	// (what a2amd_fragment() would refuse halfway through the stretch)
+	if(!frames || frames > A2D_FRAG)
+		return c->fail(A2AMD_EINVAL, "fragment of %u frames", frames);
+	if(!c->stack.empty())
+		return c->fail(A2AMD_ESTATE, "fragment inside an inline window");
+	if(c->uploaded)
+		return c->fail(A2AMD_ESTATE, "batch already uploaded; finish the render first");
+	if((uint64_t)c->nfrags + count > c->cfg.max_batch)
+		return c->fail(A2AMD_ESTATE, "more than max_batch=%u fragments without a render", c->cfg.max_batch);
+	// the oscillators, in the order the calls of the last walked fragment met them
+	int listed = 0;
+	const bool fresh = c->noise_order_serial == c->walk_serial;
+	if(fresh)
+		for(int ui : c->noise_order) {
+			const HUnit &u = c->units[ui];
+			if(!u.live || u.mode != A2D_OSC_NOISE || u.noise_serial != c->noise_order_serial)
+				continue;	// (gone, or switched to a wave since)
+			if(!u.dphase || u.p.timer || u.p_ramping)
+				return c->fail(A2AMD_EUNSUPPORTED, "fragment_repeat_noise: the pitch of noise oscillator %d is moving", ui);
+			// a record made since the last fragment was closed (a write between two stretches) belongs to the first
+			// fragment of this one: the voice would have records there, no default window and no seed
+			const HVoice &v = c->voices[u.voice];
+			if(!c->frag_open && !v.recs.empty() && (int)A2D_RFRAG(v.recs.back().head) >= c->nfrags)
+				return c->fail(A2AMD_ESTATE, "fragment_repeat_noise: a write to the voice of noise oscillator %d since the last "
+						"fragment was closed: walk a fragment by calls first", ui);
+			++listed;
+		}
+	if(listed != c->n_noise)
+		return c->fail(A2AMD_ESTATE, "fragment_repeat_noise: %d of %d live noise oscillators were processed by calls in "
+				"the last walked fragment: their place in the walk is not known", listed, c->n_noise);
+	if(!count)
+		return A2AMD_OK;
+	if(listed) {
+		const uint64_t span = (uint64_t)frames * count;
+		uint64_t draws = 0;
+		a2amd_ctx::NoiseStretch st = { c->nfrags, (int)count, frames, *noisestate, c->noise_osc.size(), (size_t)listed };
+		for(int ui : c->noise_order) {
+			HUnit &u = c->units[ui];
+			if(!u.live || u.mode != A2D_OSC_NOISE || u.noise_serial != c->noise_order_serial)
+				continue;
+			if(u.nslot_batch != c->serial_base) {
+				u.nslot_batch = c->serial_base;
+				u.nslot = c->noise_slots++;
+			}
+			const A2DNoiseOsc o = { (uint32_t)u.phase, (uint32_t)(u.phase >> 32), u.dphase, ui, u.nslot, { 0, 0, 0 } };
+			c->noise_osc.push_back(o);
+			// (the counts of consecutive windows telescope: the whole stretch at once)
+			draws += a2amd_noise_draws(u.phase, u.dphase, (unsigned)span);
+			u.phase += span * u.dphase;
+		}
+		*noisestate = a2amd_noise_jump(*noisestate, draws);
+		c->noise_st.push_back(st);
+	}
+	const long long walked = c->walk_serial;
+	for(unsigned i = 0; i < count; ++i) {
+		if(int r = a2amd_fragment(c, frames)) {
+			c->walk_serial = walked;
+			return r;
+		}
+		c->frag_open = false;
+		c->walk_time += frames;
+		c->prev_frames = frames;
+	}
+	c->walk_serial = walked;
 	return A2AMD_OK;
 }
 
@@ -1155,6 +1264,17 @@ int a2amd_unit_process(a2amd_ctx *c, int ui, unsigned offset, unsigned frames, u
 			if(!noisestate)
 				return c->fail(A2AMD_EINVAL, "noise oscillator needs the engine's noise state");
 			push_rec(c, vi, R_NOISESEED, u.chainpos, 0, (int)*noisestate, 0, 0);
+			{	// its place in this fragment's walk (a2amd_fragment_repeat_noise)
+				const long long serial = c->serial_base + c->cur_frag;
+				if(c->noise_order_serial != serial) {
+					c->noise_order.clear();
+					c->noise_order_serial = serial;
+				}
+				if(u.noise_serial != serial) {
+					u.noise_serial = serial;
+					c->noise_order.push_back(ui);
+				}
+			}
 			shadow_run_pitch(c, u, frames);
 			uint64_t end = u.phase + (uint64_t)frames * u.dphase;
 			uint64_t draws = u.dphase >= (1u << 23) ? frames : (end >> 23) - (u.phase >> 23);

@@ -146,6 +146,10 @@ struct HUnit {
 	int p_ramping = 0;
 	uint64_t phase = 0;
 	Ramp p = {0, 0, 0, 0};
+	// noise: serial of the fragment in which a call last processed it (a2amd_ctx::noise_order), and its column of the seed
+	// table of the batch with this serial_base (a2amd_fragment_repeat_noise)
+	long long noise_serial = -1, nslot_batch = -1;
+	int nslot = -1;
 	// --- second line ---
 	// filter12 shadow: the cutoff ramper never leaves the host
 	Ramp cutoff = {0, 0, 0, 0};
@@ -200,7 +204,8 @@ struct HVoice {
 	// kernels take a voice that is not settled fragment by fragment on the scalar unit (4x a settled one)
 	uint64_t moving_until = 0;
 	bool listed_moving = false;	// in a2amd_ctx::moving
-	long long moving_run = -1;	// serial_base of the batch in which upload() gave it the stand-in record run
+	long long moving_run = -1;	// serial_base of the batch in which upload() gave it the stand-in record run (gliding, or a
+					// noise voice whose windows are seeded on the device and that has no record of its own)
 	long long dynf2_run = -1;	// ... in which it was put on the records kernels' list of 2 x wtosc-filter12-panmix voices
 };
 
@@ -401,6 +406,18 @@ struct a2amd_ctx {
 	int n_started_live = 0;			// voices the engine is walking
 	int walked_started = 0;			// ... of which it has walked this many in the open fragment
 	int n_noise = 0, n_cutoff_ramps = 0;
+	// a2amd_fragment_repeat_noise: the noise oscillators in the order the calls of fragment noise_order_serial processed
+	// them; walk_serial: the most recent fragment opened by a2amd_fragment() itself (walked by calls)
+	std::vector<int> noise_order;
+	long long noise_order_serial = -1, walk_serial = -2;
+	// ... and this batch's device-seeded stretches: fragments [f0, f0 + count) of 'frames' frames, the generator word in
+	// front of them, their oscillators in noise_osc[first, first + n); noise_slots: columns of the batch's seed table
+	struct NoiseStretch { int f0, count; unsigned frames; uint32_t start; size_t first, n; };
+	std::vector<NoiseStretch> noise_st;
+	std::vector<A2DNoiseOsc> noise_osc;
+	int noise_slots = 0;
+	DevBuf<uint32_t> d_nseed;	// [fragment][noise_slots]
+	DevBuf<int32_t> d_nslot;	// [unit]
 	// Self-cleaning buses: when every bus is read by k_bus_driver (its owner is a plain
 	// driver chain without records this batch), that kernel zeroes what it read and the
 	// root stores the master bus instead of adding to it - the batch needs no memset.
@@ -554,7 +571,7 @@ struct a2amd_ctx {
 	// the window kernels (a2amd_win.hip): a slab's slots (one per fragment and voice), the pool of further
 	// windows, where each voice's begin per fragment, the pool counter + overflow flag
 	std::vector<int> moving;	// voices with moving_until set
-	size_t n_moving_listed = 0;	// ... of which this batch's upload() gave the stand-in record run
+	size_t n_moving_listed = 0;	// voices this batch's upload() gave the stand-in record run: gliding ones, device-seeded noise voices
 	DevBuf<int> d_win, d_wext, d_wrc, d_wscr;	// (d_wscr: k_vm_win's rows of parked windows, A2D_VMW_ROW per voice)
 	DevBuf<unsigned> d_widx;
 	unsigned *d_wtop = nullptr;	// [2 sets]{ pool counter, overflow flag }

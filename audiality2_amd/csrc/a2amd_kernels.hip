@@ -1095,8 +1095,19 @@ void k_voices(const A2DParams *__restrict__ pp, const int *__restrict__ list, in
 			if(!explicit_) {
 				// no records: the engine called Process(0, frames)
 				// once on every unit (core.c:1875-1876)
-				if(active)
+				if(active) {
+					// (a noise oscillator's default window: a device-seeded fragment - the batch's seed table)
+					if(p.nseed) {
+						for(int u = 0; u < v.nunits; ++u)
+							if(A2D_KIND(p.udesc[v.unit[u]]) == A2D_WTOSC && c.l->us[u][OW_MODE] == A2D_OSC_NOISE) {
+								unsigned sd;
+								if(lane == 0 && a2d_noise_seed(p, f, v.unit[u], &sd))
+									c.l->us[u][OW_SEED] = (int)sd;
+							}
+						lds_sync();
+					}
 					process_window(c, v, 0, nframes);
+				}
 			} else {
 				for(; r0 < r1 && (int)A2D_RFRAG(p.recs[r0].head) == f; ++r0) {
 					const A2DRec r = p.recs[r0];

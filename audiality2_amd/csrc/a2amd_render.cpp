@@ -57,6 +57,9 @@ int a2amd_render(a2amd_ctx *c, unsigned phases, int32_t *const *out, unsigned ca
 	double t0 = timing ? now_us() : 0;
 	if(!c->stack.empty())
 		return c->fail(A2AMD_ESTATE, "render inside an inline window");
+	if((phases & A2AMD_RENDER_KEEP) && !c->noise_st.empty())
+		return c->fail(A2AMD_EUNSUPPORTED, "A2AMD_RENDER_KEEP on a batch with device-seeded noise windows "
+				"(a2amd_fragment_repeat_noise): a re-run would need a new generator word");
 	close_fragment(c);
 	unsigned total = 0;
 	for(int f = 0; f < c->nfrags; ++f)
@@ -353,6 +356,9 @@ int a2amd_replay(a2amd_ctx *c, unsigned steps)
 	const int GRAPH_STEPS = 8;
 	if(!c->uploaded || !c->nfrags)
 		return c->fail(A2AMD_ESTATE, "replay without an uploaded batch");
+	if(!c->noise_st.empty())
+		return c->fail(A2AMD_EUNSUPPORTED, "replay of a batch with device-seeded noise windows "
+				"(a2amd_fragment_repeat_noise): a re-run would need a new generator word");
 	for(int vi = 0; vi < (int)c->voices.size(); ++vi)
 		if(!c->voices[vi].recs.empty())
 			return c->fail(A2AMD_ESTATE, "replay of a batch that carries command records");

@@ -197,8 +197,10 @@ void sync_voice_mirror(a2amd_ctx *c, int vi)
 	m.own_nch = v.own_nch;
 }
 
-// what the wavetable leaf kernels play: mip-mapped waves, nothing, and - k_leaf_recs only, but a noise
-// oscillator's every window carries an R_NOISESEED record, so the quiet kernels never see one - noise
+// what the wavetable leaf kernels play: mip-mapped waves, nothing, and - k_leaf_recs / the window kernels only - noise.
+// The quiet kernels never see a noise oscillator: every window the engine calls for carries an R_NOISESEED record, and
+// a voice whose noise windows are seeded on the device (a2amd_fragment_repeat_noise) is given a stand-in record run
+// by upload() in a batch in which it has no record of its own.
 
 // wtosc (mip-mapped wave playing) -> panmix 1->2 adding into the output bus
 bool is_oscpan_chain(const a2amd_ctx *c, const HVoice &v)
@@ -327,7 +329,7 @@ int upload(a2amd_ctx *c)
 				memcmp(c->fragframes, c->blob_frames, (size_t)c->nfrags * sizeof(unsigned)) ? 10 : 12;
 		dbg_why()[why] += 1;
 	}
-	if(c->blob_quiet && c->with_recs.empty() && c->prev_with_recs.empty() && c->moving.empty() && !c->voices_dirty &&
+	if(c->blob_quiet && c->with_recs.empty() && c->prev_with_recs.empty() && c->moving.empty() && c->noise_st.empty() && !c->voices_dirty &&
 			!c->udesc_dirty && !c->waves_dirty && !c->lists_dirty && !c->ptab_dirty && !c->vm.list_dirty &&
 			c->dirty_voices.empty() && c->fbd_to_zero.empty() && c->bus_used <= c->d_busmem.cap) {
 		bool inject = false;
@@ -353,6 +355,8 @@ int upload(a2amd_ctx *c)
 			// stay valid while the NUMBER of fragments - their launch shapes - is the same.
 			A2DParams p = c->hparams;
 			p.nfrags = c->nfrags;
+			p.nseed = nullptr;	// (no device-seeded noise windows in a quiet batch)
+			p.nnoise = 0;
 			memset(p.fragframes, 0, sizeof(p.fragframes));
 			memset(p.fragstart, 0, sizeof(p.fragstart));
 			for(int f = 0, acc = 0; f < c->nfrags; ++f) {
@@ -398,6 +402,11 @@ int upload(a2amd_ctx *c)
 	if(int r = grow(c, c->d_ustage, c->d_ustate.cap, A2D_USTATE, false)) return r;
 	if(int r = grow(c, c->d_vactive, nv, 1, true)) return r;
 	if(int r = grow(c, c->d_runs, nv, 1, true)) return r;
+	if(!c->noise_st.empty()) {
+		// device-seeded noise windows (a2amd_fragment_repeat_noise): the batch's seed table and the oscillators' columns
+		if(int r = grow(c, c->d_nseed, (size_t)c->nfrags * (size_t)c->noise_slots, 1, false)) return r;
+		if(int r = grow(c, c->d_nslot, c->d_ustate.cap, 1, false)) return r;
+	}
 	{
 		const int32_t *before = c->d_busmem.d;
 		if(int r = grow(c, c->d_busmem, c->bus_used, 1, false)) return r;
@@ -544,8 +553,28 @@ int upload(a2amd_ctx *c)
 	// quiet kernels skip and the control pass never consumes: default windows throughout.
 	static const bool no_moving = getenv("A2AMD_NO_MOVING") != nullptr;
 	c->n_moving_listed = 0;
+	int nop_at = -1;
+	// the stand-in run for voice vi (no records of its own this batch): used for gliding voices here and for
+	// device-seeded noise voices below
+	auto give_stand_in = [&](int vi) {
+		HVoice &v = c->voices[vi];
+		if(nop_at < 0) {
+			nop_at = (int)recs.size();
+			A2DRec nop = { A2D_HEAD(0xffff, R_NOP, 0, 0), 0, 0, 0 };
+			recs.push_back(nop);
+		}
+		const A2DRun r = { nop_at, 1 };
+		sc_idx.resize(nsc_used + 1 + c->prev_with_recs.size());
+		sc_val.resize(sc_idx.size());
+		sc_idx[nsc_used] = vi;
+		sc_val[nsc_used++] = r;
+		now.resize(nnow + 1);
+		now[nnow++] = vi;
+		v.moving_run = c->serial_base;
+		v.listed_recs = true;
+		++c->n_moving_listed;
+	};
 	if(!c->moving.empty()) {
-		int nop_at = -1;
 		const uint64_t t0 = c->vm.batch_time;	// walk_time when this batch began
 		for(size_t i = 0; i < c->moving.size();) {
 			const int vi = c->moving[i];
@@ -564,22 +593,20 @@ int upload(a2amd_ctx *c)
 			if(no_moving || !v.recs.empty() || v.vm >= 0 || c->lists_dirty || v.mode_mix || !v.resolved ||
 					!(v.cls == CLS_OSCPAN || v.cls == CLS_OSC2PAN || v.cls == CLS_OSCFILTPAN || v.cls == CLS_OSC2FILTPAN))
 				continue;
-			if(nop_at < 0) {
-				nop_at = (int)recs.size();
-				A2DRec nop = { A2D_HEAD(0xffff, R_NOP, 0, 0), 0, 0, 0 };
-				recs.push_back(nop);
-			}
-			const A2DRun r = { nop_at, 1 };
-			sc_idx.resize(nsc_used + 1 + c->prev_with_recs.size());
-			sc_val.resize(sc_idx.size());
-			sc_idx[nsc_used] = vi;
-			sc_val[nsc_used++] = r;
-			now.resize(nnow + 1);
-			now[nnow++] = vi;
-			v.moving_run = c->serial_base;
-			v.listed_recs = true;
-			++c->n_moving_listed;
+			give_stand_in(vi);
 		}
+	}
+	// Voices with a noise oscillator in a device-seeded stretch (a2amd_fragment_repeat_noise) and no record in the whole
+	// batch: the same stand-in run keeps them with the kernels that regenerate a window's draws from a seed - the window
+	// kernels / k_leaf_recs for the four wavetable classes, the general kernel (which takes its voices with or without
+	// records) for any other chain.  The quiet kernels know no noise.
+	// (unlike a gliding voice, which the quiet kernels can take the slow way when its class is not known for sure -
+	// lists_dirty, mode_mix - a noise voice gets the run whatever its class: the quiet kernels must never see one)
+	for(const A2DNoiseOsc &o : c->noise_osc) {
+		const int vi = c->units[o.unit].voice;
+		const HVoice &v = c->voices[vi];
+		if(v.recs.empty() && v.moving_run != c->serial_base && (v.live || v.dying))
+			give_stand_in(vi);
 	}
 	now.resize(nnow);
 	c->with_recs.swap(now);
@@ -841,6 +868,11 @@ int upload(a2amd_ctx *c)
 	p.fmstate = c->d_fmstate.d;
 	p.xio = c->d_xio.d;
 	p.fmsine = c->d_fmsine;
+	if(!c->noise_st.empty()) {
+		p.nseed = c->d_nseed.d;
+		p.nslot = c->d_nslot.d;
+		p.nnoise = c->noise_slots;
+	}
 	p.nfrags = c->nfrags;
 	p.samplerate = c->cfg.samplerate;
 	p.debug = getenv("A2AMD_DEBUG") ? atoi(getenv("A2AMD_DEBUG")) : 0;
@@ -850,7 +882,7 @@ int upload(a2amd_ctx *c)
 		acc += (int)c->fragframes[f];
 	}
 
-	// the blob: [params | records | scatter indices | scatter runs | exception lists]
+	// the blob: [params | records | scatter indices | scatter runs | exception lists | noise oscillators of the seed pass]
 	auto up256 = [](size_t x) { return (x + 255) & ~(size_t)255; };
 	const size_t nsc = sc_idx.size();
 	const size_t o_recs = up256(sizeof(A2DParams));
@@ -858,7 +890,8 @@ int upload(a2amd_ctx *c)
 	const size_t o_val = o_idx + up256(nsc * sizeof(int));
 	const size_t o_dyn = o_val + up256(nsc * sizeof(A2DRun));
 	// ... and behind what the host makes, room for the records the device VM writes (a2amd_vm.cpp)
-	const size_t host_total = o_dyn + up256(dyn_all.size() * sizeof(int));
+	const size_t o_noise = o_dyn + up256(dyn_all.size() * sizeof(int));
+	const size_t host_total = o_noise + up256(c->noise_osc.size() * sizeof(A2DNoiseOsc));
 	const size_t vm_room = (size_t)vm_blob_room(c);
 	const size_t total = host_total;
 	if(int r = grow(c, c->d_blob, host_total + vm_room * sizeof(A2DRec), 1, false)) return r;
@@ -890,6 +923,8 @@ int upload(a2amd_ctx *c)
 	}
 	if(!dyn_all.empty())
 		memcpy(hb + o_dyn, dyn_all.data(), dyn_all.size() * sizeof(int));
+	if(!c->noise_osc.empty())
+		memcpy(hb + o_noise, c->noise_osc.data(), c->noise_osc.size() * sizeof(A2DNoiseOsc));
 	HIPCHK(c, hipMemcpyAsync(c->d_blob.d, hb, total, hipMemcpyHostToDevice, c->stream));
 	HIPCHK(c, hipEventRecord(c->blob_ev[bi], c->stream));
 	c->blob_busy[bi] = true;
@@ -899,6 +934,14 @@ int upload(a2amd_ctx *c)
 		if(a2d_launch_scatter_runs((const int *)(c->d_blob.d + o_idx), (const A2DRun *)(c->d_blob.d + o_val),
 				(int)nsc, c->d_runs.d, c->stream))
 			return c->fail(A2AMD_EHIP, "scatter launch failed");
+	// the seed pass: every device-seeded stretch's generator words, in front of the kernels that render its windows
+	// (the columns are this batch's: an oscillator no stretch of it lists has none - a2d_noise_seed)
+	if(!c->noise_st.empty())
+		HIPCHK(c, hipMemsetAsync(c->d_nslot.d, 0, c->d_nslot.cap * sizeof(int32_t), c->stream));
+	for(const a2amd_ctx::NoiseStretch &st : c->noise_st)
+		if(const int e = a2d_launch_noise_seeds((const A2DNoiseOsc *)(c->d_blob.d + o_noise) + st.first, (int)st.n, st.start, st.f0,
+				st.count, st.frames, c->d_nseed.d, c->noise_slots, c->d_nseed.cap, c->d_nslot.d, (int)c->d_nslot.cap, c->stream))
+			return c->fail(A2AMD_EHIP, "noise seed launch failed: %s", hipGetErrorString((hipError_t)e));
 	c->uploaded = true;
 	c->blob_quiet = recs.empty() && dyn_all.empty();
 	c->blob_nfrags = c->nfrags;
@@ -1067,6 +1110,9 @@ void end_batch(a2amd_ctx *c)
 	for(int w : c->deferred_wave_slots)
 		c->free_wave_slots.push_back(w);
 	c->deferred_wave_slots.clear();
+	c->noise_st.clear();
+	c->noise_osc.clear();
+	c->noise_slots = 0;
 	c->nfrags = 0;
 	c->cur_frag = 0;
 	c->frag_open = false;

@@ -141,6 +141,13 @@ DEV void win_ctl_body(const A2DParams *__restrict__ pp, const int *__restrict__ 
 				inrec = true;
 			}
 			op = inrec ? (int)A2D_ROP((unsigned)r.x) : (cv.active ? R_SEG : 0);
+			// (a noise oscillator's default window: a device-seeded fragment - the batch's seed table)
+			if(!inrec && cv.active && p.nseed) {
+#pragma unroll
+				for(int o = 0; o < NOSC; ++o)
+					if(cv.os[o].mode == A2D_OSC_NOISE)
+						a2d_noise_seed(p, f, cv.uu[o], &cv.os[o].seed);
+			}
 			if(inrec && !op)
 				op = R_NOP;
 		}

@@ -117,6 +117,10 @@ class Backend:
             self._voice_process = fn("voice_process", i32, vp, i32, u32, u32, C.POINTER(C.c_uint32))
             self._voice_slot = fn("voice_slot", i32, vp, i32)
             self._default_map = fn("default_map", C.POINTER(C.c_uint8), vp, C.POINTER(u32))
+        # stretches of default windows (the product library only)
+        self._fragment_repeat_noise = None
+        if hasattr(lib, prefix + "fragment_repeat_noise"):
+            self._fragment_repeat_noise = fn("fragment_repeat_noise", i32, vp, u32, u32, C.POINTER(C.c_uint32))
         cfg = a2amd_config(C.sizeof(a2amd_config), samplerate, basepitch, channels,
                            device, max_batch, stream)
         self.ctx = vp()
@@ -153,6 +157,15 @@ class Backend:
 
     def fragment(self, frames):
         return self._chk(self._fragment(self.ctx, frames), "fragment")
+
+    def fragment_repeat_noise(self, frames, count):
+        """`count` further fragments of default windows, settled noise oscillators seeded on the device
+        (a2amd_fragment_repeat_noise): self.noise goes in and comes back as `count` walks by calls would
+        have left it."""
+        if self._fragment_repeat_noise is None:
+            raise RuntimeError(f"this library has no {self.prefix}fragment_repeat_noise")
+        return self._chk(self._fragment_repeat_noise(self.ctx, frames, count, C.byref(self.noise)),
+                         "fragment_repeat_noise")
 
     def unit_init(self, voice_key, kind, flags, nin, nout, wired, transpose=0, wakefrac=0):
         return self._chk(self._unit_init(self.ctx, voice_key, kind, flags, nin, nout, wired,

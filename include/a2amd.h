@@ -389,6 +389,9 @@ int  a2amd_render_group(a2amd_ctx *const *ctxs, int n, unsigned phases, int32_t 
  * the device's when the switch comes.) */
 int  a2amd_fragment_repeat(a2amd_ctx *ctx, unsigned frames, unsigned count);
 
+/* ... and with settled noise oscillators, seeded on the device: a2amd_fragment_repeat_noise(),
+ * include/a2amd_noise.h (included below). */
+
 /* ---- introspection (tests, bench) --------------------------------------*/
 typedef struct a2amd_stats {
 	uint64_t fragments;        /* fragments rendered so far                 */
@@ -413,4 +416,8 @@ int  a2amd_set_profiling(a2amd_ctx *ctx, int on);
 #ifdef __cplusplus
 }
 #endif
+
+/* The noise generator in closed form: a2amd_fragment_repeat_noise(), a2amd_noise_jump(), a2amd_noise_draws(). */
+#include "a2amd_noise.h"
+
 #endif /* A2AMD_H */
