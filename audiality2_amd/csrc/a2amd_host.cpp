@@ -61,6 +61,11 @@ int a2amd_open(const a2amd_config *cfg, a2amd_ctx **out)
 	build_pitch_table(c->ptab);
 	c->no_fast = getenv("A2AMD_NO_FAST") ? atoi(getenv("A2AMD_NO_FAST")) : 0;
 	c->hosttiming = getenv("A2AMD_HOSTTIMING") != nullptr;
+	c->f2vpw = getenv("A2AMD_F2VPW") ? atoi(getenv("A2AMD_F2VPW")) : 0;
+	c->no_moving = getenv("A2AMD_NO_MOVING") != nullptr;
+	c->win_slabs = getenv("A2AMD_WIN_SLABS") ? std::max(1, atoi(getenv("A2AMD_WIN_SLABS"))) : 1;
+	c->o2f_min = getenv("A2AMD_O2F_MIN") ? atoi(getenv("A2AMD_O2F_MIN")) : 512;
+	c->win_min = getenv("A2AMD_WIN_MIN") ? atoi(getenv("A2AMD_WIN_MIN")) : 2048;
 	c->bus_stride_frames = (size_t)c->cfg.max_batch * A2D_FRAG;
 	c->bus_used = c->bus_stride_frames * (size_t)c->cfg.channels;	// master bus at offset 0
 #define OPENCHK(call) do { hipError_t e_ = (call); if(e_ != hipSuccess) { \

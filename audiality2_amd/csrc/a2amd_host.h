@@ -467,6 +467,14 @@ struct a2amd_ctx {
 	std::vector<DepthRange> depth_ranges;	// index = depth
 	bool hosttiming = false;		// A2AMD_HOSTTIMING
 	int no_fast = 0;			// A2AMD_NO_FAST bit mask: 1 wtosc-panmix, 2 wtosc-filter12-panmix, 4 driver chains -> general kernel (debugging / A-B tests)
+	// Switches the tests vary from context to context inside one process: read in a2amd_open(), never through a
+	// function-local static (which keeps the value the first context of the process saw; tests/test_switches.py)
+	int f2vpw = 0;				// A2AMD_F2VPW: voices per workgroup of k_leaf_osc2filtpan (0: the launcher's own choice)
+	bool no_moving = false;			// A2AMD_NO_MOVING: gliding voices get no stand-in record (they stay the quiet kernels')
+	int win_slabs = 1;			// A2AMD_WIN_SLABS: slabs a batch of 16 fragments or more is cut into for the window kernels
+	int o2f_min = 512;			// A2AMD_O2F_MIN: voices of 2 x wtosc-filter12-panmix from which the class has its quiet kernel
+	int win_min = 2048;			// A2AMD_WIN_MIN: record-carrying voices from which the window kernels take over from k_leaf_recs
+	a2amd_batch_info last_batch = {};	// a2amd_last_batch()
 
 	// bus memory allocator (units of int32)
 	size_t bus_stride_frames;

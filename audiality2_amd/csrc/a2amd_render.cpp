@@ -438,6 +438,14 @@ int a2amd_get_stats(a2amd_ctx *c, a2amd_stats *st)
 	return A2AMD_OK;
 }
 
+int a2amd_last_batch(const a2amd_ctx *c, a2amd_batch_info *bi)
+{
+	if(!c || !bi)
+		return A2AMD_EINVAL;
+	*bi = c->last_batch;
+	return A2AMD_OK;
+}
+
 int a2amd_set_profiling(a2amd_ctx *c, int on)
 {
 	if(int r = drain_events(c))

@@ -551,7 +551,7 @@ int upload(a2amd_ctx *c)
 	// unsettled voice fragment by fragment on the scalar unit for the whole batch; the window kernels resolve its
 	// rampers in closed form.  They are given ONE shared stand-in record that belongs to no fragment - a run the
 	// quiet kernels skip and the control pass never consumes: default windows throughout.
-	static const bool no_moving = getenv("A2AMD_NO_MOVING") != nullptr;
+	const bool no_moving = c->no_moving;
 	c->n_moving_listed = 0;
 	int nop_at = -1;
 	// the stand-in run for voice vi (no records of its own this batch): used for gliding voices here and for
@@ -786,7 +786,9 @@ int upload(a2amd_ctx *c)
 			HVoice &v = c->voices[vi];
 			// (close_fragment's R_NOP is the one other record k_leaf_recs takes - as nothing)
 			const bool ok = !no_recs_kernel && !v.mode_mix && !v.fancy_recs;
-			if(ok && v.cls == CLS_OSC2FILTPAN)
+			// (on a list already, whichever: a voice the general kernel takes - dyn_rest - must not be put on dyn_f2 as
+			// well by the small-scene rule below and rendered twice)
+			if(v.cls == CLS_OSC2FILTPAN)
 				v.dynf2_run = c->serial_base;
 			(!ok ? dyn_rest : v.cls == CLS_OSCPAN ? dyn_o1 : v.cls == CLS_OSC2PAN ? dyn_o2 :
 			 v.cls == CLS_OSCFILTPAN ? dyn_f1 : dyn_f2).push_back(vi);
@@ -810,8 +812,7 @@ int upload(a2amd_ctx *c)
 		// (measured: the 60-voice song, 500 s, 2.94 s in round 5 -> 3.53 s with the quiet kernel for its handful of notes,
 		// profiles/r06_song_timing.jsonl).  Below A2AMD_O2F_MIN voices of the class (default 512) every voice of it is the
 		// records / window kernels', as in rounds 2 - 5.
-		static const int o2f_min = getenv("A2AMD_O2F_MIN") ? atoi(getenv("A2AMD_O2F_MIN")) : 512;
-		c->o2f_quiet = c->n_o2f_leaf >= o2f_min;
+		c->o2f_quiet = c->n_o2f_leaf >= c->o2f_min;
 		if(!c->o2f_quiet && c->n_o2f_leaf) {
 			const int at = c->n_fast_leaf + c->n_osc2_leaf + c->n_filt_leaf + c->n_fm_leaf + c->n_leaf;
 			for(int k = 0; k < c->n_o2f_leaf; ++k) {
@@ -1210,7 +1211,7 @@ static int issue_windows(a2amd_ctx *c, const int *const *lists, const int *count
 	// (measured, 16 384 scripted voices x 64 fragments: 0.50 ms as one slab, 0.76 as four - the control pass is as
 	// long as ONE wavefront's walk, and a wavefront that shares its SIMD with seven render wavefronts walks at a
 	// fraction of its pace - so slabs are what the memory bound asks for, not the default)
-	static const int want_slabs = getenv("A2AMD_WIN_SLABS") ? std::max(1, atoi(getenv("A2AMD_WIN_SLABS"))) : 1;
+	const int want_slabs = c->win_slabs;
 	const int nfrags = c->nfrags;
 	// (a taken speculative pass covers the batch in one piece: with it, the lists that do take slots here are not cut
 	// into slabs for the asking - A2AMD_WIN_SLABS - only where the memory bound demands it)
@@ -1219,6 +1220,9 @@ static int issue_windows(a2amd_ctx *c, const int *const *lists, const int *count
 		per = (int)std::max<size_t>(1, budget / nvoices);
 	const int nslabs = (nfrags + per - 1) / per;
 	const bool two = nslabs > 1;
+	c->last_batch.win_slabs = (uint32_t)nslabs;
+	for(int j = 0; j < nj; ++j)
+		c->last_batch.win_voices += (uint32_t)jobs[j].n;
 	const size_t nslots = nvoices * (size_t)per, cap = std::max<size_t>(nrec, 1);
 	size_t slotwords = 0;		// of a slab: every list's slots at its class's size
 	for(int j = 0; j < nj; ++j)
@@ -1495,7 +1499,7 @@ int issue_kernels(a2amd_ctx *c, unsigned phases, hipEvent_t e0, hipEvent_t e1, h
 		bool use_win;
 		{
 			const char *wenv = getenv("A2AMD_WIN");
-			static const int win_min = getenv("A2AMD_WIN_MIN") ? atoi(getenv("A2AMD_WIN_MIN")) : 2048;
+			const int win_min = c->win_min;
 			int nwinv = rtotal;
 			for(int k = 0; k < 3; ++k)
 				nwinv += c->vm.list.empty() ? 0 : c->vm.n_cls[k];
@@ -1505,6 +1509,12 @@ int issue_kernels(a2amd_ctx *c, unsigned phases, hipEvent_t e0, hipEvent_t e1, h
 		static const bool vmwin_ok = !(getenv("A2AMD_VMWIN") && !atoi(getenv("A2AMD_VMWIN")));
 		if(int r = vm_issue(c, use_win && vmwin_ok && !c->vm.fused_off))
 			return r;
+		// a2amd_last_batch(): the lists as upload() made them; the launches below fill in the rest
+		c->last_batch = a2amd_batch_info{};
+		c->last_batch.o2f_class = (uint32_t)c->n_o2f_leaf;
+		c->last_batch.o2f_listed = (uint32_t)c->n_dyn_filt2;
+		c->last_batch.n_moving_listed = (uint32_t)c->n_moving_listed;
+		c->last_batch.general_voices = (uint32_t)c->n_dyn_rest;
 		// The batch's other leaf kernels - the quiet kernels of the classes, the records kernels where the window kernels
 		// are not in use, the general kernel - as a block that runs once: normally behind the window kernels, and
 		// (round 6) from INSIDE issue_windows, between its control passes and its render passes, when a speculative VM
@@ -1585,7 +1595,7 @@ int issue_kernels(a2amd_ctx *c, unsigned phases, hipEvent_t e0, hipEvent_t e1, h
 				// fewest whole rounds of 256 workgroups that allows (16 384 voices: 2 rounds of 32 - measured 1.09 ms per 256
 				// fragments against 3.83 with 48 and 1.50 with 64 voices per workgroup)
 				const int nf = c->n_o2f_leaf;
-				static const int env_vpg = getenv("A2AMD_F2VPW") ? atoi(getenv("A2AMD_F2VPW")) : 0;
+				const int env_vpg = c->f2vpw;
 				const int maxv = a2d_osc2filtpan_max_vpg();
 				const int rounds = std::max(1, (nf + 256 * maxv - 1) / (256 * maxv));
 				const int vpg = env_vpg ? env_vpg : std::min(std::max((nf + 256 * rounds - 1) / (256 * rounds), 1), maxv);
@@ -1593,6 +1603,10 @@ int issue_kernels(a2amd_ctx *c, unsigned phases, hipEvent_t e0, hipEvent_t e1, h
 						c->n_filt_leaf + c->n_fm_leaf + c->n_leaf, nf, vpg, c->stream))
 					return c->fail(A2AMD_EHIP, "2-osc filter leaf launch failed: %s", hipGetErrorString(hipGetLastError()));
 				++c->stats.launches;
+				c->last_batch.o2f_launched = 1;
+				c->last_batch.o2f_voices = (uint32_t)nf;
+				c->last_batch.o2f_max_vpg = (uint32_t)maxv;
+				c->last_batch.o2f_vpg = (uint32_t)std::min(std::max(vpg, 1), 64);	// (the launcher's clamp: a filter wavefront's lanes)
 			}
 			int fm_kinds = 0;
 			for(int k = 0; k < 8; ++k)
@@ -1645,6 +1659,9 @@ int issue_kernels(a2amd_ctx *c, unsigned phases, hipEvent_t e0, hipEvent_t e1, h
 				const int total = rtotal;
 				const int kinds = (counts[0] != 0) + (counts[1] != 0) + (counts[2] != 0) + (counts[3] != 0);
 				if(!use_win) {
+				c->last_batch.recs_voices = (uint32_t)total;
+				if(!c->vm.list.empty())
+					c->last_batch.recs_voices += (uint32_t)(c->vm.n_cls[0] + c->vm.n_cls[1] + c->vm.n_cls[2]);
 				if(kinds > 1 && total <= 4096 && !getenv("A2AMD_RVPW")) {
 					// few voices of several kinds (a song): one launch - on one stream the per-kind
 					// launches would run back to back, each as long as one voice's walk through the batch

@@ -412,6 +412,23 @@ int  a2amd_get_stats(a2amd_ctx *ctx, a2amd_stats *st);
 /* Bracket every batch's kernels with HIP events on the launch stream; the sums
  * appear in a2amd_stats.  Switching it on resets the sums. */
 int  a2amd_set_profiling(a2amd_ctx *ctx, int on);
+/* Which kernels the most recent batch's wavetable leaf voices went to (tests assert the path taken, not only the
+ * audio).  Filled where the launches are issued; a batch replayed from a captured graph keeps the values of its
+ * capture. */
+typedef struct a2amd_batch_info {
+	uint32_t o2f_launched;     /* 1: k_leaf_osc2filtpan (2 x wtosc-filter12-panmix, quiet) was launched */
+	uint32_t o2f_voices;       /* ... over this many voices of the class                                */
+	uint32_t o2f_vpg;          /* ... with this many voices per workgroup                               */
+	uint32_t o2f_max_vpg;      /* ... of at most this many where the launcher chooses (no A2AMD_F2VPW) */
+	uint32_t o2f_class;        /* leaf voices of that class in the scene                                */
+	uint32_t o2f_listed;       /* ... of which the records / window kernels' list holds this many      */
+	uint32_t recs_voices;      /* voices on the lists the records kernels (k_leaf_recs) were given      */
+	uint32_t win_voices;       /* voices on the lists the window kernels were given                     */
+	uint32_t win_slabs;        /* slabs the window kernels cut the batch into (0: not launched)         */
+	uint32_t n_moving_listed;  /* voices given the stand-in record: gliding, device-seeded noise        */
+	uint32_t general_voices;   /* record-carrying leaf voices sent to the general kernel                */
+} a2amd_batch_info;
+int  a2amd_last_batch(const a2amd_ctx *ctx, a2amd_batch_info *bi);
 
 #ifdef __cplusplus
 }

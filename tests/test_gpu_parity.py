@@ -19,6 +19,35 @@ CASES = ["sustain", "filter", "delaybus", "scripted", "edge", "fm", "fmtest3", "
          "td_ramptestenv", "td_evtest", "td_recursetest", "td_microtonal", "td_noisephase", "td_evilnoises"]
 
 
+class BatchInfo(ctypes.Structure):
+    """a2amd_batch_info (include/a2amd.h): which kernels the last batch's wavetable leaf voices went to"""
+    _fields_ = [(n, ctypes.c_uint32) for n in (
+        "o2f_launched", "o2f_voices", "o2f_vpg", "o2f_max_vpg", "o2f_class", "o2f_listed", "recs_voices", "win_voices",
+        "win_slabs", "n_moving_listed", "general_voices")]
+
+    def __repr__(self):
+        return "BatchInfo(" + ", ".join(f"{n}={getattr(self, n)}" for n, _ in self._fields_) + ")"
+
+
+def last_batch(gpu):
+    bi = BatchInfo()
+    gpu.lib.a2amd_last_batch.argtypes = [ctypes.c_void_p, ctypes.POINTER(BatchInfo)]
+    gpu.lib.a2amd_last_batch.restype = ctypes.c_int
+    assert gpu.lib.a2amd_last_batch(gpu.ctx, ctypes.byref(bi)) == 0
+    return bi
+
+
+def is_gpu(be):
+    return hasattr(be.lib, "a2amd_last_batch")
+
+
+def auto_o2f_vpg(n, maxv):
+    """voices per workgroup the launcher deals n voices of 2 x wtosc-filter12-panmix by (issue_kernels, a2amd_sched.cpp):
+    the fewest whole rounds of 256 workgroups with at most maxv voices each"""
+    rounds = max(1, (n + 256 * maxv - 1) // (256 * maxv))
+    return min(max((n + 256 * rounds - 1) // (256 * rounds), 1), maxv)
+
+
 def first_diff(a, b):
     d = np.nonzero(a != b)
     if not len(d[0]):
@@ -253,7 +282,7 @@ def test_fm_leaf_kernel_executes_records(oracle_lib, monkeypatch, vpw):
     assert first_diff(got, want) is None
 
 
-def _wt_script(be, chain, nvoices=300, batches=3, bfrags=16, seed=11, groups=0, walk=False, noise=False):
+def _wt_script(be, chain, nvoices=300, batches=3, bfrags=16, seed=11, groups=0, walk=False, noise=False, on_batch=None):
     """Wavetable voices the way a script drives them (BASELINE variants 2b / 3b):
     control writes between sub-fragment windows - pitch, amplitude, pan, volume
     ramps of all lengths, phase resets, switches between mip-mapped waves and off
@@ -362,6 +391,8 @@ def _wt_script(be, chain, nvoices=300, batches=3, bfrags=16, seed=11, groups=0, 
                     quick.pop(l[k][0], None)
                     del l[k]
         chunks.append(be.render(bfrags * 64))
+        if on_batch:
+            on_batch()
     return np.concatenate(chunks, axis=1)
 
 
@@ -479,7 +510,7 @@ def test_window_and_records_kernels_agree_at_size(monkeypatch, chain, groups):
     records kernels (k_leaf_recs) on the same random script - writes, ramps, sub-fragment windows, births, deaths - at
     the size where the library switches from the one to the other by itself, in one slab and cut into slabs (the
     record cursor carried between them), with one stream and with a stream per list."""
-    outs = {}
+    outs, infos = {}, {}
     for tag, env in (("records", {"A2AMD_WIN": "0"}), ("windows", {"A2AMD_WIN": "1"}),
                      ("slabs", {"A2AMD_WIN": "1", "A2AMD_WIN_SLABS": "3"}), ("auto", {})):
         for k in ("A2AMD_WIN", "A2AMD_WIN_SLABS"):
@@ -487,11 +518,50 @@ def test_window_and_records_kernels_agree_at_size(monkeypatch, chain, groups):
         for k, v in env.items():
             monkeypatch.setenv(k, v)
         gpu = make_gpu(max_batch=64)
-        outs[tag] = _wt_script(gpu, chain, nvoices=5000, batches=2, bfrags=64, groups=groups)
+        infos[tag] = []
+        outs[tag] = _wt_script(gpu, chain, nvoices=5000, batches=2, bfrags=64, groups=groups,
+                               on_batch=lambda: infos[tag].append(last_batch(gpu)))
         gpu.close()
+        print(chain, tag, infos[tag])
+    # the path each leg took (a switch read once per process would make the legs one and the same)
+    for bi in infos["records"]:
+        assert bi.recs_voices > 0 and bi.win_voices == 0 and bi.win_slabs == 0, bi
+    for bi in infos["windows"]:
+        assert bi.win_voices > 0 and bi.recs_voices == 0 and bi.win_slabs == 1, bi
+    for bi in infos["slabs"]:
+        assert bi.win_voices > 0 and bi.recs_voices == 0 and bi.win_slabs == 3, bi      # (64 fragments in slabs of 22)
+    for a, b in zip(infos["records"], infos["windows"]):
+        assert a.recs_voices == b.win_voices, (a, b)
+    for bi in infos["auto"]:
+        assert (bi.win_voices > 0) != (bi.recs_voices > 0), bi
     assert outs["records"].any()
     for tag in ("windows", "slabs", "auto"):
         assert first_diff(outs[tag], outs["records"]) is None, tag
+
+
+@pytest.mark.parametrize("chain,groups", [("osc-pan", 0), ("osc2-pan", 3), ("osc-filter-pan", 2), ("osc2-filter-pan", 0),
+                                          ("osc2-filter-pan", 3)])
+def test_window_kernels_cut_into_slabs_match_oracle(oracle_lib, monkeypatch, chain, groups):
+    """The window kernels with the batch cut into slabs (A2AMD_WIN_SLABS=3: 32 fragments in slabs of 11, 11 and 10; the
+    control pass of slab k + 1 beside the render pass of slab k, the record cursor of every voice carried from slab to
+    slab) against the ORACLE, at a size it follows: the random script of writes, ramps, sub-fragment windows, births and
+    deaths of the records-kernel tests."""
+    monkeypatch.setenv("A2AMD_WIN", "1")
+    monkeypatch.setenv("A2AMD_WIN_SLABS", "3")
+    gpu = make_gpu(max_batch=32)
+    infos = []
+    got = _wt_script(gpu, chain, groups=groups, batches=2, bfrags=32, on_batch=lambda: infos.append(last_batch(gpu)))
+    gpu.close()
+    print(chain, groups, infos)
+    for bi in infos:
+        assert bi.win_slabs == 3 and bi.win_voices > 0 and bi.recs_voices == 0, bi
+        if chain == "osc2-filter-pan":       # (a small scene: every voice of the class is the window kernels')
+            assert not bi.o2f_launched and 0 < bi.o2f_listed and bi.o2f_listed + bi.general_voices <= bi.o2f_class, bi
+    ora = make_oracle(oracle_lib)
+    want = _wt_script(ora, chain, groups=groups, batches=2, bfrags=32)
+    ora.close()
+    assert want.any()
+    assert first_diff(got, want) is None
 
 
 def test_wave_drop_and_pool_reuse(oracle_lib):
@@ -560,14 +630,14 @@ def test_voice_table_grows_between_batches(oracle_lib):
     assert first_diff(outs[0], outs[1]) is None
 
 
-def _scene_fuzz(be, seed, nvoices, batches, bfrags):
+def _scene_fuzz(be, seed, nvoices, batches, bfrags, more_chains=(), on_batch=None):
     """Thousands of voices of mixed classes; in every batch random voices get
     control writes with random timing, some die, new ones arrive: every leaf
     kernel sees quiet, ramping and record-carrying voices side by side."""
     rng = np.random.default_rng(seed)
     sc = synth.Scene(be)
     sc.root()
-    chains = ["osc-pan", "osc-filter-pan", "osc2-pan", "fmmix-pan", "fm2-pan"]
+    chains = ["osc-pan", "osc-filter-pan", "osc2-pan", "fmmix-pan", "fm2-pan"] + list(more_chains)
     g = sc.add_group()
     for i, ch in enumerate(chains):
         sc.add_voices(nvoices // len(chains), chain=ch, total=nvoices, group=g if i == 2 else None)
@@ -586,6 +656,8 @@ def _scene_fuzz(be, seed, nvoices, batches, bfrags):
                         be.unit_write(units[0], 1, synth.fix(float(rng.uniform(-2, 2))), start, dur)
             sc.walk(64)
         chunks.append(be.render(bfrags * 64))
+        if on_batch:
+            on_batch()
         # between batches: some voices die, some are born
         for _ in range(int(rng.integers(0, 12))):
             if len(sc.leaves) > 10:
@@ -605,6 +677,26 @@ def test_scene_fuzz_matches_oracle(oracle_lib, seed, nvoices, bfrags):
     gpu.close()
     ora = make_oracle(oracle_lib)
     want = _scene_fuzz(ora, seed, nvoices, batches, bfrags)
+    ora.close()
+    assert want.any() and first_diff(got, want) is None
+
+
+@pytest.mark.parametrize("seed,nvoices,bfrags,quiet", [(5, 3600, 16, True), (6, 1800, 8, False)])
+def test_scene_fuzz_with_osc2_filter_voices_matches_oracle(oracle_lib, seed, nvoices, bfrags, quiet):
+    """The same fuzz with 2 x wtosc-filter12-panmix as a sixth chain: 600 voices of it (k_leaf_osc2filtpan beside the
+    window kernels: quiet, gliding and record-carrying voices of the class in one batch) and 300 (below A2AMD_O2F_MIN:
+    all of them the window kernels')."""
+    gpu = make_gpu(max_batch=bfrags)
+    infos = []
+    got = _scene_fuzz(gpu, seed, nvoices, 4, bfrags, more_chains=["osc2-filter-pan"], on_batch=lambda: infos.append(last_batch(gpu)))
+    gpu.close()
+    print(seed, infos)
+    for bi in infos:
+        assert bool(bi.o2f_launched) == quiet and bi.o2f_class >= nvoices // 6 - 48, bi
+        assert bi.win_voices > 0 and (quiet or bi.o2f_listed == bi.o2f_class), bi
+    assert any(bi.o2f_listed > 0 for bi in infos)
+    ora = make_oracle(oracle_lib)
+    want = _scene_fuzz(ora, seed, nvoices, 4, bfrags, more_chains=["osc2-filter-pan"])
     ora.close()
     assert want.any() and first_diff(got, want) is None
 
@@ -1002,7 +1094,11 @@ def test_osc2_filter_leaf_launch_shapes_at_bench_batch_match_oracle(oracle_lib, 
         return sc
     gpu = make_gpu(max_batch=256)
     got = _async_steps(gpu, build(gpu), 2, 256)
+    bi = last_batch(gpu)
     gpu.close()
+    print(f2vpw, bi)
+    assert bi.o2f_launched and bi.o2f_voices == 900 and bi.o2f_vpg == f2vpw, bi
+    assert bi.win_voices == 0 and bi.recs_voices == 0 and bi.general_voices == 0, bi
     want = _oracle_fragments(oracle_lib, build, 512)
     assert want.any()
     assert first_diff(got, want) is None
@@ -1020,12 +1116,16 @@ def test_osc2_filter_leaf_paths_mixed_buses_filter_shapes_and_short_fragments(or
     monkeypatch.setenv("A2AMD_F2VPW", str(f2vpw))
     if no_moving:
         monkeypatch.setenv("A2AMD_NO_MOVING", no_moving)
-    outs = []
+    else:
+        monkeypatch.delenv("A2AMD_NO_MOVING", raising=False)
+    outs, infos = [], []
     for be in (make_gpu(max_batch=32), make_oracle(oracle_lib)):
         sc = synth.Scene(be)
         sc.root()
-        groups = [sc.add_bus_group() for _ in range(3)]
-        for g, n in zip(groups, (37, 100, 203)):
+        # (four bus groups of different sizes and the root's own voices: 640 of the class - from A2AMD_O2F_MIN = 512 on
+        # the class has its quiet kernel, below that every voice of it is the records / window kernels')
+        groups = [sc.add_bus_group() for _ in range(4)]
+        for g, n in zip(groups, (37, 100, 203, 150)):
             sc.add_voices(n, chain="osc2-filter-pan", group=g, total=1024)
         sc.add_voices(150, chain="osc2-filter-pan", total=1024)
         leaves = [u for g in groups for u in g["leaves"]] + sc.leaves
@@ -1044,14 +1144,348 @@ def test_osc2_filter_leaf_paths_mixed_buses_filter_shapes_and_short_fragments(or
                 be.unit_write(oscb, 2, synth.fix(0.0007), 0, 33 << 8)
             if k % 43 == 3:                          # pan sweep past the clamp
                 be.unit_write(pan, 1, synth.fix(1.4), 0, 20 << 8)
-        a = sc.run(40, batch=32, frames=64)
-        b = sc.run(7, batch=32, frames=23)
-        c = sc.run(3, batch=32, frames=1)
-        d = sc.run(36, batch=32, frames=64)
-        outs.append(np.concatenate([a, b, c, d], axis=1))
+            # ... and the same five kinds over 3 000 - 6 500 frames: still under way in the second batch and after (a glide
+            # that ends inside the first batch - all of the above - is never listed: the launch lists are new in that batch)
+            if k % 53 == 8:
+                be.unit_write(filt, 1, synth.fix(8.0), 0, 3000 << 8)
+            if k % 61 == 12:
+                be.unit_write(osca, 2, synth.fix(0.0012), 0, 6500 << 8)
+            if k % 59 == 6:
+                be.unit_write(oscb, 1, synth.fix(((k % 61) - 30) / 12.0 + 1.1), 0, 5000 << 8)
+            if k % 47 == 10:
+                be.unit_write(oscb, 2, synth.fix(0.0009), 0, 4000 << 8)
+            if k % 43 == 4:
+                be.unit_write(pan, 1, synth.fix(-1.3), 0, 6000 << 8)
+        parts = []
+        for nfr, frames in ((40, 64), (7, 23), (3, 1), (36, 64)):
+            for at in range(0, nfr, 32):
+                parts.append(sc.run(min(32, nfr - at), batch=32, frames=frames))
+                if is_gpu(be):
+                    infos.append(last_batch(be))
+        outs.append(np.concatenate(parts, axis=1))
         be.close()
+    print(f2vpw, repr(no_moving), infos)
+    assert len(infos) == 6
+    for bi in infos:
+        # the quiet kernel ran, over the whole class, in the shape this leg is about
+        assert bi.o2f_launched and bi.o2f_voices == bi.o2f_class == 640 and bi.o2f_vpg == f2vpw, bi
+        assert bi.recs_voices == 0, bi
+    # (the batch a voice is born in is the window kernels': its birth and first settings are records)
+    assert infos[0].win_voices == 640 and infos[0].n_moving_listed == 0, infos[0]
+    # (63 voices have a long glide, 37 of them one that lasts into the last batch)
+    for i, bi in enumerate(infos[1:], 1):
+        assert bi.general_voices == 0, bi
+        if no_moving:       # every gliding voice stays the quiet kernel's: its general loop
+            assert bi.n_moving_listed == 0 and bi.win_voices == 0, (i, bi)
+        else:               # ... is the window kernels' for as long as it glides
+            assert bi.win_voices == bi.n_moving_listed > 0, (i, bi)
     assert outs[1].any()
     assert first_diff(outs[0], outs[1]) is None
+
+
+def _o2f_scene(be, n, groups=(0.2, 0.35), amp_total=64):
+    """n voices of wtosc; wtosc; filter12; panmix: a share of them under each of len(groups) bus groups, the rest under
+    the root; band and high pass mixed in for every seventh voice.  (amp_total: add_voices' `total` - the amplitude is
+    4.0 / total per oscillator, and filter12 takes its input >> 5: loud enough to leave more than a bit or two of it)"""
+    sc = synth.Scene(be)
+    sc.root()
+    left = n
+    for share in groups:
+        g = sc.add_bus_group()
+        k = int(n * share)
+        sc.add_voices(k, chain="osc2-filter-pan", group=g, total=amp_total)
+        left -= k
+    sc.add_voices(left, chain="osc2-filter-pan", total=amp_total)
+    for k, units in enumerate(_o2f_leaves(sc)):
+        if k % 7 == 3:
+            be.unit_write(units[2], 3, synth.fix(0.4))
+            be.unit_write(units[2], 4, synth.fix(-0.3))
+    return sc
+
+
+def _o2f_leaves(sc):
+    return [u for g in sc.groups for u in g["leaves"]] + sc.leaves
+
+
+def _o2f_glides(be, leaves, step, dur):
+    """the five kinds of glide k_leaf_osc2filtpan's general loop / the window kernels' closed forms know, on every
+    `step`-th voice in turn, over `dur` frames"""
+    for k, units in enumerate(leaves):
+        osca, oscb, filt, pan = units
+        if k % step:
+            continue
+        kind = (k // step) % 5
+        if kind == 0:
+            be.unit_write(filt, 1, synth.fix(2.0 + (k % 7)), 0, dur << 8)
+        elif kind == 1:
+            be.unit_write(osca, 2, synth.fix(0.02 + 0.001 * (k % 9)), 0, dur << 8)
+        elif kind == 2:
+            be.unit_write(oscb, 1, synth.fix(((k % 61) - 30) / 12.0 + 0.9), 0, dur << 8)
+        elif kind == 3:
+            be.unit_write(oscb, 2, synth.fix(0.015), 0, dur << 8)
+        else:
+            be.unit_write(pan, 1, synth.fix(1.4 if k % 2 else -1.2), 0, dur << 8)
+
+
+def _o2f_walk(sc, rng, frames=64, busy=0, born=()):
+    """One fragment of the engine's walk over a scene of _o2f_scene: `busy` voices picked at random get control writes
+    between two windows inside the fragment (pitch, amplitude, phase, another wave; cutoff set or swept, q, the filter's
+    mix; volume and pan - set, or ramped over up to 7 800 frames), the voices in `born` their first window from a frame
+    inside the fragment on, every other voice the default window."""
+    be = sc.be
+    leaves = _o2f_leaves(sc)
+    pick = set(int(k) for k in rng.choice(len(leaves), min(busy, len(leaves)), replace=False)) if busy else set()
+    todo = {id(u): k for k, u in enumerate(leaves)}
+
+    def leaf(units):
+        k = todo[id(units)]
+        for b, off in born:
+            if b is units:
+                for u in units:
+                    be.unit_process(u, off, frames - off)
+                return
+        if k not in pick or frames < 2:
+            for u in units:
+                be.unit_process(u, 0, frames)
+            return
+        osca, oscb, filt, pan = units
+        cut = int(rng.integers(1, frames))
+        for u in units:
+            be.unit_process(u, 0, cut)
+        dur = int(rng.choice([0, 100, 3000, 70000, 2000000]))
+        start = int(rng.integers(0, 256))
+        what = int(rng.integers(0, 8))
+        osc = (osca, oscb)[int(rng.integers(0, 2))]
+        if what == 0:
+            be.unit_write(osc, 0, sc.wave_ids[int(rng.choice([0, 3, 7, 11, 23]))], start, 0)
+        elif what == 1:
+            be.unit_write(osc, 1, synth.fix(float(rng.uniform(-3, 3))), start, dur)
+        elif what == 2:
+            be.unit_write(osc, 2, synth.fix(float(rng.uniform(0, 0.1))), start, dur)
+        elif what == 3:
+            be.unit_write(osc, 3, int(rng.integers(0, 65536)), start, 0)
+        elif what == 4:
+            be.unit_write(filt, 0, synth.fix(float(rng.uniform(-1, 5))), start, dur)
+        elif what == 5:
+            be.unit_write(filt, 1, synth.fix(float(rng.uniform(0.2, 9))), start, dur)
+        elif what == 6:
+            be.unit_write(filt, int(rng.integers(2, 5)), synth.fix(float(rng.uniform(0, 1))), start, dur)
+        else:
+            be.unit_write(pan, int(rng.integers(0, 2)), synth.fix(float(rng.uniform(-1.5, 1.5))), start, dur)
+        for u in units:
+            be.unit_process(u, cut, frames - cut)
+
+    be.fragment(frames)
+    be.unit_process(sc.rootv[0], 0, frames)
+    for g in sc.groups:
+        be.unit_process(g["units"][0], 0, frames)
+        for units in g["leaves"]:
+            leaf(units)
+        be.inline_end(g["units"][0])
+        for u in g["units"][1:]:
+            be.unit_process(u, 0, frames)
+    for units in sc.leaves:
+        leaf(units)
+    be.inline_end(sc.rootv[0])
+    be.unit_process(sc.rootv[1], 0, frames)
+    be.unit_process(sc.rootv[2], 0, frames)
+
+
+@pytest.mark.parametrize("win", ["1", "0"])
+@pytest.mark.parametrize("n", [511, 512, 513])
+def test_osc2_filter_class_at_the_small_scene_threshold(oracle_lib, monkeypatch, n, win):
+    """A2AMD_O2F_MIN (512 by default): below it every voice of 2 x wtosc-filter12-panmix is the records / window kernels',
+    from it on a voice without records is k_leaf_osc2filtpan's.  511, 512 and 513 voices over two bus groups and the root,
+    some gliding, some scripted, three batches of 8 fragments, with the window kernels and with the records kernels."""
+    monkeypatch.setenv("A2AMD_WIN", win)
+    monkeypatch.delenv("A2AMD_O2F_MIN", raising=False)
+    outs, infos = [], []
+    for be in (make_gpu(max_batch=8), make_oracle(oracle_lib)):
+        rng = np.random.default_rng(n)
+        sc = _o2f_scene(be, n)
+        _o2f_glides(be, _o2f_leaves(sc), 9, 900)
+        parts = []
+        for b in range(3):
+            for f in range(8):
+                _o2f_walk(sc, rng, busy=0 if b == 0 else 20)
+            parts.append(be.render(8 * 64))
+            if is_gpu(be):
+                infos.append(last_batch(be))
+        outs.append(np.concatenate(parts, axis=1))
+        be.close()
+    print(n, win, infos)
+    for b, bi in enumerate(infos):
+        assert bi.o2f_class == n and bool(bi.o2f_launched) == (n >= 512), bi
+        assert (bi.win_voices if win == "1" else bi.recs_voices) == bi.o2f_listed and bi.general_voices == 0, bi
+        assert (bi.recs_voices if win == "1" else bi.win_voices) == 0, bi
+        if n < 512 or b == 0:
+            assert bi.o2f_listed == n, bi       # (b == 0: every voice carries the records of its birth)
+        else:
+            assert 20 <= bi.o2f_listed < 300 and bi.o2f_voices == n and bi.o2f_vpg == auto_o2f_vpg(n, bi.o2f_max_vpg), bi
+    assert outs[1].any()
+    assert first_diff(outs[0], outs[1]) is None
+
+
+@pytest.mark.parametrize("win", ["1", "0"])
+def test_osc2_filter_voices_cross_the_small_scene_threshold_both_ways(oracle_lib, monkeypatch, win):
+    """The hand-over of a voice between the records / window kernels and k_leaf_osc2filtpan when its class crosses
+    A2AMD_O2F_MIN between batches: 510 voices; births inside a batch take the class to 514; deaths take it to 509.  Voices
+    glide (q, both oscillators' amplitude, pitch, pan: for 1 400 frames, begun again in every second batch) and carry
+    records in every batch, so filter state, oscillator phases and rampers in mid-flight change hands in both directions;
+    which kernel had the class is asserted batch by batch."""
+    monkeypatch.setenv("A2AMD_WIN", win)
+    monkeypatch.delenv("A2AMD_O2F_MIN", raising=False)
+    #        class size the batch is rendered with (a voice that dies is its class's until the batch it dies in is over)
+    plan = [510, 510, 514, 514, 514, 509, 509]
+    outs, infos = [], []
+    for be in (make_gpu(max_batch=8), make_oracle(oracle_lib)):
+        rng = np.random.default_rng(77)
+        sc = _o2f_scene(be, 510)
+        parts = []
+        for b in range(len(plan)):
+            if b % 2 == 1:
+                _o2f_glides(be, _o2f_leaves(sc), 11 + b, 1400)
+            for f in range(8):
+                born = []
+                if b == 2 and f in (1, 2, 5, 6):        # a note begins inside a fragment: 510 -> 514 in this batch
+                    g = sc.groups[f % 2] if f < 5 else None
+                    sc.add_voices(1, chain="osc2-filter-pan", group=g, total=64)
+                    born = [((g["leaves"] if g else sc.leaves)[-1], 5 + 9 * f)]
+                _o2f_walk(sc, rng, busy=24, born=born)
+                if b == 4 and f in (0, 2, 3, 6, 7):     # ... and notes end: 509 from the next batch on
+                    l = (sc.groups[0]["leaves"], sc.groups[1]["leaves"], sc.leaves)[f % 3]
+                    k = int(rng.integers(0, len(l)))
+                    for u in l[k]:
+                        be.unit_deinit(u)
+                    del l[k]
+            parts.append(be.render(8 * 64))
+            if is_gpu(be):
+                infos.append(last_batch(be))
+        outs.append(np.concatenate(parts, axis=1))
+        be.close()
+    print(win, infos)
+    for b, bi in enumerate(infos):
+        assert bi.o2f_class == plan[b] and bool(bi.o2f_launched) == (plan[b] >= 512), (b, bi)
+        assert (bi.win_voices if win == "1" else bi.recs_voices) == bi.o2f_listed and bi.general_voices == 0, (b, bi)
+        if plan[b] < 512:
+            assert bi.o2f_listed == plan[b], (b, bi)
+        else:
+            assert 24 <= bi.o2f_listed < 300 and bi.o2f_voices == plan[b], (b, bi)
+    assert outs[1].any()
+    assert first_diff(outs[0], outs[1]) is None
+
+
+@pytest.mark.parametrize("n", [512, 513, 768, 769, 770, 771, "256*max", "256*max+1"])
+def test_osc2_filter_leaf_automatic_shapes_match_oracle(oracle_lib, monkeypatch, n):
+    """The shape the launcher picks by itself (no A2AMD_F2VPW) at the class sizes where it steps: 2 -> 3 voices per
+    workgroup at 513, 3 -> 4 at 769; a last workgroup - and a last oscillator wavefront - of 1, 2 and 3 voices (769, 770,
+    771 at 4 per workgroup); one round of 256 workgroups full to the last voice at 256 x a2d_osc2filtpan_max_vpg(), two
+    rounds from one voice more.  Few fragments, so the oracle stays cheap: 3 (the voices' births: the window kernels',
+    the quiet kernel launched over a class it skips entirely), then 5 and 2 quiet ones."""
+    monkeypatch.delenv("A2AMD_F2VPW", raising=False)
+    monkeypatch.delenv("A2AMD_O2F_MIN", raising=False)
+    maxv = 36       # (checked against what the library reports below)
+    nv = 256 * maxv if n == "256*max" else 256 * maxv + 1 if n == "256*max+1" else n
+    outs, infos = [], []
+    for be in (make_gpu(max_batch=8), make_oracle(oracle_lib)):
+        sc = _o2f_scene(be, nv, amp_total=max(64, nv // 16))
+        parts = []
+        for nfr in (3, 5, 2):
+            parts.append(sc.run(nfr, batch=8))
+            if is_gpu(be):
+                infos.append(last_batch(be))
+        outs.append(np.concatenate(parts, axis=1))
+        be.close()
+    print(n, infos)
+    for bi in infos:
+        assert bi.o2f_max_vpg == maxv, "the test's sizes were chosen for a2d_osc2filtpan_max_vpg() == 36"
+        assert bi.o2f_launched and bi.o2f_voices == bi.o2f_class == nv and bi.o2f_vpg == auto_o2f_vpg(nv, maxv), bi
+    assert [bi.win_voices for bi in infos] == [nv, 0, 0], infos
+    assert infos[0].o2f_vpg == {512: 2, 513: 3, 768: 3, 769: 4, 770: 4, 771: 4, "256*max": 36, "256*max+1": 19}[n]
+    assert outs[1].any()
+    assert first_diff(outs[0], outs[1]) is None
+
+
+def _repeat_batch(be, sc, frames, count):
+    """one fragment walked by calls and count - 1 repeats of it (fragment_repeat), rendered as ONE batch on the GPU and
+    in pieces of at most 64 fragments by the oracle"""
+    fr = be.lib.a2amd_fragment_repeat if is_gpu(be) else be.lib.a2o_fragment_repeat
+    fr.argtypes = [ctypes.c_void_p, ctypes.c_uint, ctypes.c_uint]
+    sc.walk(frames)
+    parts, done, pending = [], 0, 1
+    step = count if is_gpu(be) else 64
+    while done < count:
+        n = min(step - pending, count - done - pending)
+        if n:
+            assert fr(be.ctx, frames, n) == 0
+        parts.append(be.render((pending + n) * frames).copy())
+        done += pending + n
+        pending = 0
+    return np.concatenate(parts, axis=1)
+
+
+@pytest.mark.parametrize("no_moving", ["", "1"])
+@pytest.mark.parametrize("f2vpw", [0, 48, 64])
+def test_osc2_filter_leaf_batch_lengths_and_fragment_lengths_match_oracle(oracle_lib, monkeypatch, f2vpw, no_moving):
+    """k_leaf_osc2filtpan over batches that are not a whole number of its fragment chunks - 1 fragment, 7, 255 - and over
+    fragments of 64 frames, 23, 17 and single frames, in the shape the launcher picks (600 voices: 3 per workgroup), in
+    the 4-voice all-settled loop (48) and in the general loop for settled voices (64); voices gliding for 9 000 frames are
+    the window kernels' for that long, or (no_moving) the quiet kernel's own."""
+    if f2vpw:
+        monkeypatch.setenv("A2AMD_F2VPW", str(f2vpw))
+    else:
+        monkeypatch.delenv("A2AMD_F2VPW", raising=False)
+    if no_moving:
+        monkeypatch.setenv("A2AMD_NO_MOVING", no_moving)
+    else:
+        monkeypatch.delenv("A2AMD_NO_MOVING", raising=False)
+    batches = [(1, 64), (7, 64), (255, 23), (5, 1), (255, 64), (1, 1), (9, 17), (1, 64)]
+    outs, infos = [], []
+    for be in (make_gpu(max_batch=255), make_oracle(oracle_lib)):
+        sc = _o2f_scene(be, 600, groups=(0.1, 0.3, 0.25))
+        _o2f_glides(be, _o2f_leaves(sc), 13, 9000)
+        parts = []
+        for count, frames in batches:
+            parts.append(_repeat_batch(be, sc, frames, count))
+            if is_gpu(be):
+                infos.append(last_batch(be))
+        outs.append(np.concatenate(parts, axis=1))
+        be.close()
+    print(f2vpw, repr(no_moving), infos)
+    for b, bi in enumerate(infos):
+        assert bi.o2f_launched and bi.o2f_voices == 600 and bi.o2f_vpg == (f2vpw or 3), (b, bi)
+        assert bi.recs_voices == 0 and bi.general_voices == 0, (b, bi)
+        if b == 0:
+            assert bi.win_voices == 600, bi
+        elif no_moving:
+            assert bi.win_voices == 0 and bi.n_moving_listed == 0, (b, bi)
+        elif b in (1, 2, 3):        # (frames 64 ... 6 382 of the glides' 9 000)
+            assert bi.win_voices == bi.n_moving_listed > 0, (b, bi)       # (47 voices glide)
+    assert outs[1].any()
+    assert first_diff(outs[0], outs[1]) is None
+
+
+@pytest.mark.parametrize("groups", [0, 3])
+def test_osc2_filter_small_scene_records_without_the_records_kernel_match_oracle(oracle_lib, monkeypatch, groups):
+    """A2AMD_NO_FAST=64 (records to the general kernel) in a small scene: a 2 x wtosc-filter12-panmix voice that carries
+    records is the general kernel's, one without is the records kernel's (below A2AMD_O2F_MIN the class has no quiet
+    kernel) - each voice on ONE of the two lists.  (Until this test the voice with records stood on both and was rendered
+    twice: upload() marked it as listed only where the records kernels took it.)"""
+    monkeypatch.setenv("A2AMD_WIN", "0")
+    monkeypatch.setenv("A2AMD_NO_FAST", "64")
+    gpu = make_gpu(max_batch=16)
+    infos = []
+    got = _wt_script(gpu, "osc2-filter-pan", groups=groups, on_batch=lambda: infos.append(last_batch(gpu)))
+    gpu.close()
+    print(groups, infos)
+    for bi in infos:
+        assert not bi.o2f_launched and bi.win_voices == 0 and bi.general_voices > 0, bi
+        assert bi.o2f_listed + bi.general_voices <= bi.o2f_class, f"a voice on two lists: {bi}"
+    ora = make_oracle(oracle_lib)
+    want = _wt_script(ora, "osc2-filter-pan", groups=groups)
+    ora.close()
+    assert want.any()
+    assert first_diff(got, want) is None
 
 
 def test_subtractive_note_at_full_size_matches_oracle_golden():
