@@ -313,6 +313,13 @@ int a2d_launch_build_coef(const int16_t *pool, int *coef, unsigned lo, unsigned 
 int a2d_launch_capture(const int32_t *bus, int32_t *dst, const uint32_t *fragpos, int nfrags, int nch, void *stream);
 int a2d_launch_wave_from_pcm(const int32_t *pcm, int16_t *pool, const uint32_t *off, const uint32_t *size, int levels, int looped,
 		int pre, int post, void *stream);
+int a2d_launch_wave_level0(const int32_t *pcm, int16_t *d, unsigned size, void *stream);
+int a2d_launch_wave_finish(int16_t *pool, const uint32_t *off, const uint32_t *size, int levels, int looped, int pre, int post,
+		void *stream);
+// a2amd_wavepost.hip: level 0 with A2_NORMALIZE / A2_XFADE; scratch: a2d_wavepost_scratch_words() device words
+unsigned a2d_wavepost_scratch_words(unsigned size, unsigned flags, unsigned chunk);
+int a2d_launch_wave_level0_post(const int32_t *pcm, int16_t *d, unsigned size, unsigned flags, unsigned chunk, uint32_t *scratch,
+		void *stream);
 int a2d_osc2filtpan_max_vpg(void);
 int a2d_launch_leaf_osc2filtpan(const A2DParams *dparams, const A2DParams &hp, const int *dlist, int nlist,
 		int vpg, void *stream);

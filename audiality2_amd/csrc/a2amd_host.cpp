@@ -132,7 +132,7 @@ void a2amd_close(a2amd_ctx *c)
 			hipEventDestroy(c->win_ev[k]);
 	hipFree(c->d_waves.d); hipFree(c->d_wavepool.d); hipFree(c->d_wavecoef.d); hipFree(c->d_busmem.d);
 	vm_close(c);
-	hipFree(c->capture.d); hipFree(c->capture.d_fragpos);
+	hipFree(c->capture.d); hipFree(c->capture.d_fragpos); hipFree(c->d_wavepost.d);
 	hipFree(c->d_fbdmem.d); hipFree(c->d_fmstate.d); hipFree(c->d_xio.d); hipFree(c->d_fmsine); hipFree(c->d_list.d); hipFree(c->d_scatter.d); hipFree(c->d_ptab); hipFree(c->d_blob.d);
 	for(int k = 0; k < 2; ++k) { if(c->h_blob[k]) hipHostFree(c->h_blob[k]); if(c->blob_ev[k]) hipEventDestroy(c->blob_ev[k]); }
 	if(c->h_master)
@@ -289,7 +289,7 @@ int a2amd_wave_stats(a2amd_ctx *c, uint64_t *h2d, uint32_t *uploaded, uint32_t *
 	return A2AMD_OK;
 }
 
-static int wave_place(a2amd_ctx *c, uint64_t key, const a2amd_wavedesc *w, const a2amd_capture *cap);
+static int wave_place(a2amd_ctx *c, uint64_t key, const a2amd_wavedesc *w, const a2amd_capture *cap, unsigned chunk = 0);
 
 int a2amd_wave_upload(a2amd_ctx *c, uint64_t key, const a2amd_wavedesc *w)
 {
@@ -298,7 +298,8 @@ int a2amd_wave_upload(a2amd_ctx *c, uint64_t key, const a2amd_wavedesc *w)
 	return wave_place(c, key, w, nullptr);
 }
 
-int a2amd_wave_upload_captured(a2amd_ctx *c, uint64_t key, const a2amd_wavedesc *w, const a2amd_capture *cap)
+// what both entry points for captures refuse
+static int captured_refusals(a2amd_ctx *c, const a2amd_wavedesc *w, const a2amd_capture *cap)
 {
 	if(!w || !cap)
 		return c->fail(A2AMD_EINVAL, "wave_upload_captured: null");
@@ -306,19 +307,43 @@ int a2amd_wave_upload_captured(a2amd_ctx *c, uint64_t key, const a2amd_wavedesc 
 		return c->fail(A2AMD_EUNSUPPORTED, "wave_upload_captured: the capture lives on GPU %d, the context on %d", cap->device, c->cfg.device);
 	if(w->type != A2AMD_WWAVE && w->type != A2AMD_WMIPWAVE)
 		return c->fail(A2AMD_EUNSUPPORTED, "wave_upload_captured: wave type %d", w->type);
-	// A2_NORMALIZE 0x10000, A2_XFADE 0x40000, A2_REVMIX 0x80000 (include/a2_waves.h:113-115): a2_postprocess and the
-	// normalising conversion of src/waves.c are host work on the whole wave
-	if(w->flags & 0x000d0000u)
-		return c->fail(A2AMD_EUNSUPPORTED, "wave_upload_captured: flags %#x ask for post-processing", w->flags);
 	if((size_t)w->size[0] != cap->n)
 		return c->fail(A2AMD_EUNSUPPORTED, "wave_upload_captured: the wave has %u samples, the capture %zu", w->size[0], cap->n);
 	for(int l = 1; l < (w->type == A2AMD_WMIPWAVE ? A2D_MIPS : 1); ++l)
 		if(w->size[l] != ((w->size[0] + (1u << l) - 1) >> l))	// a2_wave_alloc, waves.c:76
 			return c->fail(A2AMD_EINVAL, "wave_upload_captured: level %d has %u samples", l, w->size[l]);
+	return A2AMD_OK;
+}
+
+int a2amd_wave_upload_captured(a2amd_ctx *c, uint64_t key, const a2amd_wavedesc *w, const a2amd_capture *cap)
+{
+	// A2_NORMALIZE 0x10000, A2_XFADE 0x40000, A2_REVMIX 0x80000 (include/a2_waves.h:113-115): this entry point does
+	// the plain conversion only (the first two: a2amd_wave_upload_captured_post)
+	if(w && cap && (w->flags & 0x000d0000u))
+		return c->fail(A2AMD_EUNSUPPORTED, "wave_upload_captured: flags %#x ask for post-processing", w->flags);
+	if(int r = captured_refusals(c, w, cap))
+		return r;
 	return wave_place(c, key, w, cap);
 }
 
-static int wave_place(a2amd_ctx *c, uint64_t key, const a2amd_wavedesc *w, const a2amd_capture *cap)
+int a2amd_wave_upload_captured_post(a2amd_ctx *c, uint64_t key, const a2amd_wavedesc *w, const a2amd_capture *cap, unsigned chunk)
+{
+	if(int r = captured_refusals(c, w, cap))
+		return r;
+	if(w->flags & 0x00080000u)
+		return c->fail(A2AMD_EUNSUPPORTED, "wave_upload_captured_post: A2_REVMIX (the reference's result is not defined)");
+	if((w->flags & 0x00040000u) && w->size[0] < 2)
+		return c->fail(A2AMD_EUNSUPPORTED, "wave_upload_captured_post: A2_XFADE on %u samples", w->size[0]);
+	if((w->flags & 0x00010000u) && !chunk)
+		return c->fail(A2AMD_EUNSUPPORTED, "wave_upload_captured_post: A2_NORMALIZE needs the size of the writes");
+	// the peaks and the gain live in device memory (in stream order behind whatever used them last)
+	use_device(c);
+	if(int r = grow(c, c->d_wavepost, a2d_wavepost_scratch_words(w->size[0], w->flags, chunk), 1, false))
+		return r;
+	return wave_place(c, key, w, cap, chunk);
+}
+
+static int wave_place(a2amd_ctx *c, uint64_t key, const a2amd_wavedesc *w, const a2amd_capture *cap, unsigned chunk)
 {
 	use_device(c);
 	int id = -1;
@@ -402,8 +427,13 @@ static int wave_place(a2amd_ctx *c, uint64_t key, const a2amd_wavedesc *w, const
 	}
 	if(cap) {
 		// level 0 from the samples the device rendered, pads and mip levels derived here
-		if(levels && a2d_launch_wave_from_pcm(cap->d, c->d_wavepool.d + pos0, loff, lsize, levels, (w->flags & 0x100u) != 0,
-				A2AMD_WAVEPRE, A2AMD_WAVEPOST, c->stream))
+		// (A2_NORMALIZE / A2_XFADE: peaks -> gain -> level 0 -> crossfade, a2amd_wavepost.hip, then pads and mip levels)
+		int16_t *pool0 = c->d_wavepool.d + pos0;
+		const int looped = (w->flags & 0x100u) != 0;
+		if(levels && ((w->flags & 0x00050000u)
+				? a2d_launch_wave_level0_post(cap->d, pool0 + A2AMD_WAVEPRE, lsize[0], w->flags, chunk, c->d_wavepost.d, c->stream) ||
+					a2d_launch_wave_finish(pool0, loff, lsize, levels, looped, A2AMD_WAVEPRE, A2AMD_WAVEPOST, c->stream)
+				: a2d_launch_wave_from_pcm(cap->d, pool0, loff, lsize, levels, looped, A2AMD_WAVEPRE, A2AMD_WAVEPOST, c->stream)))
 			return c->fail(A2AMD_EHIP, "wave build from capture failed");
 		++c->waves_resident;
 	} else

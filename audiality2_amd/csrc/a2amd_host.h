@@ -543,6 +543,7 @@ struct a2amd_ctx {
 	bool gdirect[12] = {};		// (the captured root launch stored there)
 	// channel 0 of what this context renders, kept on the device (a2amd_capture_begin)
 	struct Capture { int32_t *d = nullptr; size_t cap = 0, n = 0; bool on = false; uint32_t *d_fragpos = nullptr; } capture;
+	DevBuf<uint32_t> d_wavepost;	// a2amd_wave_upload_captured_post: the gain word and the chunks' peaks (a2amd_wavepost.hip)
 	uint64_t wave_h2d_bytes = 0;
 	uint32_t waves_uploaded = 0, waves_resident = 0;
 	int32_t *master_dst = nullptr;	// where the root of the batch being issued is to store the master bus (nullptr: bus memory)

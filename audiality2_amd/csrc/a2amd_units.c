@@ -140,7 +140,7 @@ typedef struct HOSTSTATE
 	/* ... and in the state that asked for the wave: captures waiting for the engine thread to build the wave's
 	 * device copy from them, at the wave's first use (a2_RenderWave may be called from the API thread of a
 	 * realtime state: the backend context belongs to the engine thread) */
-	struct PENDCAP { A2P_wave *w; int handle; a2amd_capture *cap; } *pendcaps;	/* (handle: the wave's, by which w is looked up again before it is trusted) */
+	struct PENDCAP { A2P_wave *w; int handle; a2amd_capture *cap; unsigned chunk; } *pendcaps;	/* (handle: the wave's, by which w is looked up again before it is trusted) */
 	int		npendcaps, cap_pendcaps;
 	pthread_mutex_t	pendcaps_mtx;
 	int		pendcaps_mtx_ok;
@@ -189,6 +189,7 @@ typedef struct RENDERCAP
 	struct HOSTSTATE	*sub;
 	a2amd_capture		*cap;
 	int			armed;
+	unsigned		chunk;	/* the substate's cfg->buffer: frames per a2_Write() of a2_Render (src/render.c:76-95) */
 } RENDERCAP;
 static __thread RENDERCAP *rendering;
 
@@ -370,6 +371,7 @@ static int amd_open(A2P_config *cfg, void **statedata)
 			{
 				rendering->armed = 0;
 				rendering->sub = freeone;
+				rendering->chunk = cfg->buffer > 0 ? (unsigned)cfg->buffer : 0;
 				freeone->capturing = 1;
 			}
 			*statedata = freeone;
@@ -1836,11 +1838,13 @@ static int wave_id_of(HOSTSTATE *hs, int dev, A2P_wave *w)
 		/* the device rendered this wave (a2_RenderWave below): its copy is built from what the device kept - on
 		 * the context of this state that gets to play it first; others take the engine's copy */
 		a2amd_capture *cap = NULL;
+		unsigned chunk = 0;
 		pthread_mutex_lock(&hs->pendcaps_mtx);
 		for(i = 0; i < hs->npendcaps; ++i)
 			if(hs->pendcaps[i].w == w && a2_GetWave(hs->cfg->interface, hs->pendcaps[i].handle) == w)
 			{
 				cap = hs->pendcaps[i].cap;
+				chunk = hs->pendcaps[i].chunk;
 				hs->pendcaps[i] = hs->pendcaps[--hs->npendcaps];
 				break;
 			}
@@ -1848,7 +1852,8 @@ static int wave_id_of(HOSTSTATE *hs, int dev, A2P_wave *w)
 		if(cap)
 		{
 			if(a2amd_capture_frames(cap) == w->size[0])
-				id = a2amd_wave_upload_captured(hs->ctxs[dev], (uint64_t)(uintptr_t)w, &d, cap);
+				/* ("normalize" and "xfade" are done there too; "revmix" is refused: the engine's copy) */
+				id = a2amd_wave_upload_captured_post(hs->ctxs[dev], (uint64_t)(uintptr_t)w, &d, cap, chunk);
 			if(getenv("A2AMD_WAVE_STATS"))
 				fprintf(stderr, "a2amd units: wave %p, %u frames rendered on the device: %s\n", (void *)w, a2amd_capture_frames(cap),
 						id >= 0 ? "device copy built from the capture" : "uploaded from the engine's copy");
@@ -2859,9 +2864,10 @@ int a2amd_units_vm_recall(const void *const *heads, unsigned n, void *const *vms
  * of it (the same interposition as the unit descriptors: the compiler's call, src/compiler.c:3359, and the
  * application's both bind here) only to note which state is the substate: that state's drop-in context keeps
  * what it renders in device memory (a2amd_capture_begin), and when the engine has made its wave, the device
- * builds ITS copy - samples, pads, mip levels, coefficient entries - from there (a2amd_wave_upload_captured; on the
+ * builds ITS copy - samples, pads, mip levels, coefficient entries - from there (a2amd_wave_upload_captured_post; on the
  * engine thread, when the wave is first played: wave_id_of) and the wave registry takes it as uploaded.  The rendered samples travel device -> host once, for the
- * engine's copy, and never back.  Waves with A2_NORMALIZE / A2_XFADE / A2_REVMIX, a substate on another GPU,
+ * engine's copy, and never back.  A2_NORMALIZE and A2_XFADE are applied on the device as well (the gain is per
+ * a2_Write() of a2_Render, so the substate's buffer size is noted with the capture).  Waves with A2_REVMIX, a substate on another GPU,
  * a state spread over several GPUs (A2AMD_DEVICES > 1): uploaded from the engine's copy on first use as
  * before (wave_id_of).  A2AMD_NO_RESIDENT=1 switches this off (A/B). */
 int a2_RenderWave(void *iface, int wt, unsigned period, int flags, unsigned samplerate, unsigned length, void *props,
@@ -2912,6 +2918,7 @@ int a2_RenderWave(void *iface, int wt, unsigned period, int flags, unsigned samp
 			{
 				hs->pendcaps[hs->npendcaps].w = w;
 				hs->pendcaps[hs->npendcaps].handle = wh;
+				hs->pendcaps[hs->npendcaps].chunk = rc.chunk;
 				hs->pendcaps[hs->npendcaps++].cap = rc.cap;
 				kept = 1;
 			}

@@ -70,13 +70,27 @@ int a2d_launch_capture(const int32_t *bus, int32_t *dst, const uint32_t *fragpos
 	return (int)hipGetLastError();
 }
 
+// d: first payload sample of level 0
+int a2d_launch_wave_level0(const int32_t *pcm, int16_t *d, unsigned size, void *stream)
+{
+	if(size)
+		hipLaunchKernelGGL(k_wave_level0, dim3((size + 255) / 256), dim3(256), 0, (hipStream_t)stream, pcm, d, size);
+	return (int)hipGetLastError();
+}
+
 // pool: first pad sample of level 0; off[l]: offset of level l's first pad sample from there
 int a2d_launch_wave_from_pcm(const int32_t *pcm, int16_t *pool, const uint32_t *off, const uint32_t *size, int levels, int looped,
 		int pre, int post, void *stream)
 {
+	a2d_launch_wave_level0(pcm, pool + off[0] + pre, size[0], stream);
+	return a2d_launch_wave_finish(pool, off, size, levels, looped, pre, post, stream);
+}
+
+// ... level 0's payload being there: its pads, then the mip levels with theirs
+int a2d_launch_wave_finish(int16_t *pool, const uint32_t *off, const uint32_t *size, int levels, int looped, int pre, int post,
+		void *stream)
+{
 	hipStream_t st = (hipStream_t)stream;
-	if(size[0])
-		hipLaunchKernelGGL(k_wave_level0, dim3((size[0] + 255) / 256), dim3(256), 0, st, pcm, pool + off[0] + pre, size[0]);
 	hipLaunchKernelGGL(k_wave_pad, dim3(1), dim3(256), 0, st, pool + off[0], size[0], looped, pre, post);
 	for(int l = 1; l < levels; ++l) {
 		if(size[l])

@@ -121,6 +121,16 @@ class Backend:
         self._fragment_repeat_noise = None
         if hasattr(lib, prefix + "fragment_repeat_noise"):
             self._fragment_repeat_noise = fn("fragment_repeat_noise", i32, vp, u32, u32, C.POINTER(C.c_uint32))
+        # waves built on the device from what it rendered (the product library only)
+        self.has_capture = hasattr(lib, prefix + "wave_upload_captured_post")
+        if self.has_capture:
+            self._capture_begin = fn("capture_begin", i32, vp)
+            self._capture_end = fn("capture_end", i32, vp, C.POINTER(vp))
+            self._capture_frames = fn("capture_frames", u32, vp)
+            self._capture_free = fn("capture_free", None, vp)
+            self._wave_upload_captured = fn("wave_upload_captured", i32, vp, u64, C.POINTER(a2amd_wavedesc), vp)
+            self._wave_upload_captured_post = fn("wave_upload_captured_post", i32, vp, u64, C.POINTER(a2amd_wavedesc), vp, u32)
+            self._wave_stats = fn("wave_stats", i32, vp, C.POINTER(u64), C.POINTER(u32), C.POINTER(u32))
         cfg = a2amd_config(C.sizeof(a2amd_config), samplerate, basepitch, channels,
                            device, max_batch, stream)
         self.ctx = vp()
@@ -151,6 +161,43 @@ class Backend:
             d.size[lv] = sizes[lv]
             d.data[lv] = arr.ctypes.data_as(C.POINTER(C.c_int16))
         return self._chk(self._wave_upload(self.ctx, key, C.byref(d)), "wave_upload")
+
+    def capture_begin(self):
+        """From here on channel 0 of everything this context renders is also kept in device memory."""
+        return self._chk(self._capture_begin(self.ctx), "capture_begin")
+
+    def capture_end(self):
+        """Detaches what was kept: an opaque capture (it outlives the context; release it with capture_free()),
+        or None when nothing was rendered."""
+        cap = C.c_void_p()
+        self._chk(self._capture_end(self.ctx, C.byref(cap)), "capture_end")
+        return cap if cap.value else None
+
+    def capture_frames(self, cap):
+        return self._capture_frames(cap)
+
+    def capture_free(self, cap):
+        self._capture_free(cap)
+
+    def wave_upload_captured(self, key, wtype, flags, period, sizes, cap, chunk=None, check=True):
+        """A wave built on the device from a capture (a2amd_wave_upload_captured).  With `chunk` - the frames per
+        write of the render, A2_config.buffer of the rendering substate - the entry point that also applies
+        A2_NORMALIZE / A2_XFADE there (a2amd_wave_upload_captured_post).  check=False: the return code as it is."""
+        d = a2amd_wavedesc()
+        d.type, d.flags, d.period = wtype, flags, period
+        for lv, n in enumerate(sizes):
+            d.size[lv] = n
+        if chunk is None:
+            rc = self._wave_upload_captured(self.ctx, key, C.byref(d), cap)
+        else:
+            rc = self._wave_upload_captured_post(self.ctx, key, C.byref(d), cap, chunk)
+        return self._chk(rc, "wave_upload_captured") if check else rc
+
+    def wave_stats(self):
+        """(bytes of wave data copied from the host, waves copied from the host, waves built from captures)"""
+        h2d, up, res = C.c_uint64(), C.c_uint32(), C.c_uint32()
+        self._chk(self._wave_stats(self.ctx, C.byref(h2d), C.byref(up), C.byref(res)), "wave_stats")
+        return h2d.value, up.value, res.value
 
     def wave_drop(self, key):
         return self._chk(self._wave_drop(self.ctx, key), "wave_drop")

@@ -18,6 +18,7 @@ FM_KINDS = {"fm1": (6, 1), "fm2": (7, 2), "fm3": (8, 3), "fm4": (9, 4),
 PROCADD = 1
 WOFF, WNOISE, WWAVE, WMIPWAVE = range(4)
 LOOPED = 0x100
+NORMALIZE, XFADE, REVMIX = 0x10000, 0x40000, 0x80000    # A2_waveflags, include/a2_waves.h:113-115
 WAVEPERIOD = 2048
 
 
@@ -60,6 +61,53 @@ def wave_pyramid(samples, looped=True, levels=MIPLEVELS):
         data.append(buf)
         prev = buf
     return sizes, data
+
+
+def wave_postprocess(pcm, chunk, flags):
+    """Level 0 (int16, no pads) of a wave that was written as A2_I24 samples `pcm`, `chunk` frames per write, the
+    way the engine makes it when the stream closes (src/waves.c:155-346, 405-451): with NORMALIZE the smallest of
+    the writes' gains 32767 * 256 / peak, 1000 at most, and the float conversion unless that gain is exactly 1;
+    with XFADE the triangular window, the overlap-add and the copy of the first half.  Every operation in the
+    reference's types (np.float32 / np.float64), one by one."""
+    x = np.asarray(pcm, dtype=np.int32)
+    n = len(x)
+    f32, f64 = np.float32, np.float64
+    if flags & REVMIX:
+        raise ValueError("revmix: the reference's result reads an unwritten pad sample")
+    if flags & XFADE and n < 2:
+        raise ValueError("xfade needs two samples")
+    gain = f32(1.0)
+    if flags & NORMALIZE:
+        if not chunk:
+            raise ValueError("normalize needs the size of the writes")
+        gain = f32(1000.0)
+        with np.errstate(over="ignore"):
+            mag = np.maximum(x, -x)                       # (the negation wraps: INT32_MIN stays negative)
+        for lo in range(0, n, chunk):
+            peak = max(0, int(mag[lo:lo + chunk].max()))
+            bg = f32(8388352.0) / f32(peak) if peak else f32(1.0)
+            if bg < gain:
+                gain = bg
+    if gain == f32(1.0):
+        d = (x >> 8).astype(np.int16)
+    else:
+        g2 = gain / f32(256.0)
+        p = x.astype(np.float32) * g2                     # (float32 array * float32 scalar: a float32 multiply)
+        t = np.trunc(p.astype(np.float64))
+        fits = (t > -2147483649.0) & (t < 2147483648.0)   # (cvttss2si: 0x80000000 for what does not fit)
+        d = np.where(fits, t, -2147483648.0).astype(np.int64).astype(np.int32).astype(np.int16)
+    if flags & XFADE:
+        sh = n // 2
+        dg = f64(f32(1.0) / f32(sh))
+        i = np.arange(n, dtype=np.int64)
+        g = np.where(i < sh, i, 2 * sh - i).astype(np.float64) * dg     # (= the reference's running sum, exactly)
+        d = np.trunc(d.astype(np.float64) * g).astype(np.int64).astype(np.int16)
+        with np.errstate(over="ignore"):
+            d[:sh] = d[:sh] + d[sh:2 * sh]                # (int16 addition wraps)
+        d[sh:2 * sh] = d[:sh]
+        if n & 1:
+            d[n - 1] = d[0]                               # (the copy loop runs upwards: d[2 sh] = new d[sh] = d[0])
+    return d
 
 
 def test_waves(count=24):

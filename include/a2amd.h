@@ -170,9 +170,13 @@ int  a2amd_wave_drop(a2amd_ctx *ctx, uint64_t key);
  *                                   (>> 8 into int16, waves.c:174-177), pads (a2_fix_pad) and mip levels
  *                                   (a2_render_mipmaps) built there: w->data[] is not read, nothing is copied
  *                                   from the host.  w->size[0] must be the capture's frame count and the flags
- *                                   free of A2_NORMALIZE / A2_XFADE / A2_REVMIX (the host-side post-processing
- *                                   of waves.c:300-390 is not restated): A2AMD_EUNSUPPORTED otherwise, and for a
- *                                   capture on another GPU - the caller uploads the engine's copy instead. */
+ *                                   free of A2_NORMALIZE / A2_XFADE / A2_REVMIX: A2AMD_EUNSUPPORTED otherwise, and
+ *                                   for a capture on another GPU - the caller uploads the engine's copy instead.
+ *   a2amd_wave_upload_captured_post(ctx, key, w, cap, chunk)     (include/a2amd_wavepost.h, included below)
+ *                                   the same for waves with A2_NORMALIZE and / or A2_XFADE: the peak search, the
+ *                                   gain, the float conversion and the crossfade of waves.c:155-346, 405-451 run
+ *                                   on the device, bit for bit.  A2_REVMIX stays with the host: the reference's
+ *                                   own result reads an unwritten pad sample and is not reproducible. */
 typedef struct a2amd_capture a2amd_capture;
 int  a2amd_capture_begin(a2amd_ctx *ctx);
 int  a2amd_capture_end(a2amd_ctx *ctx, a2amd_capture **cap);
@@ -436,5 +440,7 @@ int  a2amd_last_batch(const a2amd_ctx *ctx, a2amd_batch_info *bi);
 
 /* The noise generator in closed form: a2amd_fragment_repeat_noise(), a2amd_noise_jump(), a2amd_noise_draws(). */
 #include "a2amd_noise.h"
+/* Rendered waves with "normalize" / "xfade", post-processed on the device: a2amd_wave_upload_captured_post(), a2amd_wavepost_host(). */
+#include "a2amd_wavepost.h"
 
 #endif /* A2AMD_H */
