@@ -20,9 +20,7 @@
 #define A2D_MIPS      10
 #define A2D_FBD_BUFSIZE 131072          // fbdelay.c:27
 #define A2D_MAXPHINC  512               // a2_waves.h:57
-#ifndef A2D_COEF_WORDS
 #define A2D_COEF_WORDS 3                 // words per entry of the Hermite coefficient table (a2amd_fast.hip)
-#endif
 #define A2D_WTOSC_MAXLENGTH (0x01000000 - 1 - 131)   // wtosc.c:55
 
 // unit kinds: numerically equal to a2amd_unitkind
@@ -192,12 +190,8 @@ enum { XW_SLOT = 0, XW_MODE = 1 };
 #define A2D_XIO_HALF ((size_t)A2D_MAXBATCH * 8 * A2D_FRAG)	// words per direction of a slot
 #define A2D_XIO_SLOT (2 * A2D_XIO_HALF)
 
-#ifndef A2D_FAST_FCH
 #define A2D_FAST_FCH 8	// k_leaf_oscpan: fragments per chunk (the host sizes the time slices by it)
-#endif
-#ifndef A2D_OSC2_FCH
 #define A2D_OSC2_FCH 4	// k_leaf_osc2pan: fragments per chunk
-#endif
 #define A2D_MAXVPW   32       // voices one wavefront may walk per fragment
 
 struct A2DParams {

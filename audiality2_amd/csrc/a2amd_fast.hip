@@ -28,7 +28,6 @@
 #include <type_traits>
 #include <algorithm>
 #include <stdlib.h>
-#include <type_traits>
 #include "a2amd_device.h"
 #include "a2amd_dsp.h"
 #include "a2amd_fm.h"
@@ -47,12 +46,7 @@ __global__ void k_build_coef(const int16_t *__restrict__ pool, int *__restrict__
 	int *e = coef + A2D_COEF_WORDS * (size_t)j;
 	e[0] = a;
 	e[1] = b;
-#if A2D_COEF_WORDS == 4
-	e[2] = c;
-	e[3] = d0;
-#else
 	e[2] = (int)(((unsigned)c << 16) | ((unsigned)d0 & 0xffffu));
-#endif
 }
 
 // coefficient entries for pool samples [lo, hi): needs pool[lo - 1 .. hi + 1]
@@ -343,9 +337,7 @@ DEV void osc_to_mem(int *w, const OscS &o)
 	w[OW_A] = o.a.value; w[OW_A + 1] = o.a.target; w[OW_A + 2] = o.a.delta; w[OW_A + 3] = o.a.timer;
 }
 
-#ifndef OSC1_WPE
 #define OSC1_WPE 4
-#endif
 __global__ __launch_bounds__(64 * FAST_WPB) __attribute__((amdgpu_waves_per_eu(OSC1_WPE, OSC1_WPE)))
 void k_leaf_oscpan(const A2DParams *__restrict__ pp, const int *__restrict__ list, int nlist, int vpw,
 		int ysplit, const A2DVoice *__restrict__ voices, const int *ustate,
@@ -737,11 +729,9 @@ DEV void osc_to_lanes(int (&so)[OV_NWORDS], const OscS &o, bool me)
 	WRL(so[OV_A + 2], o.a.delta); WRL(so[OV_A + 3], o.a.timer);
 }
 
-#ifndef OSC2_WPE
 #define OSC2_WPE 4	// (round 2: 3 wavefronts per SIMD with 143 registers and no spills beat 4 with 128 and 39 spills by a
 			// fifth.  Round 3: with only the settled loop's values parked in registers the kernel needs 118 -
 			// 4 wavefronts without spills: 2.30 -> 2.24 ms at configs[3]; 3 wavefronts of the same code: 2.40)
-#endif
 __global__ __launch_bounds__(64 * FAST_WPB) __attribute__((amdgpu_waves_per_eu(OSC2_WPE, OSC2_WPE)))
 void k_leaf_osc2pan(const A2DParams *__restrict__ pp, const int *__restrict__ list, int nlist, int vpw,
 		int ysplit, const A2DVoice *__restrict__ voices, const int *ustate, int *ustage,
@@ -875,11 +865,9 @@ void k_leaf_osc2pan(const A2DParams *__restrict__ pp, const int *__restrict__ li
 				cur_nch = rdl(my_nch, v);
 			}
 			const int v0 = rdl(v0l, v), v1 = rdl(v1l, v);
-			// one oscillator after the other: the eight coefficient entries of a
-			// chunk (4 fragments x 2 taps, 24 registers) in flight at a time
-#ifndef OSC2_SEQ
 			// the coefficient entries of BOTH oscillators (4 fragments x 2 taps x 2: 48 registers) are in
-			// flight before either is used (one oscillator after the other: -DOSC2_SEQ, 4 % slower)
+			// flight before either is used (one oscillator after the other, 24 registers in flight at a
+			// time, was 4 % slower)
 			int xs[OSC2_FCH];
 			uint64_t endph[2];
 			Coef4 ka[2][OSC2_FCH], kb[2][OSC2_FCH];
@@ -890,51 +878,6 @@ void k_leaf_osc2pan(const A2DParams *__restrict__ pp, const int *__restrict__ li
 				const unsigned mm = (unsigned)rdl(od[o][OD_MM], v), dph = (unsigned)rdl(od[o][OD_DPH], v);
 				const unsigned sizem = (unsigned)rdl(od[o][OD_SIZEM], v), doff = (unsigned)rdl(od[o][OD_DOFF], v);
 				amps[o] = rdl(amp_l[o], v);
-				const uint64_t phase = (uint64_t)(unsigned)rdl(phlo_l[o], v) |
-						((uint64_t)(unsigned)rdl(phhi_l[o], v) << 32);
-				uint64_t ph = (phase >> mm) + (uint64_t)before * dph;
-				const unsigned ldph = lane_dph(lane, dph);
-				const int cb = coef_base(doff);
-				uint64_t phs[OSC2_FCH];
-				if(!(sizem & (sizem - 1)) && !(ph >> 48)) {
-					const uint64_t mask = ((uint64_t)sizem << 24) - 1;
-#pragma unroll
-					for(int j = 0; j < OSC2_FCH; ++j)
-						phs[j] = (ph + (uint64_t)dph * pre[j]) & mask;
-					ph = phs[OSC2_FCH - 1] + (uint64_t)dph * (unsigned)nfr[OSC2_FCH - 1];
-				} else {
-#pragma unroll
-					for(int j = 0; j < OSC2_FCH; ++j) {
-						ph = wrap_phase(ph, sizem);
-						phs[j] = ph;
-						ph += (uint64_t)dph * (unsigned)nfr[j];
-					}
-				}
-#pragma unroll
-				for(int j = 0; j < OSC2_FCH; ++j) {
-					pa[o][j] = tap_phase(phs[j], ldph);
-					asm("" : "+v"(pa[o][j]));
-					pb[o][j] = pa[o][j] + (dph >> 17);
-					ka[o][j] = coef_at(crs, cb, pa[o][j]);
-					kb[o][j] = coef_at(crs, cb, pb[o][j]);
-				}
-				endph[o] = ph << mm;
-			}
-#pragma unroll
-			for(int o = 0; o < 2; ++o)
-#pragma unroll
-				for(int j = 0; j < OSC2_FCH; ++j) {
-					const int y = mul64s(hermite_c(ka[o][j], pa[o][j]) + hermite_c(kb[o][j], pb[o][j]), amps[o], 17);
-					xs[j] = o ? wadd(xs[j], y) : y;
-				}
-#else
-			int xs[OSC2_FCH];
-			uint64_t endph[2];
-#pragma unroll
-			for(int o = 0; o < 2; ++o) {
-				const unsigned mm = (unsigned)rdl(od[o][OD_MM], v), dph = (unsigned)rdl(od[o][OD_DPH], v);
-				const unsigned sizem = (unsigned)rdl(od[o][OD_SIZEM], v), doff = (unsigned)rdl(od[o][OD_DOFF], v);
-				const int amp = rdl(amp_l[o], v);
 				const uint64_t phase = (uint64_t)(unsigned)rdl(phlo_l[o], v) |
 						((uint64_t)(unsigned)rdl(phhi_l[o], v) << 32);
 				uint64_t ph = (phase >> mm) + (uint64_t)before * dph;
@@ -956,25 +899,24 @@ void k_leaf_osc2pan(const A2DParams *__restrict__ pp, const int *__restrict__ li
 						ph += (uint64_t)dph * (unsigned)nfr[j];
 					}
 				}
-				Coef4 ka[OSC2_FCH], kb[OSC2_FCH];
-				unsigned pa[OSC2_FCH], pb[OSC2_FCH];
 #pragma unroll
 				for(int j = 0; j < OSC2_FCH; ++j) {
-					pa[j] = tap_phase(phs[j], ldph);
-					asm("" : "+v"(pa[j]));	// (32 bit offsets: scalar-base loads, as in k_leaf_oscpan)
-					pb[j] = pa[j] + (dph >> 17);
-					ka[j] = coef_at(crs, cb, pa[j]);
-					kb[j] = coef_at(crs, cb, pb[j]);
-				}
-#pragma unroll
-				for(int j = 0; j < OSC2_FCH; ++j) {
-					const int y = mul64s(hermite_c(ka[j], pa[j]) + hermite_c(kb[j], pb[j]), amp, 17);
-					// the second oscillator adds into the scratch buffer (wrap-around)
-					xs[j] = o ? wadd(xs[j], y) : y;
+					pa[o][j] = tap_phase(phs[j], ldph);
+					asm("" : "+v"(pa[o][j]));	// (32 bit offsets: scalar-base loads, as in k_leaf_oscpan)
+					pb[o][j] = pa[o][j] + (dph >> 17);
+					ka[o][j] = coef_at(crs, cb, pa[o][j]);
+					kb[o][j] = coef_at(crs, cb, pb[o][j]);
 				}
 				endph[o] = ph << mm;
 			}
-#endif
+#pragma unroll
+			for(int o = 0; o < 2; ++o)
+#pragma unroll
+				for(int j = 0; j < OSC2_FCH; ++j) {
+					const int y = mul64s(hermite_c(ka[o][j], pa[o][j]) + hermite_c(kb[o][j], pb[o][j]), amps[o], 17);
+					// the second oscillator adds into the scratch buffer (wrap-around)
+					xs[j] = o ? wadd(xs[j], y) : y;
+				}
 #pragma unroll
 			for(int j = 0; j < OSC2_FCH; ++j) {
 				const int x = (lane < nfr[j]) ? xs[j] : 0;
@@ -1095,9 +1037,7 @@ void k_leaf_osc2pan(const A2DParams *__restrict__ pp, const int *__restrict__ li
 // batch; the sums of RECS_FCH fragments of all the wavefront's voices on one bus go
 // out in one atomic add per fragment and channel.
 #define RECS_FCH 4
-#ifndef RECS_WPB
 #define RECS_WPB 8		// wavefronts per workgroup
-#endif
 
 DEV void osc_init_s(const FastPtrs &g, OscS &o, int pitch)
 {
@@ -1171,91 +1111,23 @@ DEV int writelane_s(int y, int val, int sel)
 	return a2d_writelane(val, sel, y);
 }
 
-// One window of f12_process (filter12.c:74-119) over the frames a wavefront holds one per
-// lane: the recurrence runs on the SCALAR unit - per frame a v_readlane, 17 to 26 scalar
-// operations (nine of them the dependent chain d1 -> d1) and a v_writelane.  Measured on a
-// wavefront that has its SIMD to itself (a song: -DRECS_PROF): ~7 cycles per instruction.
-DEV int filt_window_s(FiltS &fs, int x, int off, int len, int lane)
-{
-	int f0 = fs.f1, df = 0, f1 = fs.f1;
-	ramp_prepare_s(fs.q, len);
-	if(fs.ramp) {		// the host ran the cutoff ramper and f12_pitch2coeff (R_F1RAMP)
-		f1 = fs.f1next;
-		df = rfl(wadd(wsub(f1, f0), len >> 1) / len);
-	}
-	int qv = fs.q.value, d1 = fs.d1, d2 = fs.d2;
-	const int qd = fs.q.delta, lp = fs.lp, bp = fs.bp, hp = fs.hp;
-	// (input and output in registers of their own: reading frame s + 1 does not wait
-	// for frame s to be written)
-	int y = x;
-	// Three things most windows do not need, each a twelfth to a seventh of the frame's
-	// instructions (the variant is chosen per window, uniformly):
-	//   bit 0  bp = hp = 0, the plain low-pass most voices are: their products drop out of the sum
-	//   bit 1  q is not ramping
-	//   bit 2  the cutoff is not ramping
-	auto frame = [&](int s, auto variant) {
-		constexpr int V = decltype(variant)::value;
-		const int xin = rdl(x, off + s);
-		const int f = f0 >> 12, qq = qv >> 12;
-		const int d1s = d1 >> 4;
-		const int l = wadd(d2, wmul(f, d1s) >> 8);
-		const int h = wsub(wsub(xin >> 5, l), wmul(qq, d1s) >> 8);
-		const int b = wadd(wmul(f, h >> 4) >> 8, d1);
-		const int out = ((V & 1) ? wmul(l, lp) : wadd(wadd(wmul(l, lp), wmul(b, bp)), wmul(h, hp))) >> 3;
-		d1 = b;
-		d2 = l;
-		if(!(V & 4))
-			f0 = wadd(f0, df);
-		if(!(V & 2))
-			qv = wadd(qv, qd);
-		y = writelane_s(y, out, off + s);
-	};
-	// (four frames per trip: the output sums of one frame fill the waits of the next
-	// one's recurrence, and a taken branch costs a wavefront on its own more than an
-	// instruction)
-	auto frames = [&](auto variant) {
-		int s = 0;
-		for(; s + 4 <= len; s += 4) {
-			frame(s, variant);
-			frame(s + 1, variant);
-			frame(s + 2, variant);
-			frame(s + 3, variant);
-		}
-		for(; s < len; ++s)
-			frame(s, variant);
-	};
-	switch(((bp | hp) == 0 ? 1 : 0) | (qd == 0 ? 2 : 0) | (df == 0 ? 4 : 0)) {
-	  case 0: frames(std::integral_constant<int, 0>()); break;
-	  case 1: frames(std::integral_constant<int, 1>()); break;
-	  case 2: frames(std::integral_constant<int, 2>()); break;
-	  case 3: frames(std::integral_constant<int, 3>()); break;
-	  case 4: frames(std::integral_constant<int, 4>()); break;
-	  case 5: frames(std::integral_constant<int, 5>()); break;
-	  case 6: frames(std::integral_constant<int, 6>()); break;
-	  default: frames(std::integral_constant<int, 7>()); break;
-	}
-	fs.d1 = d1;
-	fs.d2 = d2;
-	fs.q.value = qv;	// (= a2_RunRamper(&q, 1) per frame)
-	fs.f1 = f1;
-	fs.ramp = 0;
-	return y;
-}
-
-// Round 4, last: the same window as a relaxation ALONG THE LANES (RECS_JFILT).  Frame s of the window
-// sits in lane s with its own input, cutoff and q; what it needs of frame s - 1 - d1 and d2, i.e. that
+// One window of f12_process (filter12.c:74-119) over the frames a wavefront holds one per lane, as a
+// relaxation ALONG THE LANES (round 4, last).  Frame s of the window sits in lane s with its own
+// input, cutoff and q; what it needs of frame s - 1 - d1 and d2, i.e. that
 // frame's b and l - it reads from lane s - 1 through the DPP wave shift, on the vector unit, every
 // lane at once.  One such step makes one more lane right: lane 0 takes the voice's state (the shift
 // has no source for it and leaves it alone), after step k lanes 0..k hold what f12_process
 // (filter12.c:97-118) computes for frames 0..k, and a lane that is right stays right, because its
 // left neighbour no longer changes.  len - 1 steps of 13 vector instructions (no v_readlane, no
 // v_writelane, no M0, the cutoff and q ramps in closed form per lane, the output sums once per
-// window with lane = frame) against 19 - 28 scalar ones per frame above; what the other lanes
-// compute in the meantime is thrown away, which costs a lone wavefront nothing.  A window that does
-// not begin at frame 0 is rotated to lane 0 and back (ds_bpermute).
-#ifndef RECS_JFILT
-#define RECS_JFILT 1
-#endif
+// window with lane = frame); what the other lanes compute in the meantime is thrown away, which costs
+// a lone wavefront nothing.  A window that does not begin at frame 0 is rotated to lane 0 and back
+// (ds_bpermute).
+// (Rounds 2-4 ran the recurrence on the SCALAR unit instead, frame after frame: per frame a v_readlane,
+// 17 to 26 scalar operations - nine of them the dependent chain d1 -> d1 - and a v_writelane, 19 - 28
+// instructions in all, at the ~7 cycles per instruction measured on a wavefront that has its SIMD to
+// itself (a song: -DRECS_PROF).  profiles/r04_jfilt_ab.txt has the comparison; that window function left
+// the tree with its build switch.)
 #define F12_JSTEP \
 	"s_nop 1\n\t" \
 	"v_mov_b32_dpp %[bsh], %[B] wave_shr:1 row_mask:0xf bank_mask:0xf\n\t" \
@@ -1319,10 +1191,10 @@ DEV int filt_window_j(FiltS &fs, int x, int off, int len, int lane)
 	return (unsigned)(lane - off) < (unsigned)len ? yw : x;
 }
 
-// Round 4: the filter of the records kernels with lane = VOICE.  filt_window_s above runs filter12's
-// recurrence on the scalar unit, a window at a time, in the middle of the voice's walk: ~20 scalar
-// instructions per frame and voice at the 5-7 cycles a lone scalar stream issues at - two thirds of
-// what a scripted filter voice costs.  With RECS_VFILT the walk (lane = frame, scalar control) only
+// Round 4: the filter of the records kernels with lane = VOICE.  The window filter of the time ran
+// filter12's recurrence on the scalar unit, a window at a time, in the middle of the voice's walk: ~20
+// scalar instructions per frame and voice at the 5-7 cycles a lone scalar stream issues at - two thirds
+// of what a scripted filter voice cost.  On this path the walk (lane = frame, scalar control) only
 // renders the oscillators of a window into the voice's row of an LDS tile and works out what the
 // window needs of the filter and of the pan stage - f0 and its step (the host's / the device VM's
 // coefficient records), the q ramp, the mix levels; the volume and pan rampers' values and steps -
@@ -1331,9 +1203,6 @@ DEV int filt_window_j(FiltS &fs, int x, int off, int len, int lane)
 // runs the recurrence over its pending windows in place - 12 vector instructions per frame for up
 // to 64 voices at once - then, lane = frame again, the pan stage reads the rows back window by
 // window.  Filter state (d1, d2) never leaves the lane it is parked in.
-#ifndef RECS_VFILT
-#define RECS_VFILT 1
-#endif
 #define RECS_ENTRY 12		// words per pending window: [j | off << 4 | len << 12 | clamp << 20, f0, df, qv, qd, lp, bp, hp, vol, dvol, pan, dpan]
 #define RECS_VF_FCH 2		// fragments per chunk on that path (rows of the chunk live in LDS)
 DEV int recs_pool_cap(int vpw) { return vpw * RECS_VF_FCH * 2 + 16; }
@@ -1374,12 +1243,12 @@ DEV void recs_body(const A2DParams *__restrict__ pp, const int *__restrict__ lis
 	const A2DParams &p = *pp;
 	const int wv = rfl((int)(threadIdx.x >> 6));	// (wave-uniform, and known to the compiler as such)
 	const int lane = threadIdx.x & 63;
-	// (skip_empty bit 1: the launcher gave this launch the lane = voice filter, RECS_VFILT - worth it from a
-	// few voices per wavefront up; a song's one-voice wavefronts keep the scalar recurrence)
+	// (skip_empty bit 1: the launcher gave this launch the lane = voice filter - worth it from a
+	// few voices per wavefront up; a song's one-voice wavefronts keep the window filter)
 	// (VFT, a kernel of its own: with both filters in one kernel the window filter's registers took
 	// k_leaf_recs<1, 1> from 127 to 132 vector registers - four wavefronts per SIMD to three - and a launch
 	// uses only one of the two)
-	constexpr bool VF = FILT && RECS_VFILT && VFT;
+	constexpr bool VF = FILT && VFT;
 	skip_empty &= 1;
 	const int first = gw * vpw;
 	// (a wavefront past the end of the list still meets the others at the barriers)
@@ -1472,7 +1341,7 @@ DEV void recs_body(const A2DParams *__restrict__ pp, const int *__restrict__ lis
 		for(int j = 0; j < RECS_FCH; ++j)
 			acc0[j] = acc1[j] = 0;
 		int cur_off = nv ? rdl(my_off, 0) : -1, cur_nch = rdl(my_nch, 0);
-		// RECS_VFILT: the windows walked but not yet filtered and panned - per voice (lane = voice) a run of
+		// the lane = voice filter (VF): the windows walked but not yet filtered and panned - per voice (lane = voice) a run of
 		// pool entries [wbeg, wend) - and the turn-round that works them off
 		int wbeg = 0, wend = 0, pool_n = 0;
 		int *const tile = recs_dyn + wv * recs_wave_words(vpw);
@@ -1672,7 +1541,7 @@ DEV void recs_body(const A2DParams *__restrict__ pp, const int *__restrict__ lis
 					t_osc += w1 - w0;
 #endif
 					if(FILT)
-						x = RECS_JFILT ? filt_window_j(fs, x, off, len, lane) : filt_window_s(fs, x, off, len, lane);
+						x = filt_window_j(fs, x, off, len, lane);
 #ifdef RECS_PROF
 					asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" : "+v"(x));
 					t_flt += __builtin_readcyclecounter() - w1;
@@ -1918,13 +1787,8 @@ DEV void recs_body(const A2DParams *__restrict__ pp, const int *__restrict__ lis
 }
 
 
-#ifdef RECS_WPE
-#define RECS_ATTR __attribute__((amdgpu_waves_per_eu(RECS_WPE, 8)))
-#else
-#define RECS_ATTR
-#endif
 template<int NOSC, int FILT, int VFT = 0>
-__global__ __launch_bounds__(64 * RECS_WPB) RECS_ATTR
+__global__ __launch_bounds__(64 * RECS_WPB)
 void k_leaf_recs(const A2DParams *__restrict__ pp, const int *__restrict__ list, int nlist, int vpw,
 		const A2DVoice *__restrict__ voices, int *ustate, int *vactive,
 		const int16_t *__restrict__ wavepool, const A2DWave *__restrict__ waves,
@@ -2005,8 +1869,8 @@ int a2d_launch_leaf_recs_all(const A2DParams *dparams, const A2DParams &hp, cons
 	}
 	if(!nblocks)
 		return 0;
-	// (dynamic LDS: the filter kinds' window rows and pool, RECS_VFILT)
-	// (plumbing-sized launches keep the scalar recurrence: no rows, no pool)
+	// (no dynamic LDS - the lane = voice filter's window rows and pool: plumbing-sized launches keep the
+	// window filter)
 	hipLaunchKernelGGL(k_leaf_recs_all, dim3(nblocks), dim3(64 * wpb), 0, (hipStream_t)stream, dparams, segs, vpw,
 			hp.voices, hp.ustate, hp.vactive, hp.wavepool, hp.waves, hp.ptab, hp.busmem, skip_mask);
 	return (int)hipGetLastError();
@@ -2018,18 +1882,18 @@ int a2d_launch_leaf_recs(const A2DParams *dparams, const A2DParams &hp, int nosc
 	if(nlist <= 0)
 		return 0;
 	vpw = min(max(vpw, 1), 64);
-	// The lane = voice filter (RECS_VFILT) pays from a few voices per wavefront up: at 4 096 voices and
+	// The lane = voice filter pays from a few voices per wavefront up: at 4 096 voices and
 	// more the launch gets 4-8 voices per wavefront (fewer, fatter wavefronts: the scalar walk of a voice
 	// is latency, the recurrence 12 vector instructions per frame for all of a wavefront's voices).
 	// (measured, 64 fragments of voices with a split window and a pitch ramp in every second fragment: 16 384
 	// voices 3.46 -> 2.24 ms, 65 536: 13.5 -> 10.0; 4 096: 0.99 -> 1.36.  Against the window filter along the
-	// lanes (RECS_JFILT, the end of round 4) the margin is thinner - 12 288 voices 2.02 (window filter) / 2.17 ms,
+	// lanes (filt_window_j, the end of round 4) the margin is thinner - 12 288 voices 2.02 (window filter) / 2.17 ms,
 	// 16 384: 2.58 / 2.21, 32 768: 4.97 / 5.00, 65 536: 9.7 with it; two oscillators 16 384: 4.29 / 3.88,
 	// 32 768: 8.24 / 6.58 (profiles/r04_jfilt_ab.txt) - hence the threshold.  A2AMD_VFILT=0 / 1
 	// forces it off / on: A/B measurements, and the tests run the path at sizes an oracle can follow.)
 	const char *fv = getenv("A2AMD_VFILT");
 	const int force_vf = fv ? atoi(fv) : -1;
-	const bool vf = filt && RECS_VFILT && (force_vf >= 0 ? force_vf != 0 : nlist >= 16384);
+	const bool vf = filt && (force_vf >= 0 ? force_vf != 0 : nlist >= 16384);
 	if(vf && !getenv("A2AMD_RVPW"))
 		vpw = min(max((nlist + 4095) / 4096, 4), 8);
 	if(vf)
@@ -2097,32 +1961,11 @@ int a2d_launch_leaf_recs(const A2DParams *dparams, const A2DParams &hp, int nosc
 // bus sums (configs[4]'s share, 32 768 voices on 128 buses: 2.42 -> 1.12 ms).
 #define FILT_MAXV   64
 #define FILT_PITCH  65
-#ifndef FILT_ROWAHEAD
-#define FILT_ROWAHEAD 1	// filt_row reads the next sixteen frames while it filters these sixteen
-#endif
-#ifndef FILT_WAVES
 #define FILT_WAVES  16	// wavefronts per workgroup: one filters, the others run the oscillators / pans.  (One
 			// workgroup of 16 per CU with 64 voices - every lane of the filter wavefront busy - since the
 			// oscillator wavefronts have their all-settled loop; 8 and two workgroups per CU before.)
-#endif
-#ifndef FILT_BATCH
 #define FILT_BATCH  5	// settled voices whose coefficient loads are in flight together
-#endif
-#ifndef FILT_PARTNER
-#define FILT_PARTNER 0	// voices of an oscillator wavefront that shares the filter wavefront's SIMD
-#endif
-// Two shapes measured in round 3 and left switched off (tools/filt_sweep_*.sh, profiles/r03_filt_sweep.jsonl:
-// 1.25 - 1.38 ms against 1.26 ms per 256 fragments x 16 384 voices - the oscillator wavefronts that
-// sit next to a filter wavefront just wait longer at the barrier):
-#ifndef FILT_LIGHT
-#define FILT_LIGHT -1	// voices of an oscillator wavefront next to the OTHER workgroup's filter wavefront (-1: even share)
-#endif
-#ifndef FILT_FASTV
 #define FILT_FASTV 6	// most voices an oscillator wavefront takes through its all-settled loop (0: the general loop only)
-#endif
-#ifndef FILT_ROT
-#define FILT_ROT 0	// 1: workgroups that share a CU put their filter wavefronts on different SIMDs
-#endif
 enum { FV_Q = 0, FV_LP = 4, FV_BP, FV_HP, FV_F1, FV_D1, FV_D2, FV_NWORDS };
 
 // one filter step (f12_process, filter12.c:98-117).  The filter wavefront's chain of dependent
@@ -2149,7 +1992,6 @@ template<bool LPRAW, bool QREST>
 DEV void filt_row(int *row, int n, int ff, int lp, int bp, int hp, int &d1, int &d2, int &qv, int qdelta)
 {
 	if(n == A2D_FRAG) {
-#if FILT_ROWAHEAD
 		// (round 4: the next sixteen frames are on their way from the LDS while these sixteen are filtered -
 		// two register sets; before, each of a fragment's four groups waited out its own LDS round trip)
 		int xb[2][16];
@@ -2173,24 +2015,6 @@ DEV void filt_row(int *row, int n, int ff, int lp, int bp, int hp, int &d1, int 
 			for(int k = 0; k < 16; ++k)
 				row[g * 16 + k] = xb[g & 1][k];
 		}
-#else
-#pragma unroll 1
-		for(int s0 = 0; s0 < A2D_FRAG; s0 += 16) {
-			int x[16];
-#pragma unroll
-			for(int k = 0; k < 16; ++k)
-				x[k] = row[s0 + k];
-#pragma unroll
-			for(int k = 0; k < 16; ++k) {
-				x[k] = filt_step<LPRAW>(x[k], qv >> 12, ff, lp, bp, hp, d1, d2);
-				if(!QREST)
-					qv = wadd(qv, qdelta);
-			}
-#pragma unroll
-			for(int k = 0; k < 16; ++k)
-				row[s0 + k] = x[k];
-		}
-#endif
 		return;
 	}
 	for(int s = 0; s < n; ++s) {
@@ -2200,19 +2024,13 @@ DEV void filt_row(int *row, int n, int ff, int lp, int bp, int hp, int &d1, int 
 	}
 }
 
-#ifndef FILT_WPE
 #define FILT_WPE 4
-#endif
-#ifndef FILT_AHEAD
-#define FILT_AHEAD 1	// the all-settled loop asks for a fragment's coefficient entries a step ahead
-#endif
 // a workgroup barrier that waits for this wavefront's LDS traffic only: loads from device memory
 // stay in flight across it (__syncthreads() is a fence: it waits for them too)
 DEV void filt_barrier()
 {
 	asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }
-__device__ unsigned g_filt_turn[4096];	// FILT_ROT == 2: workgroups arriving on a CU take turns (k_leaf_oscfiltpan)
 // Round 6: the body is shared by two kernels - NOSC = 1, k_leaf_oscfiltpan (wtosc -> filter12 -> panmix, configs[2]),
 // and NOSC = 2, k_leaf_osc2filtpan: wtosc; wtosc (adding); filter12; panmix, the usual subtractive note (every lead of the
 // reference's benchmark/k2*.a2s), which rounds 2-5 rendered through the records / window kernels whether or not it
@@ -2229,7 +2047,7 @@ __device__ unsigned g_filt_turn[4096];	// FILT_ROT == 2: workgroups arriving on 
 // What configs[2] takes on it is measured)
 // Voices an oscillator wavefront of the two-oscillator kernel takes through its all-settled loop: the LAUNCHER deals at
 // most FILT2_LAUNCHV = 3 (a2d_osc2filtpan_max_vpg) - four tap pairs x 3 registers per voice in flight across the barrier
-// (FILT_AHEAD): the 4-voice loop holds 27 - 29 scratch reloads and as many vmcnt(0) stalls per trip
+// (the loads asked for a step ahead): the 4-voice loop holds 27 - 29 scratch reloads and as many vmcnt(0) stalls per trip
 // (profiles/r06_oscfiltpan_spill_sites.txt) and MEASURED 3.5x slower (16 384 voices x 256 fragments: 48 voices per
 // workgroup = 4 per wavefront 3.83 ms, 32 = 2 - 3 per wavefront 1.09 ms, 64 = 5 - 6 per wavefront, general loop, 1.50 ms;
 // profiles/r06_osc2filtpan_shapes.txt).  The KERNEL is nevertheless built with the 4-voice loop in it (FILT2_FASTV 4;
@@ -2238,12 +2056,8 @@ __device__ unsigned g_filt_turn[4096];	// FILT_ROT == 2: workgroups arriving on 
 // (profiles/r06_fastv_build_ab.txt) - although the 2- and 3-voice loops and the filter wavefront's loop it executes
 // are the same code in both builds (same instruction counts and event order: tools/r06 notes in DESIGN 6).  Where the
 // code sits is what is left; NOT understood, and kept because it is measured.
-#ifndef FILT2_FASTV
 #define FILT2_FASTV 4
-#endif
-#ifndef FILT2_LAUNCHV
 #define FILT2_LAUNCHV 3
-#endif
 template<int NOSC>
 DEV void oscfiltpan_body(const A2DParams *__restrict__ pp, const int *__restrict__ list, int nlist, int vpg,
 		const A2DVoice *__restrict__ voices, int *ustate, const int16_t *__restrict__ wavepool,
@@ -2268,45 +2082,17 @@ DEV void oscfiltpan_body(const A2DParams *__restrict__ pp, const int *__restrict
 #define FILT_FRAMES(f) ((int)rfl((int)p.fragframes[f]))
 #define FILT_START(f)  ((int)rfl((int)p.fragstart[f]))
 
-	// Which wavefront filters, and which oscillator wavefronts sit next to a filter wavefront.
-	// Where a wavefront runs is the hardware's choice (observed: wavefronts w and w + 4 of a
-	// workgroup share a SIMD, simd = {0, 2, 1, 3}[(w + s) & 3] with s changing from workgroup to
-	// workgroup), so with FILT_ROT == 2 the roles follow the PHYSICAL SIMD ids (s_getreg HW_ID):
-	// the workgroups that arrive on a CU take turns (a counter per CU in device memory) putting
-	// their filter wavefront - a stream of dependent instructions that wants a SIMD's issue slots -
-	// on SIMD 0 and on SIMD 1; the other wavefront of that SIMD stays idle ("partner"), and the
-	// oscillator wavefronts that sit on the OTHER workgroup's filter SIMD take fewer voices ("light").
+	// Wavefront 0 filters.  Where a wavefront runs is the hardware's choice (observed: wavefronts w and
+	// w + 4 of a workgroup share a SIMD, simd = {0, 2, 1, 3}[(w + s) & 3] with s changing from workgroup
+	// to workgroup), so every fourth wavefront sits on the filter's SIMD: those stay idle ("partner") and
+	// leave its issue slots to the filter - a stream of dependent instructions.
 	// The workgroup's share of a bus, fragment by fragment (a ring of three like the tiles): where all
 	// its voices mix into ONE stereo bus the oscillator / pan wavefronts add their sums here (LDS
 	// atomics) and an idle wavefront next to the filter ("flusher") adds the total to the bus in device
 	// memory one step later - one pair of global atomics per workgroup and fragment instead of one per
 	// wavefront (16 384 voices straight into the root bus: every wavefront of the chip on the same 128 words).
 	__shared__ int s_acc[3][2][A2D_FRAG];
-	__shared__ int s_simd[FILT_WAVES];
-	__shared__ int s_target;
-	int fw = 0, my_simd = wv & 3, tgt = 0;
-	if(FILT_ROT == 2) {
-		my_simd = (int)__builtin_amdgcn_s_getreg(2308) & 3;		// HW_ID.simd_id
-		if(lane == 0)
-			s_simd[wv] = my_simd;
-		if(threadIdx.x == 0) {
-			const unsigned hw = __builtin_amdgcn_s_getreg(63492);	// HW_ID: cu_id 11:8, sh_id 12, se_id 15:13
-			const unsigned xcc = __builtin_amdgcn_s_getreg(6164) & 15u;	// XCC_ID
-			const unsigned key = (xcc << 8) | ((hw >> 8) & 255u);
-			s_target = (int)(atomicAdd(&g_filt_turn[key & 4095u], 1u) & 1u);
-		}
-		__syncthreads();
-		tgt = s_target;
-		fw = -1;
-		for(int k = FILT_WAVES - 1; k >= 0; --k)
-			if(s_simd[k] == tgt)
-				fw = k;		// the first wavefront on that SIMD
-		if(fw < 0) {		// (nobody there: the roles by wavefront number, as without FILT_ROT)
-			fw = 0;
-			tgt = s_simd[0];
-		}
-	} else if(FILT_ROT)
-		fw = (int)((blockIdx.x >> 8) & 3u);
+	const int fw = 0;
 	if(wv == fw) {
 		// ================= the filter wavefront: lane = voice =================
 		// (its dependent chain is the workgroup's critical path: first in line for
@@ -2331,14 +2117,8 @@ DEV void oscfiltpan_body(const A2DParams *__restrict__ pp, const int *__restrict
 		// the common shapes, decided for the whole wavefront: low pass only (for the batch: the
 		// oscillator wavefronts come to the same answer from the same words), q at rest (per fragment)
 		const bool lponly = __all(!mine || (fv[FV_BP] == 0 && fv[FV_HP] == 0));
-#ifdef FILT_PROF
-		long long tb = 0, tw = 0;
-#endif
 		for(int st = -1; st <= nfrags; ++st) {
 			const int f = st;
-#ifdef FILT_PROF
-			const long long c0 = __builtin_readcyclecounter();
-#endif
 			if(f >= 0 && f < nfrags && mine) {
 				const int n = FILT_FRAMES(f);
 				int *row = tiles + (f % 3) * tsize + lane * FILT_PITCH;
@@ -2360,20 +2140,8 @@ DEV void oscfiltpan_body(const A2DParams *__restrict__ pp, const int *__restrict
 				fv[FV_D1] = d1;
 				fv[FV_D2] = d2;
 			}
-#ifdef FILT_PROF
-			const long long c1 = __builtin_readcyclecounter();
-#endif
 			__syncthreads();
-#ifdef FILT_PROF
-			tb += c1 - c0;
-			tw += __builtin_readcyclecounter() - c1;
-#endif
 		}
-#ifdef FILT_PROF
-		if((blockIdx.x == 7 || blockIdx.x == 263) && lane == 0 && nfrags > 100)
-			printf("block %d wave %d simd %d cu %d (filter, %d voices): %lld cycles filtering, %lld waiting (%d fragments)\n",
-					(int)blockIdx.x, wv, (int)__builtin_amdgcn_s_getreg(2308), (int)__builtin_amdgcn_s_getreg(6660), nv, tb, tw, nfrags);
-#endif
 		if(mine) {
 			int *w1 = ustate + (size_t)u1 * A2D_USTATE;
 #pragma unroll
@@ -2388,44 +2156,25 @@ DEV void oscfiltpan_body(const A2DParams *__restrict__ pp, const int *__restrict
 	// ============ oscillator / pan wavefronts: lane = frame, voices [vb, ve) ============
 	// Every fourth wavefront of a workgroup lands on the SIMD of wavefront 0, the filter, whose
 	// stream of dependent instructions is the workgroup's critical path: those "partner"
-	// wavefronts take FILT_PARTNER voices each (0: they only meet the others at the barriers) -
-	// what the filter's SIMD has left over when the other three carry the rest of the
-	// oscillator / pan work - and the other wavefronts share the remaining voices evenly.
-	// With FILT_ROT two workgroups share a CU, their filter wavefronts on SIMDs fw and fw ^ 1: the
-	// oscillator wavefronts of THIS workgroup that run on SIMD fw ^ 1 sit next to the other
-	// workgroup's filter wavefront and take fewer voices ("light": FILT_LIGHT each, -1 = an even
-	// share), so that the four SIMDs of the CU carry about the same number of instructions.
-	int npart = FILT_WAVES / 4 - 1;			// the other wavefronts on the filter's SIMD
-	int nlight = (FILT_ROT && FILT_LIGHT >= 0) ? FILT_WAVES / 4 : 0;
-	int role = 0, ridx = 0;				// 0 full, 1 light, 2 partner; my index among those of my role
-	if(FILT_ROT == 2) {
-		npart = nlight = 0;
-		for(int k = 0; k < FILT_WAVES; ++k) {
-			if(k == fw)
-				continue;
-			const int r = s_simd[k] == tgt ? 2 : (FILT_LIGHT >= 0 && s_simd[k] == (tgt ^ 1)) ? 1 : 0;
-			npart += r == 2;
-			nlight += r == 1;
-			if(k == wv)
-				role = r;
-		}
-		for(int k = 0; k < wv; ++k)
-			if(k != fw)
-				ridx += (s_simd[k] == tgt ? 2 : (FILT_LIGHT >= 0 && s_simd[k] == (tgt ^ 1)) ? 1 : 0) == role;
-	} else {
-		const int sm = wv & 3;
-		role = sm == fw ? 2 : (nlight && sm == (fw ^ 1)) ? 1 : 0;
-		if(role == 2)
-			ridx = (wv >> 2) - 1;			// (wv >> 2 == 0 is the filter wavefront)
-		else if(role == 1)
-			ridx = wv >> 2;
-		else {
-			for(int k = 0; k < sm; ++k)
-				ridx += (k != fw && !(nlight && k == (fw ^ 1)));
-			ridx += (wv >> 2) * (nlight ? 2 : 3);
-		}
+	// wavefronts take no voices - they only meet the others at the barriers, and the first of
+	// them flushes the workgroup's bus sums - and the other wavefronts share the voices evenly.
+	// (Measured in round 3, profiles/r03_filt_sweep.jsonl, and lost: partners with a small share of
+	// voices, and two workgroups per CU with their filter wavefronts rotated onto different SIMDs - by
+	// workgroup number or by physical SIMD id, the oscillator wavefronts next to the other workgroup's
+	// filter given a "light" share: 1.25 - 1.38 ms against 1.26 ms per 256 fragments x 16 384 voices - the
+	// oscillator wavefronts that sit next to a filter wavefront just wait longer at the barrier.)
+	const int npart = FILT_WAVES / 4 - 1;		// the other wavefronts on the filter's SIMD
+	const int sm = wv & 3;
+	const bool partner = sm == fw;
+	int ridx = 0;					// my index among the partners / among the others
+	if(partner)
+		ridx = (wv >> 2) - 1;			// (wv >> 2 == 0 is the filter wavefront)
+	else {
+		for(int k = 0; k < sm; ++k)
+			ridx += k != fw;
+		ridx += (wv >> 2) * 3;
 	}
-	const bool flusher = role == 2 && ridx == 0;
+	const bool flusher = partner && ridx == 0;
 	bool wgbus = false;
 	int wg_off = -1;
 	{
@@ -2468,20 +2217,19 @@ DEV void oscfiltpan_body(const A2DParams *__restrict__ pp, const int *__restrict
 		if(a0) atomicAdd(&dst[lane], a0);
 		if(a1) atomicAdd(&dst[A2D_FRAG + lane], a1);
 	};
-	const int nfull = max(1, FILT_WAVES - 1 - npart - nlight);
-	const int pshare = min(FILT_PARTNER, nv / (FILT_WAVES - 1));	// (never more than an even share)
-	const int lshare = nlight ? min(FILT_LIGHT, nv / (FILT_WAVES - 1)) : 0;
-	const int rem = nv - npart * pshare - nlight * lshare;
+	const int nfull = max(1, FILT_WAVES - 1 - npart);
+	// (The partners' share of the voices: none.  nv > 0 - the grid has no empty workgroups - but the compiler
+	// does not know that, so this min() and what follows from it are live code to it: written out as 0 by hand
+	// the two kernels come out 64 bytes shorter, i.e. other code than the code that was measured.)
+	const int pshare = min(0, nv / (FILT_WAVES - 1));
+	const int rem = nv - npart * pshare;
 	// (an even deal: 32 voices over six wavefronts are 6 6 5 5 5 5 - with ceil(32 / 6) each the
 	// last one got 2 and the two SIMDs that hold the first four carried 12 voices to the third's 8)
 	const int per = rem / nfull, extra = rem % nfull;
 	int vb, ve;
-	if(role == 2) {
-		vb = rem + nlight * lshare + ridx * pshare;
+	if(partner) {
+		vb = rem + ridx * pshare;
 		ve = min(nv, vb + pshare);
-	} else if(role == 1) {
-		vb = rem + ridx * lshare;
-		ve = min(nv, vb + lshare);
 	} else {
 		vb = ridx * per + min(ridx, extra);
 		ve = min(rem, vb + per + (ridx < extra ? 1 : 0));
@@ -2664,7 +2412,7 @@ DEV void oscfiltpan_body(const A2DParams *__restrict__ pp, const int *__restrict
 			}
 		}
 		// The coefficient entries of the fragment the phases stand at, all voices' loads in flight together.
-		// FILT_AHEAD (round 4): asked for at the END of the step before.  The wavefronts of a workgroup march
+		// Round 4: asked for at the END of the step before.  The wavefronts of a workgroup march
 		// in step - a barrier per fragment - so loads issued at the top of a step found all four wavefronts
 		// of a SIMD waiting for them at the same time, with only the pan stage to hide behind; issued before
 		// the barrier they have the barrier and the pan stage to arrive (the barrier itself waits for the
@@ -2688,23 +2436,11 @@ DEV void oscfiltpan_body(const A2DParams *__restrict__ pp, const int *__restrict
 				}
 			}
 		};
-#if FILT_AHEAD
 		if(nfrags > 0)
 			ask();
-#endif
-#ifdef FILT_PROF
-		long long ta = 0, tc = 0, tw = 0;
-#endif
 		for(int st = -1; st <= nfrags; ++st) {
-#ifdef FILT_PROF
-			const long long c0 = __builtin_readcyclecounter();
-#endif
-			// ---- A: the coefficient entries of fragment st + 1 were asked for a step ago (FILT_AHEAD) ----
+			// ---- A: the coefficient entries of fragment st + 1 were asked for a step ago ----
 			const int fa = st + 1;
-#if !FILT_AHEAD
-			if(fa < nfrags)
-				ask();
-#endif
 			// ---- C: pan + mix-down of fragment st - 1 (rows hold zeros past a short fragment's end) ----
 			const int fc = st - 1;
 			if(fc >= 0) {
@@ -2735,9 +2471,6 @@ DEV void oscfiltpan_body(const A2DParams *__restrict__ pp, const int *__restrict
 					}
 				}
 			}
-#ifdef FILT_PROF
-			const long long c1 = __builtin_readcyclecounter();
-#endif
 			// ---- A, second half: Hermite, amplitude, rows of the next tile; the phases move on ----
 			if(fa < nfrags) {
 				const int n = FILT_FRAMES(fa);
@@ -2786,30 +2519,10 @@ DEV void oscfiltpan_body(const A2DParams *__restrict__ pp, const int *__restrict
 					}
 				}
 			}
-#if FILT_AHEAD
 			if(fa + 1 < nfrags)
 				ask();		// (the phases have moved on to fragment fa + 1)
-#endif
-#ifdef FILT_PROF
-			const long long c2 = __builtin_readcyclecounter();
-#endif
-#if FILT_AHEAD
 			filt_barrier();
-#else
-			__syncthreads();
-#endif
-#ifdef FILT_PROF
-			ta += c1 - c0;
-			tc += c2 - c1;
-			tw += __builtin_readcyclecounter() - c2;
-#endif
 		}
-#ifdef FILT_PROF
-		if((blockIdx.x == 7 || blockIdx.x == 263) && lane == 0 && nfrags > 100)
-			printf("block %d wave %d simd %d cu %d (osc/pan, all-settled loop, %d voices, sums %s): %lld cycles loads+pan, %lld hermite+rows, %lld waiting\n",
-					(int)blockIdx.x, wv, (int)__builtin_amdgcn_s_getreg(2308), (int)__builtin_amdgcn_s_getreg(6660), NV,
-					WG ? "in LDS" : "to the bus", ta, tc, tw);
-#endif
 #pragma unroll
 		for(int k = 0; k < NV; ++k)
 			if(lane == k) {
@@ -2842,13 +2555,7 @@ DEV void oscfiltpan_body(const A2DParams *__restrict__ pp, const int *__restrict
 		return;
 	}
 
-#ifdef FILT_PROF
-	long long ta = 0, tc = 0, tw = 0;
-#endif
 	for(int st = -1; st <= nfrags; ++st) {
-#ifdef FILT_PROF
-		const long long c0 = __builtin_readcyclecounter();
-#endif
 		// ---- A: oscillators of fragment st + 1, frame = lane.  The coefficient loads of
 		// the wavefront's first FILT_BATCH settled voices are issued here, the pan stage
 		// of fragment st - 1 runs while they are in flight, the Hermite arithmetic after.
@@ -2937,9 +2644,6 @@ DEV void oscfiltpan_body(const A2DParams *__restrict__ pp, const int *__restrict
 		}
 		if(flusher && wgbus && st >= 2 && !(dbg & 1))
 			bus_flush(st - 2);
-#ifdef FILT_PROF
-		const long long c1 = __builtin_readcyclecounter();
-#endif
 		// ---- A, second half ----
 		if(fa < nfrags) {
 			const int n = FILT_FRAMES(fa);
@@ -3069,24 +2773,11 @@ DEV void oscfiltpan_body(const A2DParams *__restrict__ pp, const int *__restrict
 				}
 			}
 		}
-#ifdef FILT_PROF
-		const long long c2 = __builtin_readcyclecounter();
-#endif
 		__syncthreads();
-#ifdef FILT_PROF
-		ta += c1 - c0;
-		tc += c2 - c1;
-		tw += __builtin_readcyclecounter() - c2;
-#endif
 	}
 	// (step st flushed fragment st - 2; the last fragment's sums were complete at the last barrier)
 	if(flusher && wgbus && nfrags >= 1 && !(dbg & 1))
 		bus_flush(nfrags - 1);
-#ifdef FILT_PROF
-	if((blockIdx.x == 7 || blockIdx.x == 263) && lane == 0 && nfrags > 100)
-		printf("block %d wave %d simd %d cu %d (osc/pan, %d voices): %lld cycles issue+pan, %lld oscillators, %lld waiting\n",
-				(int)blockIdx.x, wv, (int)__builtin_amdgcn_s_getreg(2308), (int)__builtin_amdgcn_s_getreg(6660), mv, ta, tc, tw);
-#endif
 
 	if(mine) {
 		if(dv[DV_SETTLED]) {

@@ -64,7 +64,7 @@ DEV int inter_dwords(const int16_t *d, unsigned ph, unsigned dph16)
 
 // Hermite coefficients of one window, precomputed per wave sample when the wave is
 // uploaded (k_build_coef): a2_Hermite's a, b and - packed - c (high half) and d[i]
-// (low half), one 12 byte entry per wave sample (A2D_COEF_WORDS 4: c and d[i] apart).  The settled paths fetch one entry per tap instead of four samples and go
+// (low half), one 12 byte entry per wave sample (A2D_COEF_WORDS words).  The settled paths fetch one entry per tap instead of four samples and go
 // straight into the three multiply-shift-add steps, which are the reference's own
 // (a2_dsp.h:64-74: x = frac << 7, 32 bit wrap-around products, arithmetic >> 15) - no
 // unpacking of samples, no deriving a, b, c for every output frame.
@@ -73,13 +73,8 @@ DEV int inter_dwords(const int16_t *d, unsigned ph, unsigned dph16)
 // arithmetic in the vector unit; the level's first payload sample is the load's scalar
 // byte offset.  (Round 2 added a byte offset
 // (phase >> 8) * 12 to a scalar base: one more vector instruction per tap.)
-#if A2D_COEF_WORDS == 4
-typedef int Coef4 __attribute__((ext_vector_type(4)));		// a, b, c, d0
-#define A2D_COEF_LOAD "llvm.amdgcn.struct.buffer.load.v4i32"
-#else
 typedef int Coef4 __attribute__((ext_vector_type(3)));		// a, b, c:d0 (the halves come apart inside the adds: SDWA)
 #define A2D_COEF_LOAD "llvm.amdgcn.struct.buffer.load.v3i32"
-#endif
 typedef int CoefRsrc __attribute__((ext_vector_type(4)));
 extern "C" __device__ Coef4 a2d_coef_load(CoefRsrc rsrc, int vindex, int voffset, int soffset, int aux)
 		__asm(A2D_COEF_LOAD);
@@ -104,15 +99,11 @@ DEV int coef_base(unsigned doff) { return (int)(doff * (4u * A2D_COEF_WORDS)); }
 // of its operand (SDWA) - the compiler spells it as a shift and a mask
 DEV int frac_x(unsigned ph)
 {
-#ifdef A2D_NO_SDWA_X
-	return (int)((ph & 0xffu) << 7);
-#else
 	int x;
 	const int seven = 7;
 	asm("v_lshlrev_b32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_0"
 			: "=v"(x) : "v"(seven), "v"(ph));
 	return x;
-#endif
 }
 
 DEV int hermite_c(const Coef4 k, unsigned ph)
@@ -120,13 +111,8 @@ DEV int hermite_c(const Coef4 k, unsigned ph)
 	const int x = frac_x(ph);
 	int t = wmul(k.x, x) >> 15;
 	t = wmul(wadd(t, k.y), x) >> 15;
-#if A2D_COEF_WORDS == 4
-	t = wmul(wadd(t, k.z), x) >> 15;
-	return wadd(k.w, t);
-#else
 	t = wmul(wadd(t, k.z >> 16), x) >> 15;
 	return wadd((int)(int16_t)(k.z & 0xffff), t);
-#endif
 }
 
 // wtosc_Inter (wtosc.c:28-33) from the coefficient table: cb = coef_base() of the

@@ -651,12 +651,7 @@ void k_win_render(const int *__restrict__ list, int nlist, int vpw, int fa, int 
 
 // ---- with filter12: a workgroup owns its voices for the whole slab -----------------------------
 #define WINF_PITCH 65
-#ifndef WINF_W1
 #define WINF_W1 8	/* (16 for the one-oscillator kernel measured slower: 0.71 against 0.63 ms, 16 384 gliding voices x 64) */
-#endif
-#ifndef WINF_SPEC
-#define WINF_SPEC 1
-#endif
 #define WINF_MAXW(NOSC) ((NOSC) == 1 ? WINF_W1 : 8)	// wavefronts per workgroup, one of which filters (two oscillators: the
 							// kernel needs more than the 128 registers sixteen would leave it)
 
@@ -698,7 +693,7 @@ DEV void winf_filter_t(int *row, int off, int len, int f0v, int df, int qv, int 
 
 DEV void winf_filter(int *row, int off, int len, int f0v, int df, int qv, int qd, int lp, int bp, int hp, int &d1, int &d2)
 {
-	const bool lponly = WINF_SPEC && __all((bp | hp) == 0), rest = WINF_SPEC && __all((df | qd) == 0);
+	const bool lponly = __all((bp | hp) == 0), rest = __all((df | qd) == 0);
 	// (Round 6, tried and dropped: a blocked loop for the case that every lane's window is the whole fragment - 8 or 4 frames
 	// at a time, the next block on its way from the LDS, as k_leaf_oscfiltpan's filt_row - measured SLOWER on one box
 	// against this loop: 16 384 x 64, wtosc-filter12-panmix scripted 0.896 -> 0.948 ms, gliding 0.633 -> 0.686; two

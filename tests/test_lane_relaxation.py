@@ -1,4 +1,4 @@
-"""The arithmetic behind the records kernels' filter window (a2amd_fast.hip: filt_window_j, RECS_JFILT).
+"""The arithmetic behind the records kernels' filter window (a2amd_fast.hip: filt_window_j).
 
 filter12's per-frame step (the reference's filter12.c:97-118, one channel, 32-bit wrapping arithmetic) is a
 recurrence in time: frame s needs d1 and d2 as frame s - 1 left them.  The kernel keeps frame s in lane s and lets

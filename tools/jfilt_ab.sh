@@ -1,5 +1,5 @@
 #!/bin/bash
-# RECS_JFILT (the filter window as a relaxation along the lanes): parity of the record paths, then
+# filt_window_j (the filter window as a relaxation along the lanes): parity of the record paths, then
 # scripted filter voices through the C ABI (kernel times) and the song
 mkdir -p gpurun_out
 {

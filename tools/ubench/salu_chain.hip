@@ -1,6 +1,6 @@
 // salu_chain.hip - what one wavefront that has its SIMD to itself pays per DEPENDENT
-// instruction on the scalar unit (the filter12 recurrence of k_leaf_recs, a2amd_fast.hip
-// filt_window_s), on gfx950: chains of one instruction feeding itself, and the frame of
+// instruction on the scalar unit (the filter12 recurrence of k_leaf_recs as rounds 2-4 ran it:
+// a2amd_fast.hip had that window function until the filter window moved along the lanes), on gfx950: chains of one instruction feeding itself, and the frame of
 // independent ones for the issue rate; wall time from HIP events over 2 M instructions, one
 // wave64 in the launch (s_memtime around scalar-only loops read back nonsense here), in
 // cycles of the 2.4 GHz shader clock.

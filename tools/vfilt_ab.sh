@@ -1,5 +1,5 @@
 #!/bin/bash
-# RECS_VFILT A/B: scripted filter voices through the C ABI (kernel times), the song, variant 3b with the engine in the loop
+# the lane = voice filter of the records kernels, A/B against a variant library built without it (round 4): scripted filter voices through the C ABI (kernel times), the song, variant 3b with the engine in the loop
 V=$PWD/tools/ubench/variants
 for lib in "" $V/liba2amd_novf.so; do
   echo "== lib: ${lib:-this build}"
