@@ -564,7 +564,7 @@ void k_leaf_oscpan(const A2DParams *__restrict__ pp, const int *__restrict__ lis
 				}
 #pragma unroll
 				for(int j = 0; j < 4; ++j) {
-					int sm = hermite_c(ka[j], pa[j]) + hermite_c(kb[j], pb[j]);
+					int sm = inter_coefs(ka[j], pa[j], kb[j], pb[j]);
 					int x = mul64s(sm, amp, 17);
 					x = (lane < nfr[h + j]) ? x : 0;
 					acc0[h + j] = wadd(acc0[h + j], mul64s(x, v0, 24));
@@ -913,7 +913,7 @@ void k_leaf_osc2pan(const A2DParams *__restrict__ pp, const int *__restrict__ li
 			for(int o = 0; o < 2; ++o)
 #pragma unroll
 				for(int j = 0; j < OSC2_FCH; ++j) {
-					const int y = mul64s(hermite_c(ka[o][j], pa[o][j]) + hermite_c(kb[o][j], pb[o][j]), amps[o], 17);
+					const int y = mul64s(inter_coefs(ka[o][j], pa[o][j], kb[o][j], pb[o][j]), amps[o], 17);
 					// the second oscillator adds into the scratch buffer (wrap-around)
 					xs[j] = o ? wadd(xs[j], y) : y;
 				}
@@ -2479,10 +2479,10 @@ DEV void oscfiltpan_body(const A2DParams *__restrict__ pp, const int *__restrict
 #pragma unroll
 				for(int k = 0; k < NV; ++k) {
 					if constexpr(NOSC == 2)	// (the adding oscillator: a wrapping add in the voice's scratch, then in >> 5)
-						x[k] = wadd(mul64s(hermite_c(ka[k], pa[k]) + hermite_c(kb[k], pb[k]), g_amp[k], 17),
-								mul64s(hermite_c(kc[k], pc[k]) + hermite_c(kd[k], pd[k]), g_amp2[k], 17)) >> 5;
+						x[k] = wadd(mul64s(inter_coefs_x(ka[k], pa[k], kb[k], pb[k]), g_amp[k], 17),
+								mul64s(inter_coefs_x(kc[k], pc[k], kd[k], pd[k]), g_amp2[k], 17)) >> 5;
 					else
-					x[k] = mul64s(hermite_c(ka[k], pa[k]) + hermite_c(kb[k], pb[k]), g_amp[k], 17) >> 5;	// (x5: filt_step)
+					x[k] = mul64s(inter_coefs_x(ka[k], pa[k], kb[k], pb[k]), g_amp[k], 17) >> 5;	// (x5: filt_step)
 				}
 				if(n == A2D_FRAG) {
 #pragma unroll
@@ -2653,7 +2653,7 @@ DEV void oscfiltpan_body(const A2DParams *__restrict__ pp, const int *__restrict
 				int xs[FILT_BATCH];
 #pragma unroll
 				for(int k = 0; k < FILT_BATCH; ++k) {
-					int sm = hermite_c(pqa[k], pqph[k]) + hermite_c(pqb[k], pqph2[k]);
+					int sm = inter_coefs_x(pqa[k], pqph[k], pqb[k], pqph2[k]);
 					xs[k] = mul64s(sm, rdl(sv[SV_A], k < pnb ? k : 0), 17);
 				}
 #pragma unroll
@@ -2674,7 +2674,7 @@ DEV void oscfiltpan_body(const A2DParams *__restrict__ pp, const int *__restrict
 					unsigned ph16 = tap_phase(ph, (unsigned)lane * dph);
 					const unsigned ph16b = ph16 + (dph >> 17);
 					const int cb = coef_base(doff);
-					int sm = hermite_c(coef_at(crs, cb, ph16), ph16) + hermite_c(coef_at(crs, cb, ph16b), ph16b);
+					int sm = inter_coefs_x(coef_at(crs, cb, ph16), ph16, coef_at(crs, cb, ph16b), ph16b);
 					x = mul64s(sm, amp, 17);
 				} else {
 					OscS o;
@@ -2712,7 +2712,7 @@ DEV void oscfiltpan_body(const A2DParams *__restrict__ pp, const int *__restrict
 						unsigned ph16 = tap_phase(ph, (unsigned)lane * dph);
 						const unsigned ph16b = ph16 + (dph >> 17);
 						const int cb = coef_base(doff);
-						int sm = hermite_c(coef_at(crs, cb, ph16), ph16) + hermite_c(coef_at(crs, cb, ph16b), ph16b);
+						int sm = inter_coefs_x(coef_at(crs, cb, ph16), ph16, coef_at(crs, cb, ph16b), ph16b);
 						xb = mul64s(sm, amp, 17);
 					} else {
 						OscS o;

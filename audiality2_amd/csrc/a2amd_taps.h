@@ -17,24 +17,34 @@ DEV int rdl(int v, int lane) { return __builtin_amdgcn_readlane(v, lane); }
 // park a wave-uniform value back in lane 'sel' of a per-lane register
 #define WRL(reg, val) reg = me ? (val) : reg
 
-// a2_Hermite (a2_dsp.h:64-74) on four already fetched samples.  The operands of
-// the three products are below 2^20 and 2^15 in magnitude, so the 24 bit
-// multiplier returns the same low 32 bits as the reference's int multiply
-// (including its wrap-around) at full rate.
-DEV int hermite4(int dm, int d0, int d1, int d2, int frac)
+// One Horner step of a2_Hermite (a2_dsp.h:64-74): (v * x wrapped to 32 bits) >> 15 with x = frac << 7,
+// frac = the low byte of the 24:8 phase ph.  With p = v * frac exact, the low 32 bits of p << 7 are
+// p's bits 0..24 moved up, so the reference's result is bits 8..24 of p, sign extended: one
+// full-rate 24 bit multiply and one bit-field extract.  The multiply selects frac out of ph itself
+// (SDWA: byte 0 of the second source, zero extended), so neither x nor frac is ever formed.
+// Holds for |v| < 2^23: the multiplier takes v's low 24 bits, sign extended, and |p| < 2^31 then.
+// Every operand the callers have is inside that: samples are int16, so a2_Hermite's |c| <= 32767,
+// |a| <= (3 * 65535 + 65535) / 2 = 131070, |b| <= 65535 + 32767 + 131070 = 229372, a step's result
+// is a 17 bit field (below 2^16 in magnitude), and the sums fed to the next step stay below
+// 2^16 + 229372 < 2^19.  (Spelled as instructions: left to itself the compiler proves the 24 bit
+// range for one of the three products only, and spells the byte select as a mask of its own.)
+DEV int hermite_step(int v, unsigned ph)
+{
+	int p;
+	asm("v_mul_i32_i24_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_0"
+			: "=v"(p) : "v"(v), "v"(ph));
+	return __builtin_amdgcn_sbfe(p, 8, 17);
+}
+
+// a2_Hermite on four already fetched samples, at the 24:8 phase ph (its low byte counts)
+DEV int hermite4(int dm, int d0, int d1, int d2, unsigned ph)
 {
 	int c = (d1 - dm) >> 1;
 	int a = (3 * (d0 - d1) + d2 - dm) >> 1;
 	int b = dm - d0 + c - a;
-	// The reference multiplies by x = frac << 7 in 32 bit ints (wrap-around and
-	// all) and shifts right by 15.  With p = a * frac exact (|a| < 2^20, frac <
-	// 2^8), the low 32 bits of p << 7 are p's bits 0..24 moved up, so that result
-	// is bits 8..24 of p, sign extended: one full-rate 24 bit multiply and one
-	// bit-field extract, no x.  (Spelled as instructions: left to itself the
-	// compiler proves the 24 bit range for one of the three products only.)
-	a = __builtin_amdgcn_sbfe(fm_mul24(a, frac), 8, 17);
-	a = __builtin_amdgcn_sbfe(fm_mul24(a + b, frac), 8, 17);
-	return d0 + __builtin_amdgcn_sbfe(fm_mul24(a + c, frac), 8, 17);
+	a = hermite_step(a, ph);
+	a = hermite_step(a + b, ph);
+	return d0 + hermite_step(a + c, ph);
 }
 
 // Four consecutive int16 samples as two dwords from a 2-byte aligned address
@@ -46,10 +56,8 @@ struct __attribute__((packed, aligned(2))) Quad16 { uint32_t lo, hi; };
 // or i + 1 (dph16 <= 512 << 8).  Each window is one 8 byte load.
 DEV int inter_quads(const Quad16 qa, const Quad16 qb, unsigned ph, unsigned ph2)
 {
-	int h0 = hermite4((int16_t)(qa.lo & 0xffff), (int)qa.lo >> 16, (int16_t)(qa.hi & 0xffff), (int)qa.hi >> 16,
-			(int)(ph & 0xff));
-	int h1 = hermite4((int16_t)(qb.lo & 0xffff), (int)qb.lo >> 16, (int16_t)(qb.hi & 0xffff), (int)qb.hi >> 16,
-			(int)(ph2 & 0xff));
+	int h0 = hermite4((int16_t)(qa.lo & 0xffff), (int)qa.lo >> 16, (int16_t)(qa.hi & 0xffff), (int)qa.hi >> 16, ph);
+	int h1 = hermite4((int16_t)(qb.lo & 0xffff), (int)qb.lo >> 16, (int16_t)(qb.hi & 0xffff), (int)qb.hi >> 16, ph2);
 	return h0 + h1;
 }
 
@@ -95,8 +103,34 @@ DEV CoefRsrc coef_rsrc(const int *wavecoef)
 // byte offset of the entry of pool sample doff (the table follows the pool: host, a2amd_host.cpp)
 DEV int coef_base(unsigned doff) { return (int)(doff * (4u * A2D_COEF_WORDS)); }
 
-// a2_Hermite's x = frac << 7 from a 24:8 phase, one instruction: the shift takes the low byte
-// of its operand (SDWA) - the compiler spells it as a shift and a mask
+// a2_Hermite from a coefficient entry at the 24:8 phase ph, without its d[i] term: the three steps of
+// hermite_step() (the table is built from int16 samples, so its a, b and c are inside the bounds
+// stated there)
+DEV int hermite_ct(const Coef4 k, unsigned ph)
+{
+	int t = hermite_step(k.x, ph);
+	t = hermite_step(wadd(t, k.y), ph);
+	return hermite_step(wadd(t, k.z >> 16), ph);
+}
+
+// Both taps of wtosc_Inter (wtosc.c:28-33) from their coefficient entries.  The two d[i] - the low
+// halves of the entries' third words - meet in one add that sign-extends both (SDWA).  No gain of its
+// own: it keeps what the compiler made of the per-tap wadd((int16_t)k.z, t) before hermite_step()
+// (wrapping adds are associative, so the sum is the same); with the steps above in the way it
+// extracts one of the halves by itself, one instruction more per pair of taps.  Both operands are
+// vector registers: an entry held wave-uniform would cost a v_mov here.
+DEV int inter_coefs(const Coef4 ka, unsigned pa, const Coef4 kb, unsigned pb)
+{
+	int d;
+	asm("v_add_u32_sdwa %0, sext(%1), sext(%2) dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_0 src1_sel:WORD_0"
+			: "=v"(d) : "v"(ka.z), "v"(kb.z));
+	return wadd(wadd(d, hermite_ct(ka, pa)), hermite_ct(kb, pb));
+}
+
+// The same two taps in the form the filter kernels keep (k_leaf_oscfiltpan, k_leaf_osc2filtpan: both
+// stand at their register limit, and with the steps above their all-settled loops spill 6 and 1
+// registers more): x = frac << 7 formed once per tap - one SDWA shift of the phase's low byte - and the
+// reference's own 32 bit wrap-around products and arithmetic >> 15.
 DEV int frac_x(unsigned ph)
 {
 	int x;
@@ -106,13 +140,18 @@ DEV int frac_x(unsigned ph)
 	return x;
 }
 
-DEV int hermite_c(const Coef4 k, unsigned ph)
+DEV int hermite_cx(const Coef4 k, unsigned ph)
 {
 	const int x = frac_x(ph);
 	int t = wmul(k.x, x) >> 15;
 	t = wmul(wadd(t, k.y), x) >> 15;
 	t = wmul(wadd(t, k.z >> 16), x) >> 15;
 	return wadd((int)(int16_t)(k.z & 0xffff), t);
+}
+
+DEV int inter_coefs_x(const Coef4 ka, unsigned pa, const Coef4 kb, unsigned pb)
+{
+	return hermite_cx(ka, pa) + hermite_cx(kb, pb);
 }
 
 // wtosc_Inter (wtosc.c:28-33) from the coefficient table: cb = coef_base() of the
@@ -125,8 +164,11 @@ DEV Coef4 coef_at(const CoefRsrc rs, int cb, unsigned ph)
 // The 24:8 phase of a tap: (ph + lane * dph) >> 16 for a wave-uniform 64 bit phase ph and
 // ldph = lane * dph (below 2^31: dph <= A2D_MAXPHINC << 16 on the settled paths).  Split at
 // bit 16 the sum needs no 64 bit vector arithmetic: the halves of ph stay scalar, the lane
-// part is two adds and a shift of the fast issue class (a 64 bit multiply-add and a funnel
-// shift otherwise).
+// part is two adds (a 64 bit multiply-add and a funnel shift otherwise).  lo + ldph is below
+// 2^31 + 2^16, so the shifted value is the upper 16 bit word of that sum, and the compiler folds
+// the shift into the second add (v_add_u32_sdwa, WORD_1 of the sum, hi from its scalar register):
+// left in C, because spelled as instructions hi would need one register class for every caller
+// (it is a scalar register wherever ph is wave-uniform, a vector register elsewhere).
 DEV unsigned tap_phase(uint64_t ph, unsigned ldph)
 {
 	const unsigned lo = (unsigned)ph & 0xffffu, hi = (unsigned)(ph >> 16);

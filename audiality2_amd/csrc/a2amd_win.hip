@@ -383,7 +383,7 @@ DEV int win_oscs_finish(const EA &E, const WinTaps<NOSC> &T, int fl, bool in)
 		const int b = WE_OSC + 6 * o;
 		if(m == WM_TAPS) {
 			if(in) {
-				const int h = hermite_c(T.k1[o], T.t1[o]) + hermite_c(T.k2[o], T.t2[o]);
+				const int h = inter_coefs(T.k1[o], T.t1[o], T.k2[o], T.t2[o]);
 				// (an amplitude at rest - most windows - is one scalar for the window)
 				const int ak = T.da[o] ? wadd(T.ak[o], wmul(T.da[o], fl)) : T.ak[o];
 				x = wadd(x, mul64s(h, ak, 17));
@@ -466,7 +466,7 @@ DEV void win_finish_pan(const EA &E, const WinTaps<NOSC> &T, int lane, int &a0, 
 		int x = 0;
 #pragma unroll
 		for(int o = 0; o < NOSC; ++o)
-			x = wadd(x, mul64s(hermite_c(T.k1[o], T.t1[o]) + hermite_c(T.k2[o], T.t2[o]), T.ak[o], 17));
+			x = wadd(x, mul64s(inter_coefs(T.k1[o], T.t1[o], T.k2[o], T.t2[o]), T.ak[o], 17));
 		if(PLAIN != 1)
 			x = (unsigned)(lane - WH_OFF(T.head)) < (unsigned)WH_LEN(T.head) ? x : 0;	// (lanes outside a cut window)
 		a0 = wadd(a0, mul64s(x, E(WE_VOL), 24));	// (WE_VOL / WE_PAN: the two gains, WH_PLAIN)
@@ -910,7 +910,7 @@ void k_win_render_f(const int *__restrict__ list, int nlist, int vpg, int fa, in
 							int x = 0;
 #pragma unroll
 							for(int o = 0; o < NOSC; ++o)
-								x = wadd(x, mul64s(hermite_c(T0.k1[o], T0.t1[o]) + hermite_c(T0.k2[o], T0.t2[o]), T0.ak[o], 17));
+								x = wadd(x, mul64s(inter_coefs(T0.k1[o], T0.t1[o], T0.k2[o], T0.t2[o]), T0.ak[o], 17));
 							// (PL == 2, a cut window: the lanes outside it write the row's padding cell - WINF_PITCH is 65 -
 							// instead of a store under an exec mask)
 							const int col = PL == 1 || (unsigned)(lane - WH_OFF(T0.head)) < (unsigned)WH_LEN(T0.head) ? lane : A2D_FRAG;

@@ -1,6 +1,8 @@
 // valu_rates.hip - issue rate of the integer VALU instructions the leaf kernels
-// are made of, on gfx950: one wave64 per SIMD (and 4 per SIMD), a long unrolled
-// chain of independent copies of one instruction, cycles from s_memtime.
+// are made of, on gfx950: 1, 4 and 8 wave64 per SIMD (profiles/r02_valu_rates.txt was made with
+// 4 and 8 only), a long unrolled chain of independent copies of one instruction, cycles from
+// s_memtime.  The SDWA forms of the wavetable taps (a2amd_taps.h) stand beside what they replace:
+// mul24_sdwa_b0 / lshl_sdwa_b0 / add_sdwa_w1, and the dependent pairs mul24sdwa+bfe against mul_lo+ashr.
 //   hipcc --offload-arch=gfx950 -O3 -o valu_rates valu_rates.hip && ./valu_rates
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -66,6 +68,11 @@ KERNEL(k_and_or, , OP8("v_and_or_b32 %0, %0, %1, %2"))
 KERNEL(k_sub_ashr, , OP8("v_sub_u32 %0, %0, %1\n v_ashrrev_i32 %0, 1, %0"))
 KERNEL(k_add_sdwa, , OP8("v_add_u32_sdwa %0, %0, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_1 src1_sel:DWORD"))
 KERNEL(k_ashr_sdwa, , OP8("v_mov_b32_sdwa %0, sext(%0) dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:WORD_0"))
+KERNEL(k_mul24_sdwa, , OP8("v_mul_i32_i24_sdwa %0, %0, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_0"))
+KERNEL(k_add_sdwa_w1, , OP8("v_add_u32_sdwa %0, %1, %0 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:WORD_1"))
+KERNEL(k_lshl_sdwa, , OP8("v_lshlrev_b32_sdwa %0, %1, %0 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_0"))
+KERNEL(k_mix_mul24_sdwa_bfe, , OP8("v_mul_i32_i24_sdwa %0, %0, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_0\n v_bfe_i32 %0, %0, 8, 17"))
+KERNEL(k_mix_mul_lo_ashr, , OP8("v_mul_lo_u32 %0, %0, %1\n v_ashrrev_i32 %0, 15, %0"))
 // mixes: 1 add + 1 mul24 ; 2 add + 1 mul24 ; add + bfe ; add + mad_i64
 KERNEL(k_mix_add_mul, , OP8("v_add_u32 %0, %0, %1\n v_mul_i32_i24 %0, %0, %2"))
 KERNEL(k_mix_2add_mul, , OP8("v_add_u32 %0, %0, %1\n v_add_u32 %0, %0, %2\n v_mul_i32_i24 %0, %0, %2"))
@@ -113,7 +120,7 @@ template<class K> void run(const char *name, K k, int waves_per_simd)
 
 int main()
 {
-	for(int w : {4, 8}) {
+	for(int w : {1, 4, 8}) {
 		run("add_u32", k_add, w); run("mul_lo_u32", k_mul_lo, w); run("mul_hi_i32", k_mul_hi, w);
 		run("mul_i32_i24", k_mul24, w); run("mul_hi_i24", k_mulhi24, w); run("mad_i32_i24", k_mad24, w);
 		run("mad_i64_i32", k_mad64, w); run("bfe_i32", k_bfe, w); run("alignbit", k_alignbit, w);
@@ -125,6 +132,8 @@ int main()
 		run("add_co", k_addco, w); run("cndmask_sgpr", k_cnd3, w); run("mul_u32_u24", k_mulu24, w); run("bfe_u32", k_bfeu, w);
 		run("bfi", k_bfi, w); run("perm", k_perm, w); run("and_or", k_and_or, w); run("sub+ashr(2)", k_sub_ashr, w);
 		run("add_sdwa", k_add_sdwa, w); run("mov_sdwa_sext", k_ashr_sdwa, w);
+		run("mul24_sdwa_b0", k_mul24_sdwa, w); run("add_sdwa_w1", k_add_sdwa_w1, w); run("lshl_sdwa_b0", k_lshl_sdwa, w);
+		run("mul24sdwa+bfe(2)", k_mix_mul24_sdwa_bfe, w); run("mul_lo+ashr(2)", k_mix_mul_lo_ashr, w);
 		run("add+mul24(2)", k_mix_add_mul, w); run("2add+mul24(3)", k_mix_2add_mul, w); run("add+bfe(2)", k_mix_add_bfe, w);
 		run("mul24+bfe(2)", k_mix_mul_bfe, w);
 		printf("\n");
