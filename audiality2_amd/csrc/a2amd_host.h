@@ -209,10 +209,31 @@ struct HVoice {
 	long long dynf2_run = -1;	// ... in which it was put on the records kernels' list of 2 x wtosc-filter12-panmix voices
 };
 
-struct DepthRange { int fast_first = 0, fast_count = 0, fbd_first = 0, fbd_count = 0, gen_first = 0, gen_count = 0,
-		dyn_first = 0, dyn_count = 0; };
 enum { CLS_GENERIC = 0, CLS_OSCPAN, CLS_OSCFILTPAN, CLS_BUSDRIVER, CLS_BUSGENERIC, CLS_OSC2PAN, CLS_FMPAN, CLS_FBDCHAIN,
-	CLS_OSC2FILTPAN };
+	CLS_OSC2FILTPAN, CLS_N };	// (cls_lists below has a row per class, in this order)
+
+// ---- the launch lists: one table of ranges ----
+// a2amd_ctx::list_all (on the device: d_list), rebuilt when the voice tree changes, holds every listed voice by launch class:
+//   [ wtosc-panmix | 2 x wtosc-panmix | wtosc-filter12-panmix | fm-panmix | general leaves | 2 x wtosc-filter12-panmix |
+//     per nesting depth, 0 first: driver chains | delay chains | general bus voices ]
+// a2amd_ctx::leaf[LEAF_*] are the leaf segments IN LIST ORDER (2 x wtosc-filter12-panmix was appended behind the general
+// leaves in round 6 and stays there: the order shows in d_list offsets and in the device VM's lists), depth_ranges[d] the
+// rest.  The wavetable and general segments are sorted by output bus, so that a wavefront can sum several voices before
+// it touches the bus; fm-panmix by unit kind (fm1..fm4r: fm_kind_count, one launch each), then by bus.
+// The quiet kernels skip a voice whose runs[] entry is non-zero; those voices are this batch's exceptions, shipped in the
+// blob (d_dyn), laid out the same way:
+//   [ wtosc-panmix | 2 x wtosc-panmix | wtosc-filter12-panmix | 2 x wtosc-filter12-panmix | the general kernel's |
+//     per depth: bus owners with records ]
+// a2amd_ctx::dyn[DYN_*] (the first four: the records / window kernels' lists) and depth_ranges[d].dyn are OFFSETS into
+// d_dyn, which moves when the blob grows (a2amd_vm.cpp).
+struct ListRange { int first = 0, count = 0; };
+enum { LEAF_OSCPAN = 0, LEAF_OSC2PAN, LEAF_OSCFILTPAN, LEAF_FMPAN, LEAF_GENERIC, LEAF_OSC2FILTPAN, LEAF_N };
+enum { DYN_OSC1 = 0, DYN_OSC2, DYN_FILT, DYN_FILT2, DYN_REST, DYN_N };
+struct DepthRange { ListRange driver, fbd, generic, dyn; };
+// a launch class's leaf segment and, where k_leaf_recs knows the class, its exception list (-1: a bus owner), in CLS_* order
+static const struct { int8_t leaf, dyn; } cls_lists[CLS_N] = {
+	{ LEAF_GENERIC, DYN_REST }, { LEAF_OSCPAN, DYN_OSC1 }, { LEAF_OSCFILTPAN, DYN_FILT }, { -1, -1 }, { -1, -1 },
+	{ LEAF_OSC2PAN, DYN_OSC2 }, { LEAF_FMPAN, DYN_REST }, { -1, -1 }, { LEAF_OSC2FILTPAN, DYN_FILT2 } };
 
 // host side of an xinsert client slot
 struct XioSlot {
@@ -398,11 +419,7 @@ struct a2amd_ctx {
 	std::vector<int> with_recs, prev_with_recs;	// voices carrying records this / last batch
 	std::vector<int> dirty_voices;		// voice mirror entries to re-upload
 	long long serial_base = 0;		// fragments rendered before this batch
-	int n_leaf_dyn = 0, static_len = 0;
-	int n_dyn_osc1 = 0, n_dyn_osc2 = 0, n_dyn_filt = 0;	// ... of n_leaf_dyn, first in the list: k_leaf_recs renders them
 	bool o2f_quiet = true;			// this batch: the class's voices without records go to k_leaf_osc2filtpan (upload() decides)
-	int n_dyn_filt2 = 0, n_dyn_rest = 0;	// ... 2 x wtosc-filter12-panmix (round 6: a quiet kernel of its own) / the general kernel's
-	int n_o2f_leaf = 0;			// 2 x wtosc-filter12-panmix leaves (list_all, behind the general leaves)
 	int n_started_live = 0;			// voices the engine is walking
 	int walked_started = 0;			// ... of which it has walked this many in the open fragment
 	int n_noise = 0, n_cutoff_ramps = 0;
@@ -459,12 +476,12 @@ struct a2amd_ctx {
 	std::vector<uint32_t> mudesc;
 	std::vector<A2DWave> mwaves;
 	bool voices_dirty = true, udesc_dirty = true, waves_dirty = true, lists_dirty = true, ptab_dirty = true;
-	std::vector<int> list_all;		// leaf list followed by per-depth lists
-	int n_leaf = 0;
-	int n_fast_leaf = 0, n_osc2_leaf = 0, n_filt_leaf = 0;	// list_all = [wtosc-panmix | 2 x wtosc-panmix | wtosc-filter12-panmix | fm-panmix | general leaves | per depth ...]
-	int n_fm_leaf = 0, fm_kind_count[8] = { 0 };		// fm-panmix: grouped by unit kind (fm1..fm4r), one launch each
-	int n_list_pads = 0;
+	// the launch lists (ListRange, above)
+	std::vector<int> list_all;
+	ListRange leaf[LEAF_N];			// list_all's leaf segments
+	int fm_kind_count[8] = { 0 };		// ... and leaf[LEAF_FMPAN]'s voices by unit kind
 	std::vector<DepthRange> depth_ranges;	// index = depth
+	ListRange dyn[DYN_N];			// this batch's leaf exceptions in d_dyn
 	bool hosttiming = false;		// A2AMD_HOSTTIMING
 	int no_fast = 0;			// A2AMD_NO_FAST bit mask: 1 wtosc-panmix, 2 wtosc-filter12-panmix, 4 driver chains -> general kernel (debugging / A-B tests)
 	// Switches the tests vary from context to context inside one process: read in a2amd_open(), never through a

@@ -175,7 +175,7 @@ int a2amd_render(a2amd_ctx *c, unsigned phases, int32_t *const *out, unsigned ca
 					c->root_clean = true;
 				if(kphases & A2AMD_RENDER_ROOT) {
 					c->stats.fragments += c->nfrags;
-					c->stats.voice_fragments += (uint64_t)c->nfrags * (c->list_all.size() - c->n_list_pads);
+					c->stats.voice_fragments += (uint64_t)c->nfrags * c->list_all.size();
 				}
 				return 0;
 			}
@@ -379,7 +379,7 @@ int a2amd_replay(a2amd_ctx *c, unsigned steps)
 			c->others_clean = c->root_clean = c->consume_ok;
 			steps -= GRAPH_STEPS;
 			c->stats.fragments += (uint64_t)c->nfrags * GRAPH_STEPS;
-			c->stats.voice_fragments += (uint64_t)c->nfrags * (c->list_all.size() - c->n_list_pads) * GRAPH_STEPS;
+			c->stats.voice_fragments += (uint64_t)c->nfrags * c->list_all.size() * GRAPH_STEPS;
 		} else if(graphs) {
 			if(int r = ensure_clean(c))
 				return r;
@@ -387,7 +387,7 @@ int a2amd_replay(a2amd_ctx *c, unsigned steps)
 			c->others_clean = c->root_clean = c->consume_ok;
 			--steps;
 			c->stats.fragments += c->nfrags;
-			c->stats.voice_fragments += (uint64_t)c->nfrags * (c->list_all.size() - c->n_list_pads);
+			c->stats.voice_fragments += (uint64_t)c->nfrags * c->list_all.size();
 		} else {
 			if(c->profiling) {
 				if(c->ev_used + 3 > c->ev_pool.size())

@@ -314,6 +314,14 @@ bool is_fbdchain(const a2amd_ctx *c, const HVoice &v)
 	return true;
 }
 
+// append a launch list to list_all / to the batch's exceptions; the range it takes there
+static ListRange append_range(std::vector<int> &to, const std::vector<int> &l)
+{
+	const ListRange r = { (int)to.size(), (int)l.size() };
+	to.insert(to.end(), l.begin(), l.end());
+	return r;
+}
+
 int upload(a2amd_ctx *c)
 {
 	// (voices the device VM took over during this batch: the host's interpreter carries them to its
@@ -629,17 +637,11 @@ int upload(a2amd_ctx *c)
 		dbg_counters()[4] += (double)c->with_recs.size();
 	}
 
-	// Launch lists.  Static part, rebuilt when the voice tree changes: every
-	// listed voice by class -
-	//   leaves: [wtosc-panmix | wtosc-filter12-panmix | general]  (each sorted by
-	//           output bus so a wavefront can sum several voices before touching it)
-	//   voices with an inline unit, per nesting depth: [driver chain | general]
-	// The fast kernels skip a voice whose runs[] entry is non-zero; those voices
-	// form the dynamic part (this batch's exceptions) and go to the general kernel.
+	// Launch lists (a2amd_host.h: ListRange).  Static part, rebuilt when the voice tree changes: every listed voice by class.
 	if(c->lists_dirty) {
 		static const bool cls_check = getenv("A2AMD_CLS_CHECK") != nullptr;
 		bool owners_ok = !getenv("A2AMD_NO_SELFCLEAN"), root_driver = false;
-		std::vector<int> fast_leaf, osc2_leaf, filt_leaf, fm_leaf, gen_leaf, o2f_leaf;
+		std::vector<int> leaf[LEAF_N];
 		std::map<int, std::pair<std::vector<int>, std::vector<int>>> bydepth;
 		std::map<int, std::vector<int>> fbd_bydepth;
 		int maxdepth = -1;
@@ -680,9 +682,7 @@ int upload(a2amd_ctx *c)
 							!(c->no_fast & 16) && is_fmpan_chain(c, v) ? CLS_FMPAN : CLS_GENERIC;
 				if(v.out_off == 0)
 					owners_ok = false;	// adds straight into the master bus
-				(v.cls == CLS_OSCPAN ? fast_leaf : v.cls == CLS_OSC2PAN ? osc2_leaf :
-				 v.cls == CLS_OSCFILTPAN ? filt_leaf : v.cls == CLS_FMPAN ? fm_leaf :
-				 v.cls == CLS_OSC2FILTPAN ? o2f_leaf : gen_leaf).push_back((int)vi);
+				leaf[cls_lists[v.cls].leaf].push_back((int)vi);
 			}
 			if(cls_check && !v.cls_stale && was_cls >= 0 && was_cls != v.cls)
 				return c->fail(A2AMD_ESTATE, "voice %zu: remembered launch class %d, classified %d (a change nobody reported)",
@@ -693,53 +693,28 @@ int upload(a2amd_ctx *c)
 		// (slots follow the order of birth, births the walk: a class is usually grouped by bus already - one pass
 		// says so, where a sort of 16 384 voices by a key two loads away was most of a rebuild; a scene with a note
 		// born or ended in most batches rebuilds in most batches)
-		auto sort_by_bus = [&](std::vector<int> &l) {
-			if(!std::is_sorted(l.begin(), l.end(), by_bus))
-				std::stable_sort(l.begin(), l.end(), by_bus);
-		};
-		sort_by_bus(fast_leaf);
-		sort_by_bus(gen_leaf);
-		sort_by_bus(filt_leaf);
-		sort_by_bus(osc2_leaf);
-		c->list_all = fast_leaf;
-		c->n_fast_leaf = (int)fast_leaf.size();
-		c->list_all.insert(c->list_all.end(), osc2_leaf.begin(), osc2_leaf.end());
-		c->n_osc2_leaf = (int)osc2_leaf.size();
-		c->list_all.insert(c->list_all.end(), filt_leaf.begin(), filt_leaf.end());
-		c->n_filt_leaf = (int)filt_leaf.size();
-		{
-			// fm voices, grouped by unit kind: one launch per kind present
-			std::stable_sort(fm_leaf.begin(), fm_leaf.end(), [&](int a, int b) {
-				const int ka = c->units[c->voices[a].unit[0]].kind, kb = c->units[c->voices[b].unit[0]].kind;
-				return ka != kb ? ka < kb : c->voices[a].out_off < c->voices[b].out_off;
-			});
-			for(int k = 0; k < 8; ++k)
-				c->fm_kind_count[k] = 0;
-			for(int vi : fm_leaf)
-				++c->fm_kind_count[c->units[c->voices[vi].unit[0]].kind - A2AMD_FM1];
-			c->list_all.insert(c->list_all.end(), fm_leaf.begin(), fm_leaf.end());
-			c->n_fm_leaf = (int)fm_leaf.size();
-		}
-		c->list_all.insert(c->list_all.end(), gen_leaf.begin(), gen_leaf.end());
-		c->n_leaf = (int)gen_leaf.size();
-		sort_by_bus(o2f_leaf);
-		c->list_all.insert(c->list_all.end(), o2f_leaf.begin(), o2f_leaf.end());
-		c->n_o2f_leaf = (int)o2f_leaf.size();
+		for(int k = 0; k < LEAF_N; ++k)
+			if(k != LEAF_FMPAN && !std::is_sorted(leaf[k].begin(), leaf[k].end(), by_bus))
+				std::stable_sort(leaf[k].begin(), leaf[k].end(), by_bus);
+		// fm voices, grouped by unit kind: one launch per kind present
+		std::stable_sort(leaf[LEAF_FMPAN].begin(), leaf[LEAF_FMPAN].end(), [&](int a, int b) {
+			const int ka = c->units[c->voices[a].unit[0]].kind, kb = c->units[c->voices[b].unit[0]].kind;
+			return ka != kb ? ka < kb : c->voices[a].out_off < c->voices[b].out_off;
+		});
+		for(int k = 0; k < 8; ++k)
+			c->fm_kind_count[k] = 0;
+		for(int vi : leaf[LEAF_FMPAN])
+			++c->fm_kind_count[c->units[c->voices[vi].unit[0]].kind - A2AMD_FM1];
+		c->list_all.clear();
+		for(int k = 0; k < LEAF_N; ++k)
+			c->leaf[k] = append_range(c->list_all, leaf[k]);
 		c->depth_ranges.assign(maxdepth + 1, DepthRange());
 		for(int d = 0; d <= maxdepth; ++d) {
-			auto &l = bydepth[d];
 			DepthRange &r = c->depth_ranges[d];
-			r.fast_first = (int)c->list_all.size();
-			r.fast_count = (int)l.first.size();
-			c->list_all.insert(c->list_all.end(), l.first.begin(), l.first.end());
-			r.fbd_first = (int)c->list_all.size();
-			r.fbd_count = (int)fbd_bydepth[d].size();
-			c->list_all.insert(c->list_all.end(), fbd_bydepth[d].begin(), fbd_bydepth[d].end());
-			r.gen_first = (int)c->list_all.size();
-			r.gen_count = (int)l.second.size();
-			c->list_all.insert(c->list_all.end(), l.second.begin(), l.second.end());
+			r.driver = append_range(c->list_all, bydepth[d].first);
+			r.fbd = append_range(c->list_all, fbd_bydepth[d]);
+			r.generic = append_range(c->list_all, bydepth[d].second);
 		}
-		c->static_len = (int)c->list_all.size();
 		if(int r = grow(c, c->d_list, c->list_all.size() + 64, 1, false)) return r;
 		if(!c->list_all.empty())
 			HIPCHK(c, hipMemcpyAsync(c->d_list.d, c->list_all.data(), c->list_all.size() * sizeof(int),
@@ -754,19 +729,31 @@ int upload(a2amd_ctx *c)
 	std::vector<int> dyn_all;
 	{
 		// this batch's exceptions (shipped in the blob)
-		std::vector<int> dyn_leaf;
+		// Voices of the wtosc[+wtosc]->panmix classes whose records are what
+		// k_leaf_recs executes (windows, writes, births, deaths; oscillators on
+		// mip-mapped waves throughout the batch) go first, by class; the rest -
+		// filter voices, a wave of another kind somewhere in the batch - to the
+		// general kernel.
+		std::vector<int> dyn[DYN_N];
 		std::vector<std::vector<int>> dyn_bus(c->depth_ranges.size());
+		const bool no_recs_kernel = (c->no_fast & 64) != 0;
 		static const bool dump = getenv("A2AMD_VM_DUMP") != nullptr;	// (debugging aid: the records of a batch, host-made ...)
 		for(int vi : c->with_recs) {
-			const HVoice &v = c->voices[vi];
+			HVoice &v = c->voices[vi];
 			if(dump)
 				for(const A2DRec &r : v.recs)
 					fprintf(stderr, "REC %lld v%d f%u op%u u%u r%u val %d dur %u start %u\n", c->serial_base, vi,
 							A2D_RFRAG(r.head), A2D_ROP(r.head), A2D_RUNIT(r.head), A2D_RREG(r.head), r.value, r.dur, r.start);
 			// (fm-panmix voices execute their own records in k_leaf_fmpan)
-			if(v.cls == CLS_OSCPAN || v.cls == CLS_OSCFILTPAN || v.cls == CLS_OSC2PAN || v.cls == CLS_OSC2FILTPAN)
-				dyn_leaf.push_back(vi);
-			else if((v.cls == CLS_BUSDRIVER || v.cls == CLS_FBDCHAIN) && v.depth < (int)dyn_bus.size()) {
+			if(v.cls == CLS_OSCPAN || v.cls == CLS_OSCFILTPAN || v.cls == CLS_OSC2PAN || v.cls == CLS_OSC2FILTPAN) {
+				// (close_fragment's R_NOP is the one other record k_leaf_recs takes - as nothing)
+				const bool ok = !no_recs_kernel && !v.mode_mix && !v.fancy_recs;
+				// (on a list already, whichever: a voice the general kernel takes - DYN_REST - must not be put on DYN_FILT2 as
+				// well by the small-scene rule below and rendered twice)
+				if(v.cls == CLS_OSC2FILTPAN)
+					v.dynf2_run = c->serial_base;
+				dyn[ok ? cls_lists[v.cls].dyn : DYN_REST].push_back(vi);
+			} else if((v.cls == CLS_BUSDRIVER || v.cls == CLS_FBDCHAIN) && v.depth < (int)dyn_bus.size()) {
 				dyn_bus[v.depth].push_back(vi);
 				static const int trace = getenv("A2AMD_HOSTTIMING") ? atoi(getenv("A2AMD_HOSTTIMING")) : 0;
 				if(trace >= 3 && !v.recs.empty())
@@ -774,24 +761,6 @@ int upload(a2amd_ctx *c)
 							vi, v.depth, v.cls, v.recs.size(), A2D_RFRAG(v.recs[0].head), A2D_ROP(v.recs[0].head),
 							A2D_RUNIT(v.recs[0].head), A2D_RREG(v.recs[0].head), v.recs[0].value);
 			}
-		}
-		// Voices of the wtosc[+wtosc]->panmix classes whose records are what
-		// k_leaf_recs executes (windows, writes, births, deaths; oscillators on
-		// mip-mapped waves throughout the batch) go first, by class; the rest -
-		// filter voices, a wave of another kind somewhere in the batch - to the
-		// general kernel.
-		std::vector<int> dyn_o1, dyn_o2, dyn_f1, dyn_f2, dyn_rest;
-		const bool no_recs_kernel = (c->no_fast & 64) != 0;
-		for(int vi : dyn_leaf) {
-			HVoice &v = c->voices[vi];
-			// (close_fragment's R_NOP is the one other record k_leaf_recs takes - as nothing)
-			const bool ok = !no_recs_kernel && !v.mode_mix && !v.fancy_recs;
-			// (on a list already, whichever: a voice the general kernel takes - dyn_rest - must not be put on dyn_f2 as
-			// well by the small-scene rule below and rendered twice)
-			if(v.cls == CLS_OSC2FILTPAN)
-				v.dynf2_run = c->serial_base;
-			(!ok ? dyn_rest : v.cls == CLS_OSCPAN ? dyn_o1 : v.cls == CLS_OSC2PAN ? dyn_o2 :
-			 v.cls == CLS_OSCFILTPAN ? dyn_f1 : dyn_f2).push_back(vi);
 		}
 		// Round 6: 2 x wtosc-filter12-panmix has a quiet kernel of its own (k_leaf_osc2filtpan) and rounds 2-5's "the records
 		// kernels render every voice of the class" is over: like the other three classes, a voice is the quiet kernel's
@@ -804,7 +773,7 @@ int upload(a2amd_ctx *c)
 			if(v.dynf2_run == c->serial_base || v.cls != CLS_OSC2FILTPAN || !(v.live || v.dying) || v.vm < 0)
 				continue;
 			v.dynf2_run = c->serial_base;
-			dyn_f2.push_back(vi);
+			dyn[DYN_FILT2].push_back(vi);
 		}
 		// ... but not in a small scene.  A launch of k_leaf_osc2filtpan takes as long as its filter wavefront's chain
 		// through the batch whatever its voice count - and on the context's one stream it runs BEHIND the records kernel,
@@ -812,44 +781,30 @@ int upload(a2amd_ctx *c)
 		// (measured: the 60-voice song, 500 s, 2.94 s in round 5 -> 3.53 s with the quiet kernel for its handful of notes,
 		// profiles/r06_song_timing.jsonl).  Below A2AMD_O2F_MIN voices of the class (default 512) every voice of it is the
 		// records / window kernels', as in rounds 2 - 5.
-		c->o2f_quiet = c->n_o2f_leaf >= c->o2f_min;
-		if(!c->o2f_quiet && c->n_o2f_leaf) {
-			const int at = c->n_fast_leaf + c->n_osc2_leaf + c->n_filt_leaf + c->n_fm_leaf + c->n_leaf;
-			for(int k = 0; k < c->n_o2f_leaf; ++k) {
-				const int vi = c->list_all[at + k];
+		const ListRange o2f = c->leaf[LEAF_OSC2FILTPAN];
+		c->o2f_quiet = o2f.count >= c->o2f_min;
+		if(!c->o2f_quiet)
+			for(int k = 0; k < o2f.count; ++k) {
+				const int vi = c->list_all[o2f.first + k];
 				HVoice &v = c->voices[vi];
 				if(v.dynf2_run == c->serial_base || v.mode_mix)
 					continue;
 				v.dynf2_run = c->serial_base;
-				dyn_f2.push_back(vi);
+				dyn[DYN_FILT2].push_back(vi);
 			}
-		}
 		// (the walk order usually has them grouped by bus already)
 		auto by_bus_dyn = [&](int a, int b) { return c->voices[a].out_off < c->voices[b].out_off; };
-		for(std::vector<int> *l : { &dyn_o1, &dyn_o2, &dyn_f1, &dyn_f2, &dyn_rest })
-			if(!std::is_sorted(l->begin(), l->end(), by_bus_dyn))
-				std::stable_sort(l->begin(), l->end(), by_bus_dyn);
-		std::vector<int> dyn = dyn_o1;
-		dyn.insert(dyn.end(), dyn_o2.begin(), dyn_o2.end());
-		dyn.insert(dyn.end(), dyn_f1.begin(), dyn_f1.end());
-		dyn.insert(dyn.end(), dyn_f2.begin(), dyn_f2.end());
-		dyn.insert(dyn.end(), dyn_rest.begin(), dyn_rest.end());
-		c->n_dyn_osc1 = (int)dyn_o1.size();
-		c->n_dyn_osc2 = (int)dyn_o2.size();
-		c->n_dyn_filt = (int)dyn_f1.size();
-		c->n_dyn_filt2 = (int)dyn_f2.size();
-		c->n_dyn_rest = (int)dyn_rest.size();
-		c->n_leaf_dyn = (int)dyn.size();	// (with the device VM's voices of the fourth class, which dyn_leaf does not hold)
-		for(size_t d = 0; d < dyn_bus.size(); ++d) {
-			c->depth_ranges[d].dyn_first = (int)dyn.size();
-			c->depth_ranges[d].dyn_count = (int)dyn_bus[d].size();
-			dyn.insert(dyn.end(), dyn_bus[d].begin(), dyn_bus[d].end());
+		for(int k = 0; k < DYN_N; ++k) {
+			if(!std::is_sorted(dyn[k].begin(), dyn[k].end(), by_bus_dyn))
+				std::stable_sort(dyn[k].begin(), dyn[k].end(), by_bus_dyn);
+			c->dyn[k] = append_range(dyn_all, dyn[k]);
 		}
-		dyn_all.swap(dyn);
 		c->consume_ok = c->owners_all_driver;
-		for(const std::vector<int> &d : dyn_bus)
-			if(!d.empty())
+		for(size_t d = 0; d < dyn_bus.size(); ++d) {
+			c->depth_ranges[d].dyn = append_range(dyn_all, dyn_bus[d]);
+			if(!dyn_bus[d].empty())
 				c->consume_ok = false;	// a bus owner carries records: the general kernel renders it
+		}
 	}
 
 	A2DParams p;
@@ -966,46 +921,36 @@ void pick_fast_shape(int n, int nfrags, int *vpw, int *ysplit, int ymax = 32)
 	*ysplit = y;
 }
 
-int pick_fast_vpw(int n)
-{
-	// enough wavefronts to fill 256 CUs x 4 SIMDs several times over, then
-	// more voices per wavefront (fewer, fatter bus updates)
-	if(getenv("A2AMD_VPW"))
-		return std::min(std::max(atoi(getenv("A2AMD_VPW")), 1), 64);
-	int v = (n + 4095) / 4096;
-	return std::min(std::max(v, 1), 64);
-}
-
 int launch_depth(a2amd_ctx *c, int d, int consume, A2DCommitSet *pend)	// consume: 1 zero what is read, 2 root stores the master bus
 {
 	const DepthRange &r = c->depth_ranges[d];
-	if(r.fast_count) {
+	if(r.driver.count) {
 		// (state commits the time-sliced leaf kernels left behind ride along)
 		// (the root, a plain driver chain that stores the master bus: into the host's buffer where asked)
 		// (... and only if nothing else adds into the master bus at depth 0: no voice with records there this
 		// batch, no leaf voice mixing straight into it - owners_all_driver says so for the static lists)
-		const bool direct = d == 0 && (consume & 2) && c->master_dst && r.fast_count == 1 && !r.gen_count && !r.fbd_count &&
-				!r.dyn_count && c->owners_all_driver && !c->capture.on;	// (a capture reads the bus memory)
+		const bool direct = d == 0 && (consume & 2) && c->master_dst && r.driver.count == 1 && !r.generic.count && !r.fbd.count &&
+				!r.dyn.count && c->owners_all_driver && !c->capture.on;	// (a capture reads the bus memory)
 		if(direct)
 			c->master_direct = true;
-		if(a2d_launch_bus_driver(c->d_params, c->d_list.d + r.fast_first, r.fast_count, c->nfrags, consume,
+		if(a2d_launch_bus_driver(c->d_params, c->d_list.d + r.driver.first, r.driver.count, c->nfrags, consume,
 				pend, c->stream, direct ? c->master_dst : nullptr))
 			return c->fail(A2AMD_EHIP, "bus driver launch failed: %s", hipGetErrorString(hipGetLastError()));
 		pend->n = 0;
 		++c->stats.launches;
 	}
-	if(r.fbd_count) {
-		if(a2d_launch_bus_fbdchain(c->d_params, c->d_list.d + r.fbd_first, r.fbd_count, consume & 1, c->stream))
+	if(r.fbd.count) {
+		if(a2d_launch_bus_fbdchain(c->d_params, c->d_list.d + r.fbd.first, r.fbd.count, consume & 1, c->stream))
 			return c->fail(A2AMD_EHIP, "delay chain launch failed: %s", hipGetErrorString(hipGetLastError()));
 		++c->stats.launches;
 	}
-	if(r.gen_count) {
-		if(a2d_launch_voices(c->d_params, c->d_list.d + r.gen_first, r.gen_count, 1, c->stream))
+	if(r.generic.count) {
+		if(a2d_launch_voices(c->d_params, c->d_list.d + r.generic.first, r.generic.count, 1, c->stream))
 			return c->fail(A2AMD_EHIP, "bus launch failed: %s", hipGetErrorString(hipGetLastError()));
 		++c->stats.launches;
 	}
-	if(r.dyn_count) {
-		if(a2d_launch_voices(c->d_params, c->d_dyn + r.dyn_first, r.dyn_count, 1, c->stream))
+	if(r.dyn.count) {
+		if(a2d_launch_voices(c->d_params, c->d_dyn + r.dyn.first, r.dyn.count, 1, c->stream))
 			return c->fail(A2AMD_EHIP, "bus launch failed: %s", hipGetErrorString(hipGetLastError()));
 		++c->stats.launches;
 	}
@@ -1133,14 +1078,13 @@ bool depth_has_mutes(const a2amd_ctx *c, int d)
 	return false;
 }
 
-// the kernels of one batch, in stream order; e* may be null
 // The wavetable leaf voices that carry records this batch - the four host-made class lists (wtosc |
 // 2 x wtosc [-> filter12] -> panmix; the last one with its quiet voices) and the three lists of voices
 // whose records the device VM has just written - through the window kernels (a2amd_win.hip): per slab
 // of the batch the control pass of every list, then the render pass of every list.  A slot per fragment
 // and voice, a pool of further windows sized by the bound the control pass allocates by (one per record);
 // a batch whose slots would not fit A2AMD_WIN_MB (1 024) is cut into slabs of fragments.
-static int issue_windows(a2amd_ctx *c, const int *const *lists, const int *counts, const std::function<int()> &mid)
+static int issue_windows(a2amd_ctx *c, const int *d_dyn, const ListRange *dyn, const std::function<int()> &mid)
 {
 	const int sset = c->vm.spec_set;	// (the speculative slot set a taken pass wrote: mid() may launch the next pass)
 	// vmk >= 0: a class of VM voices run by k_vm_win; spec: ... that a speculative pass has already run for this batch
@@ -1153,9 +1097,9 @@ static int issue_windows(a2amd_ctx *c, const int *const *lists, const int *count
 	size_t nvoices = 0;		// ... of the jobs that take slots here
 	const bool spec = c->vm.fused && c->vm.spec_use;
 	for(int k = 0; k < 4; ++k)
-		if(counts[k]) {
-			jobs[nj++] = Job{ nosc[k], filt[k], counts[k], k == 3 && c->o2f_quiet, lists[k], -1, false, 0, 0 };	// (k == 3: see upload(), dyn_f2)
-			nvoices += (size_t)counts[k];
+		if(dyn[k].count) {
+			jobs[nj++] = Job{ nosc[k], filt[k], dyn[k].count, k == DYN_FILT2 && c->o2f_quiet, d_dyn + dyn[k].first, -1, false, 0, 0 };	// (DYN_FILT2: see upload())
+			nvoices += (size_t)dyn[k].count;
 		}
 	// (the control pass takes room in the pool by the length of a voice's record run: every gliding voice's run is
 	// the ONE shared stand-in record)
@@ -1450,6 +1394,302 @@ static int issue_windows(a2amd_ctx *c, const int *const *lists, const int *count
 	return 0;
 }
 
+static void flush_commits(a2amd_ctx *c, A2DCommitSet *pend)
+{
+	for(int k = 0; k < pend->n; ++k)
+		a2d_launch_commit(c->hparams, pend->c[k], c->stream);
+	pend->n = 0;
+}
+
+// k_leaf_recs over one list of a class
+// (a wavefront walks its voices one after the other, fragment by fragment: as many
+// wavefronts as the chip holds before a wavefront gets a second voice)
+static int launch_recs(a2amd_ctx *c, int nosc, int filt, const int *list, int n, int skip_empty)
+{
+	if(!n)
+		return 0;
+	const int vpw = getenv("A2AMD_RVPW") ? atoi(getenv("A2AMD_RVPW")) : (n + 8191) / 8192;
+	if(a2d_launch_leaf_recs(c->d_params, c->hparams, nosc, filt, list, n, vpw, c->stream, skip_empty))
+		return c->fail(A2AMD_EHIP, "leaf records launch failed: %s", hipGetErrorString(hipGetLastError()));
+	++c->stats.launches;
+	return 0;
+}
+
+// k_leaf_oscpan is the batch's only leaf kernel: no voice in any other leaf segment, no exceptions
+static bool oscpan_alone(const a2amd_ctx *c)
+{
+	for(int k = 0; k < LEAF_N; ++k)
+		if((c->leaf[k].count != 0) != (k == LEAF_OSCPAN))
+			return false;
+	return c->dyn[DYN_REST].first + c->dyn[DYN_REST].count == 0;
+}
+
+// The batch's leaf kernels other than the window kernels (issue_leaf_phase says when they run): what the block needs of
+// its caller, and whether it has run
+struct LeafPass {
+	A2DCommitSet *pend;	// state commits the time-sliced quiet kernels leave for a later launch
+	hipEvent_t e1;
+	bool use_win;		// the window kernels render the voices with records (else: the records kernels, here)
+	bool solo;		// oscpan_alone()
+	bool done;
+};
+
+static int launch_leaves(a2amd_ctx *c, LeafPass &lp)
+{
+	if(lp.done)
+		return 0;
+	lp.done = true;
+	A2DCommitSet &pend = *lp.pend;
+	const int *const list = c->d_list.d;
+	// A class whose quiet voices are ALL the device VM's, none of them left alone this batch - the speculative pass
+	// that was taken for it counted (A2DVmwOut::idle) - has nothing for its quiet kernel to do, and a launch that
+	// finds that out voice by voice is 10 us (k_leaf_oscpan + commit) to 80 us (k_leaf_oscfiltpan: sixteen
+	// wavefronts per workgroup through the batch's fragments, barriers and all) in front of the next pass
+	// (profiles/r06_timeline_before.txt).  The launch classes contain the VM's (every live voice of the class is in
+	// the list, classify above): equal counts are equal sets.
+	// Not for the filter class: there the 80 us happen to keep the order that is best for it - the render pass onto
+	// the CUs first, the next pass behind it (vm_speculate) - and without them the two start together: 16 384 voices,
+	// a2_Run(4096) 1 398 -> 1 416 us per buffer, a2_Run(1024) 399 -> 416; with the pass held back behind the render
+	// pass instead 1 370 and 408 (profiles/r06_go_skip_ab.txt).  A2AMD_VMSKIP: bit 0 the classes without filter12,
+	// bit 1 the one with.
+	static const int vmskip = getenv("A2AMD_VMSKIP") ? atoi(getenv("A2AMD_VMSKIP")) : 1;
+	auto none_quiet = [&](int k, int nleaf) {
+		return (vmskip & (k == 2 ? 2 : 1)) && c->vm.spec_use && !c->vm.list.empty() && c->vm.n_cls[k] == nleaf && c->vm.spec_idle[k] == 0;
+	};
+	// e1 right behind the main kernel when it is the only leaf kernel
+	// of the batch (lp.solo): "leaf" time is then that kernel alone
+	const ListRange oscpan = c->leaf[LEAF_OSCPAN];
+	if(oscpan.count && none_quiet(0, oscpan.count)) {
+		if(lp.solo && lp.e1)
+			HIPCHK(c, hipEventRecord(lp.e1, c->stream));
+		++c->vm.quiet_skipped;
+	} else if(oscpan.count) {
+		int vpw, ysplit;
+		pick_fast_shape(oscpan.count, c->nfrags, &vpw, &ysplit);
+		if(a2d_launch_leaf_oscpan(c->d_params, c->hparams, list + oscpan.first, oscpan.count,
+				vpw, ysplit, c->d_ustage.d, c->stream, lp.solo ? (void *)lp.e1 : nullptr, &pend.c[pend.n]))
+			return c->fail(A2AMD_EHIP, "fast leaf launch failed: %s", hipGetErrorString(hipGetLastError()));
+		if(pend.c[pend.n].nlist)
+			++pend.n;
+		++c->stats.launches;
+	}
+	const ListRange osc2pan = c->leaf[LEAF_OSC2PAN];
+	if(osc2pan.count && none_quiet(1, osc2pan.count))
+		++c->vm.quiet_skipped;
+	else if(osc2pan.count) {
+		int vpw, ysplit;
+		// (its own chunk length; 16 time slices: 2.19 ms against 2.25 with 32 at configs[3], round 3)
+		pick_fast_shape(osc2pan.count, c->nfrags * A2D_FAST_FCH / A2D_OSC2_FCH, &vpw, &ysplit, 16);
+		if(a2d_launch_leaf_osc2pan(c->d_params, c->hparams, list + osc2pan.first, osc2pan.count,
+				vpw, ysplit, c->d_ustage.d, c->stream, &pend.c[pend.n]))
+			return c->fail(A2AMD_EHIP, "2-osc leaf launch failed: %s", hipGetErrorString(hipGetLastError()));
+		if(pend.c[pend.n].nlist)
+			++pend.n;
+		++c->stats.launches;
+	}
+	const ListRange oscfilt = c->leaf[LEAF_OSCFILTPAN];
+	if(oscfilt.count && none_quiet(2, oscfilt.count))
+		++c->vm.quiet_skipped;
+	else if(oscfilt.count) {
+		// voices per workgroup = lanes of its filter wavefront: all 64 once there
+		// are enough voices for a workgroup on every CU (one 16-wavefront workgroup
+		// per CU), else spread out (a workgroup takes as long as its filter chain,
+		// whatever its voice count)
+		const int nf = oscfilt.count;
+		int vpw = getenv("A2AMD_FVPW") ? atoi(getenv("A2AMD_FVPW")) :
+				std::min(std::max((nf + 255) / 256, 1), 64);
+		if(a2d_launch_leaf_oscfiltpan(c->d_params, c->hparams, list + oscfilt.first, nf, vpw, c->stream))
+			return c->fail(A2AMD_EHIP, "filter leaf launch failed: %s", hipGetErrorString(hipGetLastError()));
+		++c->stats.launches;
+	}
+	const ListRange o2f = c->leaf[LEAF_OSC2FILTPAN];
+	if(o2f.count && c->o2f_quiet) {
+		// 2 x wtosc-filter12-panmix without records (round 6).  A workgroup (16 wavefronts, 128 registers: one per CU)
+		// takes as long as its filter wavefront's chain whatever its voice count, as long as every oscillator
+		// wavefront stays in its all-settled loop (a2d_osc2filtpan_max_vpg voices): the voices are dealt over the
+		// fewest whole rounds of 256 workgroups that allows (16 384 voices: 2 rounds of 32 - measured 1.09 ms per 256
+		// fragments against 3.83 with 48 and 1.50 with 64 voices per workgroup)
+		const int nf = o2f.count;
+		const int env_vpg = c->f2vpw;
+		const int maxv = a2d_osc2filtpan_max_vpg();
+		const int rounds = std::max(1, (nf + 256 * maxv - 1) / (256 * maxv));
+		const int vpg = env_vpg ? env_vpg : std::min(std::max((nf + 256 * rounds - 1) / (256 * rounds), 1), maxv);
+		if(a2d_launch_leaf_osc2filtpan(c->d_params, c->hparams, list + o2f.first, nf, vpg, c->stream))
+			return c->fail(A2AMD_EHIP, "2-osc filter leaf launch failed: %s", hipGetErrorString(hipGetLastError()));
+		++c->stats.launches;
+		c->last_batch.o2f_launched = 1;
+		c->last_batch.o2f_voices = (uint32_t)nf;
+		c->last_batch.o2f_max_vpg = (uint32_t)maxv;
+		c->last_batch.o2f_vpg = (uint32_t)std::min(std::max(vpg, 1), 64);	// (the launcher's clamp: a filter wavefront's lanes)
+	}
+	const ListRange fm = c->leaf[LEAF_FMPAN];
+	int fm_kinds = 0;
+	for(int k = 0; k < 8; ++k)
+		fm_kinds += c->fm_kind_count[k] != 0;
+	if(fm_kinds > 1 && fm.count <= 16384 && !getenv("A2AMD_FMVPW")) {
+		// several kinds, few voices: one launch for all of them (the
+		// per-kind launches below would run back to back, each as long
+		// as a voice's serial chain)
+		if(a2d_launch_leaf_fmpan_all(c->d_params, c->hparams, list + fm.first, c->fm_kind_count, (fm.count + 1023) / 1024, c->stream))
+			return c->fail(A2AMD_EHIP, "fm leaf launch failed: %s", hipGetErrorString(hipGetLastError()));
+		++c->stats.launches;
+	} else {
+		for(int k = 0, at = fm.first; k < 8; at += c->fm_kind_count[k++]) {
+			const int n = c->fm_kind_count[k];
+			if(!n)
+				continue;
+			// A voice is a serial recurrence: a launch takes as long as its longest
+			// lane, so few voices are spread over many wavefronts (idle lanes of a
+			// wavefront shadow its voices, see fmpan_body) until there is one
+			// wavefront per SIMD (1 024), then the lanes fill up
+			// (profiles/r01_fm_vpw_sweep.txt).
+			int vpw = getenv("A2AMD_FMVPW") ? atoi(getenv("A2AMD_FMVPW")) : (n + 1023) / 1024;
+			vpw = std::min(std::max(vpw, 1), 64);
+			if(a2d_launch_leaf_fmpan(c->d_params, c->hparams, A2AMD_FM1 + k, list + at, n, vpw, c->stream))
+				return c->fail(A2AMD_EHIP, "fm leaf launch failed: %s", hipGetErrorString(hipGetLastError()));
+			++c->stats.launches;
+		}
+	}
+	const ListRange gen = c->leaf[LEAF_GENERIC];
+	if(gen.count) {
+		if(a2d_launch_voices(c->d_params, list + gen.first, gen.count, pick_vpw(gen.count), c->stream))
+			return c->fail(A2AMD_EHIP, "leaf launch failed: %s", hipGetErrorString(hipGetLastError()));
+		++c->stats.launches;
+	}
+	if(!lp.use_win) {
+		// the records kernels: the four host-made lists ...
+		// (the fourth list: this batch's record-carrying 2 x wtosc-filter12-panmix voices and the device VM's voices of that
+		// class, taken with skip_empty - upload())
+		static const int nosc[4] = { 1, 2, 1, 2 }, filt[4] = { 0, 0, 1, 1 };
+		const int *lists[4];
+		int counts[4], total = 0, kinds = 0;
+		for(int k = 0; k < 4; ++k) {
+			lists[k] = c->d_dyn + c->dyn[k].first;
+			counts[k] = c->dyn[k].count;
+			total += counts[k];
+			kinds += counts[k] != 0;
+		}
+		c->last_batch.recs_voices = (uint32_t)total;
+		if(!c->vm.list.empty())
+			c->last_batch.recs_voices += (uint32_t)(c->vm.n_cls[0] + c->vm.n_cls[1] + c->vm.n_cls[2]);
+		if(kinds > 1 && total <= 4096 && !getenv("A2AMD_RVPW")) {
+			// few voices of several kinds (a song): one launch - on one stream the per-kind
+			// launches would run back to back, each as long as one voice's walk through the batch
+			if(a2d_launch_leaf_recs_all(c->d_params, c->hparams, lists, counts, 1, c->stream, c->o2f_quiet ? 8 : 0))
+				return c->fail(A2AMD_EHIP, "leaf records launch failed: %s", hipGetErrorString(hipGetLastError()));
+			++c->stats.launches;
+		} else {
+			for(int k = 0; k < 4; ++k)
+				if(int r = launch_recs(c, nosc[k], filt[k], lists[k], counts[k], k == DYN_FILT2 && c->o2f_quiet))
+					return r;
+		}
+		// ... and the voices whose records the device VM has just written, by class (those it
+		// left without records this batch were rendered by their quiet kernels above)
+		if(!c->vm.list.empty()) {
+			const int *l = c->vm.d_list.d + c->vm.list.size();
+			for(int k = 0; k < 3; l += c->vm.n_cls[k++])
+				if(int r = launch_recs(c, nosc[k], filt[k], l, c->vm.n_cls[k], 1))
+					return r;
+		}
+	}
+	const ListRange rest = c->dyn[DYN_REST];
+	if(rest.count > 0) {
+		if(a2d_launch_voices(c->d_params, c->d_dyn + rest.first, rest.count, pick_vpw(rest.count), c->stream))
+			return c->fail(A2AMD_EHIP, "leaf launch failed: %s", hipGetErrorString(hipGetLastError()));
+		++c->stats.launches;
+	}
+	return 0;
+}
+
+// The SUBTREES phase from its start (not: resumed behind insert clients) up to the bus owners: the buses cleared, the
+// device VM, the leaf kernels
+static int issue_leaf_phase(a2amd_ctx *c, bool consume, bool consume_sub, hipEvent_t e0, hipEvent_t e1, A2DCommitSet *pend)
+{
+	// (a graph of a self-cleaning batch holds no memset: whoever launches it
+	// clears the buses first if they are not known to be clean, ensure_clean())
+	const bool selfclean = consume || consume_sub;
+	if(c->capturing ? !selfclean : !(selfclean && c->others_clean && c->root_clean))
+		HIPCHK(c, hipMemsetAsync(c->d_busmem.d, 0, c->bus_used * sizeof(int32_t), c->stream));
+	c->others_clean = selfclean;
+	c->root_clean = consume;
+	if(e0)
+		HIPCHK(c, hipEventRecord(e0, c->stream));
+	// the scripted voices the device runs itself: their VMs first - the records of this batch,
+	// runs[] pointing at them (a2amd_vm.cpp / a2amd_vm.hip) - then the kernels as for host records
+	// The voices that carry records this batch: the 2 x wtosc-filter12-panmix leaves, with and without
+	// records, and - of the classes that have quiet kernels of their own - this batch's voices with records.
+	// Round 5: the record stream resolved by a lane = voice control pass, the windows rendered
+	// from closed-form entries (a2amd_win.hip).  A2AMD_WIN=0: k_leaf_recs, the kernels of rounds
+	// 2-4 that interpret the records on the scalar unit of the rendering wavefront (A/B).
+	// Which one: the window kernels' two passes are each as long as ONE voice's walk through the batch (the
+	// control pass) / one filter chain (the render pass) whatever the voice count - 0.4 to 1 ms per 64 fragments -
+	// where k_leaf_recs, one wavefront per voice, takes 0.3 ms for a song's few dozen voices and 0.4 - 0.7 ms for a
+	// thousand; from a few thousand voices on it is k_leaf_recs that queues up (16 384: 1.1 - 3.9 ms against
+	// 0.5 - 1.8).  A2AMD_WIN=0 / 1 forces (the parity tests run both), A2AMD_WIN_MIN moves the threshold.
+	bool use_win;
+	{
+		const char *wenv = getenv("A2AMD_WIN");
+		const int win_min = c->win_min;
+		int nwinv = 0;
+		for(int k = DYN_OSC1; k <= DYN_FILT2; ++k)
+			nwinv += c->dyn[k].count;
+		for(int k = 0; k < 3; ++k)
+			nwinv += c->vm.list.empty() ? 0 : c->vm.n_cls[k];
+		use_win = wenv ? atoi(wenv) != 0 : nwinv >= win_min;
+	}
+	// (A2AMD_VMWIN=0: the device VM's voices through records - k_vm_count / k_vm_emit - whatever renders them)
+	static const bool vmwin_ok = !(getenv("A2AMD_VMWIN") && !atoi(getenv("A2AMD_VMWIN")));
+	if(int r = vm_issue(c, use_win && vmwin_ok && !c->vm.fused_off))
+		return r;
+	// a2amd_last_batch(): the lists as upload() made them; the launches below fill in the rest
+	c->last_batch = a2amd_batch_info{};
+	c->last_batch.o2f_class = (uint32_t)c->leaf[LEAF_OSC2FILTPAN].count;
+	c->last_batch.o2f_listed = (uint32_t)c->dyn[DYN_FILT2].count;
+	c->last_batch.n_moving_listed = (uint32_t)c->n_moving_listed;
+	c->last_batch.general_voices = (uint32_t)c->dyn[DYN_REST].count;
+	// The batch's other leaf kernels - the quiet kernels of the classes, the records kernels where the window kernels
+	// are not in use, the general kernel - as a block that runs once: normally behind the window kernels, and
+	// (round 6) from INSIDE issue_windows, between its control passes and its render passes, when a speculative VM
+	// pass is to follow: that pass may start as soon as the control passes (k_vm_win / k_vm_commit: the stepped state
+	// of the VM voices that are live this batch) and the quiet kernels (the phases of those that are idle) are done,
+	// and then has the render pass - the long one - beside it, not in front of it.  All of these kernels only ever
+	// ADD to the buses, and runs[] is written by the control passes: their order among themselves is free.
+	LeafPass lp = { pend, e1, use_win, oscpan_alone(c), false };
+	static const bool spec_early = !(getenv("A2AMD_VMSPEC_EARLY") && !atoi(getenv("A2AMD_VMSPEC_EARLY")));
+	const std::function<int()> mid = [&]() -> int {
+		if(!spec_early || !vmwin_ok || !vm_spec_wanted(c))
+			return 0;	// (no pass to follow: the old order)
+		if(int r = launch_leaves(c, lp))
+			return r;
+		// (a time-sliced quiet kernel leaves its voices' end state in the staging array until a commit that rides
+		// along with a later launch: the pass reads the unit state of the class voices that were idle this batch)
+		flush_commits(c, pend);
+		return vm_speculate(c);
+	};
+	// ... the window kernels first: k_vm_win says in runs[] which of the VM's voices are the quiet kernels' this batch
+	if(use_win) {
+		if(int r = issue_windows(c, c->d_dyn, c->dyn, mid))
+			return r;
+		if(vmwin_ok)
+			if(int r = vm_predict(c))
+				return r;
+	}
+	if(int r = launch_leaves(c, lp))
+		return r;
+	if(e1 && !lp.solo)
+		HIPCHK(c, hipEventRecord(e1, c->stream));
+	// Round 6: behind the leaf kernels (the quiet ones have moved the phases of the VM voices that were idle this
+	// batch), on a stream of its own beside the bus kernels, the readback and the engine thread's next walk:
+	// the class voices' VM + control pass for the batch expected next (vm_speculate, a2amd_vm.cpp)
+	if(use_win && vmwin_ok && !c->vm.spec_launched_now && vm_spec_wanted(c)) {
+		flush_commits(c, pend);	// (see mid(): the pass reads what the quiet kernels have staged)
+		if(int r = vm_speculate(c))
+			return r;
+	}
+	return 0;
+}
+
+// the kernels of one batch, in stream order; e* may be null
 int issue_kernels(a2amd_ctx *c, unsigned phases, hipEvent_t e0, hipEvent_t e1, hipEvent_t e2)
 {
 	// (self-cleaning buses need both phases in one go: the root's bus is read in ROOT)
@@ -1462,276 +1702,10 @@ int issue_kernels(a2amd_ctx *c, unsigned phases, hipEvent_t e0, hipEvent_t e1, h
 	A2DCommitSet pend;
 	pend.n = 0;
 	pend.c[0].nlist = pend.c[1].nlist = 0;
-	auto flush_commits = [&]() {
-		for(int k = 0; k < pend.n; ++k)
-			a2d_launch_commit(c->hparams, pend.c[k], c->stream);
-		pend.n = 0;
-	};
 	if(phases & A2AMD_RENDER_SUBTREES) {
-		if(c->sub_resume < 0) {
-		// (a graph of a self-cleaning batch holds no memset: whoever launches it
-		// clears the buses first if they are not known to be clean, ensure_clean())
-		const bool selfclean = consume || consume_sub;
-		if(c->capturing ? !selfclean : !(selfclean && c->others_clean && c->root_clean))
-			HIPCHK(c, hipMemsetAsync(c->d_busmem.d, 0, c->bus_used * sizeof(int32_t), c->stream));
-		c->others_clean = selfclean;
-		c->root_clean = consume;
-		if(e0)
-			HIPCHK(c, hipEventRecord(e0, c->stream));
-		// the scripted voices the device runs itself: their VMs first - the records of this batch,
-		// runs[] pointing at them (a2amd_vm.cpp / a2amd_vm.hip) - then the kernels as for host records
-		// The voices that carry records this batch: the 2 x wtosc-filter12-panmix leaves, with and without
-		// records, and - of the classes that have quiet kernels of their own - this batch's voices with records.
-		// Round 5: the record stream resolved by a lane = voice control pass, the windows rendered
-		// from closed-form entries (a2amd_win.hip).  A2AMD_WIN=0: k_leaf_recs, the kernels of rounds
-		// 2-4 that interpret the records on the scalar unit of the rendering wavefront (A/B).
-		// Which one: the window kernels' two passes are each as long as ONE voice's walk through the batch (the
-		// control pass) / one filter chain (the render pass) whatever the voice count - 0.4 to 1 ms per 64 fragments -
-		// where k_leaf_recs, one wavefront per voice, takes 0.3 ms for a song's few dozen voices and 0.4 - 0.7 ms for a
-		// thousand; from a few thousand voices on it is k_leaf_recs that queues up (16 384: 1.1 - 3.9 ms against
-		// 0.5 - 1.8).  A2AMD_WIN=0 / 1 forces (the parity tests run both), A2AMD_WIN_MIN moves the threshold.
-		const int *rlists[4] = { c->d_dyn, c->d_dyn + c->n_dyn_osc1, c->d_dyn + c->n_dyn_osc1 + c->n_dyn_osc2,
-				c->d_dyn + c->n_dyn_osc1 + c->n_dyn_osc2 + c->n_dyn_filt };
-		// (the fourth list: this batch's record-carrying 2 x wtosc-filter12-panmix voices and the device VM's voices of that
-		// class, taken with skip_empty - upload())
-		const int rcounts[4] = { c->n_dyn_osc1, c->n_dyn_osc2, c->n_dyn_filt, c->n_dyn_filt2 };
-		const int rtotal = rcounts[0] + rcounts[1] + rcounts[2] + rcounts[3];
-		bool use_win;
-		{
-			const char *wenv = getenv("A2AMD_WIN");
-			const int win_min = c->win_min;
-			int nwinv = rtotal;
-			for(int k = 0; k < 3; ++k)
-				nwinv += c->vm.list.empty() ? 0 : c->vm.n_cls[k];
-			use_win = wenv ? atoi(wenv) != 0 : nwinv >= win_min;
-		}
-		// (A2AMD_VMWIN=0: the device VM's voices through records - k_vm_count / k_vm_emit - whatever renders them)
-		static const bool vmwin_ok = !(getenv("A2AMD_VMWIN") && !atoi(getenv("A2AMD_VMWIN")));
-		if(int r = vm_issue(c, use_win && vmwin_ok && !c->vm.fused_off))
-			return r;
-		// a2amd_last_batch(): the lists as upload() made them; the launches below fill in the rest
-		c->last_batch = a2amd_batch_info{};
-		c->last_batch.o2f_class = (uint32_t)c->n_o2f_leaf;
-		c->last_batch.o2f_listed = (uint32_t)c->n_dyn_filt2;
-		c->last_batch.n_moving_listed = (uint32_t)c->n_moving_listed;
-		c->last_batch.general_voices = (uint32_t)c->n_dyn_rest;
-		// The batch's other leaf kernels - the quiet kernels of the classes, the records kernels where the window kernels
-		// are not in use, the general kernel - as a block that runs once: normally behind the window kernels, and
-		// (round 6) from INSIDE issue_windows, between its control passes and its render passes, when a speculative VM
-		// pass is to follow: that pass may start as soon as the control passes (k_vm_win / k_vm_commit: the stepped state
-		// of the VM voices that are live this batch) and the quiet kernels (the phases of those that are idle) are done,
-		// and then has the render pass - the long one - beside it, not in front of it.  All of these kernels only ever
-		// ADD to the buses, and runs[] is written by the control passes: their order among themselves is free.
-		bool leaves_done = false;
-		auto leaves = [&]() -> int {
-			if(leaves_done)
-				return 0;
-			leaves_done = true;
-			// A class whose quiet voices are ALL the device VM's, none of them left alone this batch - the speculative pass
-			// that was taken for it counted (A2DVmwOut::idle) - has nothing for its quiet kernel to do, and a launch that
-			// finds that out voice by voice is 10 us (k_leaf_oscpan + commit) to 80 us (k_leaf_oscfiltpan: sixteen
-			// wavefronts per workgroup through the batch's fragments, barriers and all) in front of the next pass
-			// (profiles/r06_timeline_before.txt).  The launch classes contain the VM's (every live voice of the class is in
-			// the list, classify above): equal counts are equal sets.
-			// Not for the filter class: there the 80 us happen to keep the order that is best for it - the render pass onto
-			// the CUs first, the next pass behind it (vm_speculate) - and without them the two start together: 16 384 voices,
-			// a2_Run(4096) 1 398 -> 1 416 us per buffer, a2_Run(1024) 399 -> 416; with the pass held back behind the render
-			// pass instead 1 370 and 408 (profiles/r06_go_skip_ab.txt).  A2AMD_VMSKIP: bit 0 the classes without filter12,
-			// bit 1 the one with.
-			static const int vmskip = getenv("A2AMD_VMSKIP") ? atoi(getenv("A2AMD_VMSKIP")) : 1;
-			auto none_quiet = [&](int k, int nleaf) {
-				return (vmskip & (k == 2 ? 2 : 1)) && c->vm.spec_use && !c->vm.list.empty() && c->vm.n_cls[k] == nleaf && c->vm.spec_idle[k] == 0;
-			};
-			if(c->n_fast_leaf && none_quiet(0, c->n_fast_leaf)) {
-				const bool solo = !c->n_osc2_leaf && !c->n_filt_leaf && !c->n_fm_leaf && !c->n_leaf && !c->n_leaf_dyn && !c->n_o2f_leaf;
-				if(solo && e1)
-					HIPCHK(c, hipEventRecord(e1, c->stream));
-				++c->vm.quiet_skipped;
-			} else if(c->n_fast_leaf) {
-				int vpw, ysplit;
-				pick_fast_shape(c->n_fast_leaf, c->nfrags, &vpw, &ysplit);
-				// e1 right behind the main kernel when it is the only leaf kernel
-				// of the batch: "leaf" time is then that kernel alone
-				const bool solo = !c->n_osc2_leaf && !c->n_filt_leaf && !c->n_fm_leaf && !c->n_leaf && !c->n_leaf_dyn && !c->n_o2f_leaf;
-				if(a2d_launch_leaf_oscpan(c->d_params, c->hparams, c->d_list.d, c->n_fast_leaf,
-						vpw, ysplit, c->d_ustage.d, c->stream, solo ? (void *)e1 : nullptr, &pend.c[pend.n]))
-					return c->fail(A2AMD_EHIP, "fast leaf launch failed: %s", hipGetErrorString(hipGetLastError()));
-				if(pend.c[pend.n].nlist)
-					++pend.n;
-				++c->stats.launches;
-			}
-			if(c->n_osc2_leaf && none_quiet(1, c->n_osc2_leaf))
-				++c->vm.quiet_skipped;
-			else if(c->n_osc2_leaf) {
-				int vpw, ysplit;
-				// (its own chunk length; 16 time slices: 2.19 ms against 2.25 with 32 at configs[3], round 3)
-				pick_fast_shape(c->n_osc2_leaf, c->nfrags * A2D_FAST_FCH / A2D_OSC2_FCH, &vpw, &ysplit, 16);
-				if(a2d_launch_leaf_osc2pan(c->d_params, c->hparams, c->d_list.d + c->n_fast_leaf, c->n_osc2_leaf,
-						vpw, ysplit, c->d_ustage.d, c->stream, &pend.c[pend.n]))
-					return c->fail(A2AMD_EHIP, "2-osc leaf launch failed: %s", hipGetErrorString(hipGetLastError()));
-				if(pend.c[pend.n].nlist)
-					++pend.n;
-				++c->stats.launches;
-			}
-			if(c->n_filt_leaf && none_quiet(2, c->n_filt_leaf))
-				++c->vm.quiet_skipped;
-			else if(c->n_filt_leaf) {
-				// voices per workgroup = lanes of its filter wavefront: all 64 once there
-				// are enough voices for a workgroup on every CU (one 16-wavefront workgroup
-				// per CU), else spread out (a workgroup takes as long as its filter chain,
-				// whatever its voice count)
-				const int nf = c->n_filt_leaf;
-				int vpw = getenv("A2AMD_FVPW") ? atoi(getenv("A2AMD_FVPW")) :
-						std::min(std::max((nf + 255) / 256, 1), 64);
-				if(a2d_launch_leaf_oscfiltpan(c->d_params, c->hparams, c->d_list.d + c->n_fast_leaf + c->n_osc2_leaf,
-						c->n_filt_leaf, vpw, c->stream))
-					return c->fail(A2AMD_EHIP, "filter leaf launch failed: %s", hipGetErrorString(hipGetLastError()));
-				++c->stats.launches;
-			}
-			if(c->n_o2f_leaf && c->o2f_quiet) {
-				// 2 x wtosc-filter12-panmix without records (round 6).  A workgroup (16 wavefronts, 128 registers: one per CU)
-				// takes as long as its filter wavefront's chain whatever its voice count, as long as every oscillator
-				// wavefront stays in its all-settled loop (a2d_osc2filtpan_max_vpg voices): the voices are dealt over the
-				// fewest whole rounds of 256 workgroups that allows (16 384 voices: 2 rounds of 32 - measured 1.09 ms per 256
-				// fragments against 3.83 with 48 and 1.50 with 64 voices per workgroup)
-				const int nf = c->n_o2f_leaf;
-				const int env_vpg = c->f2vpw;
-				const int maxv = a2d_osc2filtpan_max_vpg();
-				const int rounds = std::max(1, (nf + 256 * maxv - 1) / (256 * maxv));
-				const int vpg = env_vpg ? env_vpg : std::min(std::max((nf + 256 * rounds - 1) / (256 * rounds), 1), maxv);
-				if(a2d_launch_leaf_osc2filtpan(c->d_params, c->hparams, c->d_list.d + c->n_fast_leaf + c->n_osc2_leaf +
-						c->n_filt_leaf + c->n_fm_leaf + c->n_leaf, nf, vpg, c->stream))
-					return c->fail(A2AMD_EHIP, "2-osc filter leaf launch failed: %s", hipGetErrorString(hipGetLastError()));
-				++c->stats.launches;
-				c->last_batch.o2f_launched = 1;
-				c->last_batch.o2f_voices = (uint32_t)nf;
-				c->last_batch.o2f_max_vpg = (uint32_t)maxv;
-				c->last_batch.o2f_vpg = (uint32_t)std::min(std::max(vpg, 1), 64);	// (the launcher's clamp: a filter wavefront's lanes)
-			}
-			int fm_kinds = 0;
-			for(int k = 0; k < 8; ++k)
-				fm_kinds += c->fm_kind_count[k] != 0;
-			if(fm_kinds > 1 && c->n_fm_leaf <= 16384 && !getenv("A2AMD_FMVPW")) {
-				// several kinds, few voices: one launch for all of them (the
-				// per-kind launches below would run back to back, each as long
-				// as a voice's serial chain)
-				if(a2d_launch_leaf_fmpan_all(c->d_params, c->hparams, c->d_list.d + c->n_fast_leaf + c->n_osc2_leaf +
-						c->n_filt_leaf, c->fm_kind_count, (c->n_fm_leaf + 1023) / 1024, c->stream))
-					return c->fail(A2AMD_EHIP, "fm leaf launch failed: %s", hipGetErrorString(hipGetLastError()));
-				++c->stats.launches;
-			} else
-			for(int k = 0, at = c->n_fast_leaf + c->n_osc2_leaf + c->n_filt_leaf; k < 8; at += c->fm_kind_count[k++]) {
-				const int n = c->fm_kind_count[k];
-				if(!n)
-					continue;
-				// A voice is a serial recurrence: a launch takes as long as its longest
-				// lane, so few voices are spread over many wavefronts (idle lanes of a
-				// wavefront shadow its voices, see fmpan_body) until there is one
-				// wavefront per SIMD (1 024), then the lanes fill up
-				// (profiles/r01_fm_vpw_sweep.txt).
-				int vpw = getenv("A2AMD_FMVPW") ? atoi(getenv("A2AMD_FMVPW")) : (n + 1023) / 1024;
-				vpw = std::min(std::max(vpw, 1), 64);
-				if(a2d_launch_leaf_fmpan(c->d_params, c->hparams, A2AMD_FM1 + k, c->d_list.d + at, n, vpw, c->stream))
-					return c->fail(A2AMD_EHIP, "fm leaf launch failed: %s", hipGetErrorString(hipGetLastError()));
-				++c->stats.launches;
-			}
-			if(c->n_leaf) {
-				if(a2d_launch_voices(c->d_params, c->d_list.d + c->n_fast_leaf + c->n_osc2_leaf + c->n_filt_leaf +
-						c->n_fm_leaf, c->n_leaf,
-						pick_vpw(c->n_leaf), c->stream))
-					return c->fail(A2AMD_EHIP, "leaf launch failed: %s", hipGetErrorString(hipGetLastError()));
-				++c->stats.launches;
-			}
-			{
-				// (a wavefront walks its voices one after the other, fragment by fragment: as many
-				// wavefronts as the chip holds before a wavefront gets a second voice)
-				auto recs = [&](int nosc, int filt, const int *list, int n, int skip_empty) -> int {
-					if(!n)
-						return 0;
-					int vpw = getenv("A2AMD_RVPW") ? atoi(getenv("A2AMD_RVPW")) : (n + 8191) / 8192;
-					if(a2d_launch_leaf_recs(c->d_params, c->hparams, nosc, filt, list, n, vpw, c->stream, skip_empty))
-						return c->fail(A2AMD_EHIP, "leaf records launch failed: %s", hipGetErrorString(hipGetLastError()));
-					++c->stats.launches;
-					return 0;
-				};
-				const int *const *lists = rlists;
-				const int *counts = rcounts;
-				const int total = rtotal;
-				const int kinds = (counts[0] != 0) + (counts[1] != 0) + (counts[2] != 0) + (counts[3] != 0);
-				if(!use_win) {
-				c->last_batch.recs_voices = (uint32_t)total;
-				if(!c->vm.list.empty())
-					c->last_batch.recs_voices += (uint32_t)(c->vm.n_cls[0] + c->vm.n_cls[1] + c->vm.n_cls[2]);
-				if(kinds > 1 && total <= 4096 && !getenv("A2AMD_RVPW")) {
-					// few voices of several kinds (a song): one launch - on one stream the per-kind
-					// launches would run back to back, each as long as one voice's walk through the batch
-					if(a2d_launch_leaf_recs_all(c->d_params, c->hparams, lists, counts, 1, c->stream, c->o2f_quiet ? 8 : 0))
-						return c->fail(A2AMD_EHIP, "leaf records launch failed: %s", hipGetErrorString(hipGetLastError()));
-					++c->stats.launches;
-				} else {
-					static const int nosc[4] = { 1, 2, 1, 2 }, filt[4] = { 0, 0, 1, 1 };
-					for(int k = 0; k < 4; ++k)
-						if(int r = recs(nosc[k], filt[k], lists[k], counts[k], k == 3 && c->o2f_quiet))
-							return r;
-				}
-				// ... and the voices whose records the device VM has just written, by class (those it
-				// left without records this batch were rendered by their quiet kernels above)
-				if(!c->vm.list.empty()) {
-					static const int nosc[3] = { 1, 2, 1 }, filt[3] = { 0, 0, 1 };
-					const int *l = c->vm.d_list.d + c->vm.list.size();
-					for(int k = 0; k < 3; l += c->vm.n_cls[k++]) {
-						const int n = c->vm.n_cls[k];
-						if(!n)
-							continue;
-						int vpw = getenv("A2AMD_RVPW") ? atoi(getenv("A2AMD_RVPW")) : (n + 8191) / 8192;
-						if(a2d_launch_leaf_recs(c->d_params, c->hparams, nosc[k], filt[k], l, n, vpw, c->stream, 1))
-							return c->fail(A2AMD_EHIP, "leaf records launch failed: %s", hipGetErrorString(hipGetLastError()));
-						++c->stats.launches;
-					}
-				}
-				}
-			}
-			if(c->n_dyn_rest > 0) {
-				const int n = c->n_dyn_rest;
-				if(a2d_launch_voices(c->d_params, c->d_dyn + c->n_dyn_osc1 + c->n_dyn_osc2 + c->n_dyn_filt + c->n_dyn_filt2, n,
-						pick_vpw(n), c->stream))
-					return c->fail(A2AMD_EHIP, "leaf launch failed: %s", hipGetErrorString(hipGetLastError()));
-				++c->stats.launches;
-			}
-			return 0;
-		};
-		static const bool spec_early = !(getenv("A2AMD_VMSPEC_EARLY") && !atoi(getenv("A2AMD_VMSPEC_EARLY")));
-		const std::function<int()> mid = [&]() -> int {
-			if(!spec_early || !vmwin_ok || !vm_spec_wanted(c))
-				return 0;	// (no pass to follow: the old order)
-			if(int r = leaves())
+		if(c->sub_resume < 0)
+			if(int r = issue_leaf_phase(c, consume, consume_sub, e0, e1, &pend))
 				return r;
-			// (a time-sliced quiet kernel leaves its voices' end state in the staging array until a commit that rides
-			// along with a later launch: the pass reads the unit state of the class voices that were idle this batch)
-			flush_commits();
-			return vm_speculate(c);
-		};
-		// ... the window kernels first: k_vm_win says in runs[] which of the VM's voices are the quiet kernels' this batch
-		if(use_win) {
-			if(int r = issue_windows(c, rlists, rcounts, mid))
-				return r;
-			if(vmwin_ok)
-				if(int r = vm_predict(c))
-					return r;
-		}
-		if(int r = leaves())
-			return r;
-		if(e1 && !(c->n_fast_leaf && !c->n_osc2_leaf && !c->n_filt_leaf && !c->n_fm_leaf && !c->n_leaf && !c->n_leaf_dyn && !c->n_o2f_leaf))
-			HIPCHK(c, hipEventRecord(e1, c->stream));
-		// Round 6: behind the leaf kernels (the quiet ones have moved the phases of the VM voices that were idle this
-		// batch), on a stream of its own beside the bus kernels, the readback and the engine thread's next walk:
-		// the class voices' VM + control pass for the batch expected next (vm_speculate, a2amd_vm.cpp)
-		if(use_win && vmwin_ok && !c->vm.spec_launched_now && vm_spec_wanted(c)) {
-			flush_commits();	// (see mid(): the pass reads what the quiet kernels have staged)
-			if(int r = vm_speculate(c))
-				return r;
-		}
-		}	// (fresh start)
 		// the voices that own a bus, deepest first.  With A2AMD_RENDER_TAPS the walk stops behind a
 		// depth that holds a muted xinsert (insert clients: a2amd_unit_insertable): the host serves
 		// them and calls again.
@@ -1749,7 +1723,7 @@ int issue_kernels(a2amd_ctx *c, unsigned phases, hipEvent_t e0, hipEvent_t e1, h
 		}
 		// (the ROOT phase may run elsewhere, or later: nothing stays pending across calls)
 		if(!(phases & A2AMD_RENDER_ROOT))
-			flush_commits();
+			flush_commits(c, &pend);
 	}
 	if(phases & A2AMD_RENDER_ROOT) {
 		// The root chain adds into the master bus.  When its phase runs on its own
@@ -1766,11 +1740,11 @@ int issue_kernels(a2amd_ctx *c, unsigned phases, hipEvent_t e0, hipEvent_t e1, h
 				return r;
 		if(!has_sub && root_stores)
 			c->root_clean = true;
-		flush_commits();
+		flush_commits(c, &pend);
 		if(e2)
 			HIPCHK(c, hipEventRecord(e2, c->stream));
 		c->stats.fragments += c->nfrags;
-		c->stats.voice_fragments += (uint64_t)c->nfrags * (uint64_t)(c->list_all.size() - c->n_list_pads);
+		c->stats.voice_fragments += (uint64_t)c->nfrags * (uint64_t)c->list_all.size();
 	}
 	return 0;
 }
