@@ -250,6 +250,10 @@ struct A2DNoiseOsc { uint32_t ph_lo, ph_hi, dphase; int32_t unit, slot, pad[3]; 
 int a2d_launch_noise_seeds(const A2DNoiseOsc *osc, int n, uint32_t start, int f0, int count, unsigned frames,
 		uint32_t *seed, int stride, size_t seed_words, int32_t *nslot, int nunits, void *stream);
 
+// a2amd_noisepan.hip: k_leaf_noisepan, the quiet kernel of settled wtosc (noise) -> panmix voices in a batch with device-seeded
+// fragments (hp.nseed set): the voices of the list without records this batch, 'vpw' (at most 64) of them per wavefront
+int a2d_launch_leaf_noisepan(const A2DParams *dparams, const A2DParams &hp, const int *dlist, int nlist, int vpw, void *stream);
+
 // a2amd_vm.hip: the count pass (emit = 0) or the emit pass of the VM kernel
 int a2d_launch_vm(const A2DVmParams &vp, int emit, void *stream);
 // k_vm_pool: the window pool entries k_vm_win would take for the batch described by vp (vp.list: VM slots, any

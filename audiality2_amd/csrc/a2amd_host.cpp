@@ -14,6 +14,7 @@
 // collects (core.c:479-480, inline.c:32-33), so all children of all parents can
 // run first and each parent picks the sum up where its inline unit sits.
 #include "a2amd_host.h"
+#include "a2amd_noisemap.h"
 
 namespace a2h { thread_local char g_err[256] = ""; }
 
@@ -63,6 +64,7 @@ int a2amd_open(const a2amd_config *cfg, a2amd_ctx **out)
 	c->hosttiming = getenv("A2AMD_HOSTTIMING") != nullptr;
 	c->f2vpw = getenv("A2AMD_F2VPW") ? atoi(getenv("A2AMD_F2VPW")) : 0;
 	c->no_moving = getenv("A2AMD_NO_MOVING") != nullptr;
+	c->noise_quiet = !(getenv("A2AMD_NOISE_QUIET") && !atoi(getenv("A2AMD_NOISE_QUIET")));
 	c->win_slabs = getenv("A2AMD_WIN_SLABS") ? std::max(1, atoi(getenv("A2AMD_WIN_SLABS"))) : 1;
 	c->o2f_min = getenv("A2AMD_O2F_MIN") ? atoi(getenv("A2AMD_O2F_MIN")) : 512;
 	c->win_min = getenv("A2AMD_WIN_MIN") ? atoi(getenv("A2AMD_WIN_MIN")) : 2048;
@@ -566,6 +568,29 @@ uint64_t a2amd_noise_draws(uint64_t phase, uint32_t dphase, unsigned frames)
 	return ((phase + (uint64_t)frames * dphase) >> 23) - (phase >> 23);
 }
 
+// One window of a settled noise oscillator through the arithmetic k_leaf_noisepan renders with (a2amd_noisemap.h)
+uint32_t a2amd_noise_window(uint32_t seed, uint64_t phase, uint32_t dphase, int32_t held, unsigned frames, int32_t *values,
+		uint32_t *seed_after)
+{
+	if(frames > A2D_FRAG)
+		frames = A2D_FRAG;
+	unsigned total = 0;
+	for(unsigned s = 0; s < frames; ++s) {
+		const unsigned k = a2nm_upto((uint32_t)phase, dphase, s);
+		uint32_t A, C;
+		a2nm_map(k, &A, &C);
+		if(values)
+			values[s] = k ? a2nm_value(a2nm_word(A, C, seed)) : held;
+		total = k;
+	}
+	if(seed_after) {
+		uint32_t A, C;
+		a2nm_map(total, &A, &C);
+		*seed_after = a2nm_word(A, C, seed);
+	}
+	return total;
+}
+
 int a2amd_fragment_repeat_noise(a2amd_ctx *c, unsigned frames, unsigned count, uint32_t *noisestate)
 {
 	if(!noisestate)
@@ -912,7 +937,8 @@ int a2amd_unit_write(a2amd_ctx *c, int ui, int reg, int value, unsigned start, u
 				// the wavetable leaf kernels only know mip-mapped waves (and "off"): a
 				// voice that moves between the two kinds changes its launch class
 				const bool was = leaf_mode(u.mode), is = leaf_mode(nmode);
-				if(was != is)
+				// ... and so does one that moves between a wave and the noise generator (CLS_NOISEPAN, a2amd_sched.cpp)
+				if(was != is || (c->noise_quiet && (u.mode == A2D_OSC_NOISE) != (nmode == A2D_OSC_NOISE)))
 					c->lists_dirty = true;
 				if(!was || !is)
 					c->voices[u.voice].mode_mix = true;

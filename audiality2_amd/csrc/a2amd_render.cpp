@@ -446,6 +446,14 @@ int a2amd_last_batch(const a2amd_ctx *c, a2amd_batch_info *bi)
 	return A2AMD_OK;
 }
 
+int a2amd_last_batch_noise(const a2amd_ctx *c, a2amd_noise_batch_info *out)
+{
+	if(!c || !out)
+		return A2AMD_EINVAL;
+	*out = c->last_noise;
+	return A2AMD_OK;
+}
+
 int a2amd_set_profiling(a2amd_ctx *c, int on)
 {
 	if(int r = drain_events(c))

@@ -197,10 +197,10 @@ void sync_voice_mirror(a2amd_ctx *c, int vi)
 	m.own_nch = v.own_nch;
 }
 
-// what the wavetable leaf kernels play: mip-mapped waves, nothing, and - k_leaf_recs / the window kernels only - noise.
-// The quiet kernels never see a noise oscillator: every window the engine calls for carries an R_NOISESEED record, and
-// a voice whose noise windows are seeded on the device (a2amd_fragment_repeat_noise) is given a stand-in record run
-// by upload() in a batch in which it has no record of its own.
+// what the wavetable leaf kernels play: mip-mapped waves, nothing, and - k_leaf_recs / the window kernels and k_leaf_noisepan
+// only - noise.  The quiet kernels of the wavetable classes never see a noise oscillator: every window the engine calls for
+// carries an R_NOISESEED record, and a voice whose noise windows are seeded on the device (a2amd_fragment_repeat_noise) is
+// either k_leaf_noisepan's or given a stand-in record run by upload() in a batch in which it has no record of its own.
 
 // wtosc (mip-mapped wave playing) -> panmix 1->2 adding into the output bus
 bool is_oscpan_chain(const a2amd_ctx *c, const HVoice &v)
@@ -328,6 +328,7 @@ int upload(a2amd_ctx *c)
 	// end - records into their lists - and their states go up, a2amd_vm.cpp)
 	if(int r = vm_prepare_batch(c))
 		return r;
+	c->n_noise_standin = c->n_noise_quiet = 0;
 	if(c->hosttiming) {
 		// (A2AMD_HOSTTIMING: why a batch did not take the quiet path - first reason that applies)
 		const int why = !c->blob_quiet ? 0 : !c->with_recs.empty() ? 1 : !c->prev_with_recs.empty() ? 2 :
@@ -607,14 +608,37 @@ int upload(a2amd_ctx *c)
 	// Voices with a noise oscillator in a device-seeded stretch (a2amd_fragment_repeat_noise) and no record in the whole
 	// batch: the same stand-in run keeps them with the kernels that regenerate a window's draws from a seed - the window
 	// kernels / k_leaf_recs for the four wavetable classes, the general kernel (which takes its voices with or without
-	// records) for any other chain.  The quiet kernels know no noise.
+	// records) for any other chain.  The quiet kernels of the wavetable classes know no noise.
 	// (unlike a gliding voice, which the quiet kernels can take the slow way when its class is not known for sure -
-	// lists_dirty, mode_mix - a noise voice gets the run whatever its class: the quiet kernels must never see one)
-	for(const A2DNoiseOsc &o : c->noise_osc) {
-		const int vi = c->units[o.unit].voice;
-		const HVoice &v = c->voices[vi];
-		if(v.recs.empty() && v.moving_run != c->serial_base && (v.live || v.dying))
-			give_stand_in(vi);
+	// lists_dirty, mode_mix - a noise voice gets the run whatever its class: those kernels must never see one)
+	// The one exception is the class with a quiet kernel of its own, wtosc (noise) -> panmix (k_leaf_noisepan, round 7): a
+	// voice is left WITHOUT the run when its remembered class is CLS_NOISEPAN and still stands (a stale one may be any
+	// class once the lists are rebuilt below; one that stands comes out of a rebuild as it went in), its amplitude, volume
+	// and pan are at rest (moving_until, the test of the list above: the kernel renders settled voices only) and
+	// A2AMD_NOISE_QUIET is not 0.
+	// Invariant: a noise oscillator never stands in k_leaf_oscpan's list without a record - a noise-mode voice is classified
+	// CLS_NOISEPAN, never CLS_OSCPAN, and while a remembered CLS_OSCPAN is stale (a 'w' write to noise) it has the run - and a
+	// recordless noise voice is rendered by exactly one kernel, whether or not the lists are rebuilt in this upload():
+	// k_leaf_noisepan takes the voices of its segment whose run is empty, every other kernel those whose run is not.
+	{
+		const uint64_t t0 = c->vm.batch_time;
+		for(const A2DNoiseOsc &o : c->noise_osc) {
+			const int vi = c->units[o.unit].voice;
+			HVoice &v = c->voices[vi];
+			if(v.noise_run == c->serial_base)
+				continue;	// (a voice with two noise oscillators)
+			v.noise_run = c->serial_base;
+			if(!v.recs.empty() || !(v.live || v.dying))
+				continue;
+			const bool quiet = c->noise_quiet && v.cls == CLS_NOISEPAN && !v.cls_stale && v.resolved && v.vm < 0 &&
+					v.moving_until <= t0;
+			if(v.moving_run != c->serial_base && !quiet)
+				give_stand_in(vi);
+			if(v.moving_run == c->serial_base)
+				++c->n_noise_standin;
+			else
+				++c->n_noise_quiet;
+		}
 	}
 	now.resize(nnow);
 	c->with_recs.swap(now);
@@ -673,7 +697,9 @@ int upload(a2amd_ctx *c)
 				maxdepth = std::max(maxdepth, v.depth);
 			} else {
 				if(classify)
-					v.cls = !(c->no_fast & 1) && is_oscpan_chain(c, v) ? CLS_OSCPAN :
+					v.cls = !(c->no_fast & 1) && is_oscpan_chain(c, v) ?
+								// (the noise generator: a class of its own, k_leaf_noisepan - a 'w' write marks the class stale)
+								(c->noise_quiet && c->units[v.unit[0]].mode == A2D_OSC_NOISE ? CLS_NOISEPAN : CLS_OSCPAN) :
 							!(c->no_fast & 8) && is_osc2pan_chain(c, v) ? CLS_OSC2PAN :
 							!(c->no_fast & 2) && is_oscfiltpan_chain(c, v) ? CLS_OSCFILTPAN :
 							// (no quiet kernel of its own: k_leaf_recs renders it, records or not - unless an
@@ -745,7 +771,7 @@ int upload(a2amd_ctx *c)
 					fprintf(stderr, "REC %lld v%d f%u op%u u%u r%u val %d dur %u start %u\n", c->serial_base, vi,
 							A2D_RFRAG(r.head), A2D_ROP(r.head), A2D_RUNIT(r.head), A2D_RREG(r.head), r.value, r.dur, r.start);
 			// (fm-panmix voices execute their own records in k_leaf_fmpan)
-			if(v.cls == CLS_OSCPAN || v.cls == CLS_OSCFILTPAN || v.cls == CLS_OSC2PAN || v.cls == CLS_OSC2FILTPAN) {
+			if(v.cls == CLS_OSCPAN || v.cls == CLS_NOISEPAN || v.cls == CLS_OSCFILTPAN || v.cls == CLS_OSC2PAN || v.cls == CLS_OSC2FILTPAN) {
 				// (close_fragment's R_NOP is the one other record k_leaf_recs takes - as nothing)
 				const bool ok = !no_recs_kernel && !v.mode_mix && !v.fancy_recs;
 				// (on a list already, whichever: a voice the general kernel takes - DYN_REST - must not be put on DYN_FILT2 as
@@ -1473,6 +1499,19 @@ static int launch_leaves(a2amd_ctx *c, LeafPass &lp)
 			++pend.n;
 		++c->stats.launches;
 	}
+	// wtosc (noise) -> panmix without records: only a batch with device-seeded windows has such voices (in any other every
+	// window of a noise oscillator carries its R_NOISESEED record).  A wavefront keeps its voices for the whole batch - no
+	// time slices, the held sample travels - so the voices are spread like k_leaf_fmpan's: one wavefront per SIMD first
+	// (1 024), then the lanes fill up.
+	// (n_noise_quiet: the voices upload() left without the stand-in run - none, and every voice of the segment has records)
+	const ListRange noisepan = c->leaf[LEAF_NOISEPAN];
+	if(noisepan.count && !c->noise_st.empty() && c->n_noise_quiet) {
+		const int vpw = getenv("A2AMD_NZVPW") ? atoi(getenv("A2AMD_NZVPW")) : (noisepan.count + 1023) / 1024;
+		if(a2d_launch_leaf_noisepan(c->d_params, c->hparams, list + noisepan.first, noisepan.count, vpw, c->stream))
+			return c->fail(A2AMD_EHIP, "noise leaf launch failed: %s", hipGetErrorString(hipGetLastError()));
+		++c->stats.launches;
+		c->last_noise.quiet_launched = 1;
+	}
 	const ListRange osc2pan = c->leaf[LEAF_OSC2PAN];
 	if(osc2pan.count && none_quiet(1, osc2pan.count))
 		++c->vm.quiet_skipped;
@@ -1647,6 +1686,10 @@ static int issue_leaf_phase(a2amd_ctx *c, bool consume, bool consume_sub, hipEve
 	c->last_batch.o2f_listed = (uint32_t)c->dyn[DYN_FILT2].count;
 	c->last_batch.n_moving_listed = (uint32_t)c->n_moving_listed;
 	c->last_batch.general_voices = (uint32_t)c->dyn[DYN_REST].count;
+	c->last_noise = a2amd_noise_batch_info{};
+	c->last_noise.class_voices = (uint32_t)c->leaf[LEAF_NOISEPAN].count;
+	c->last_noise.standin_voices = c->n_noise_standin;
+	c->last_noise.quiet_voices = c->n_noise_quiet;
 	// The batch's other leaf kernels - the quiet kernels of the classes, the records kernels where the window kernels
 	// are not in use, the general kernel - as a block that runs once: normally behind the window kernels, and
 	// (round 6) from INSIDE issue_windows, between its control passes and its render passes, when a speculative VM

@@ -81,6 +81,15 @@ class a2amd_wavedesc(C.Structure):
                 ("data", C.POINTER(C.c_int16) * MIPLEVELS)]
 
 
+class a2amd_noise_batch_info(C.Structure):
+    """include/a2amd_noisepan.h: who rendered the noise voices of the most recent batch"""
+    _fields_ = [("quiet_launched", C.c_uint32), ("quiet_voices", C.c_uint32),
+                ("class_voices", C.c_uint32), ("standin_voices", C.c_uint32)]
+
+    def __repr__(self):
+        return "noise_batch_info(" + ", ".join(f"{n}={getattr(self, n)}" for n, _ in self._fields_) + ")"
+
+
 class Backend:
     """Thin ctypes veneer over one implementation of the call protocol."""
 
@@ -121,6 +130,9 @@ class Backend:
         self._fragment_repeat_noise = None
         if hasattr(lib, prefix + "fragment_repeat_noise"):
             self._fragment_repeat_noise = fn("fragment_repeat_noise", i32, vp, u32, u32, C.POINTER(C.c_uint32))
+        self._last_batch_noise = None
+        if hasattr(lib, prefix + "last_batch_noise"):
+            self._last_batch_noise = fn("last_batch_noise", i32, vp, C.POINTER(a2amd_noise_batch_info))
         # waves built on the device from what it rendered (the product library only)
         self.has_capture = hasattr(lib, prefix + "wave_upload_captured_post")
         if self.has_capture:
@@ -213,6 +225,15 @@ class Backend:
             raise RuntimeError(f"this library has no {self.prefix}fragment_repeat_noise")
         return self._chk(self._fragment_repeat_noise(self.ctx, frames, count, C.byref(self.noise)),
                          "fragment_repeat_noise")
+
+    def last_batch_noise(self):
+        """a2amd_last_batch_noise: whether k_leaf_noisepan was launched for the most recent batch, the voices it
+        rendered, the voices of its launch class, the noise voices given the stand-in record instead"""
+        if self._last_batch_noise is None:
+            raise RuntimeError(f"this library has no {self.prefix}last_batch_noise")
+        bi = a2amd_noise_batch_info()
+        self._chk(self._last_batch_noise(self.ctx, C.byref(bi)), "last_batch_noise")
+        return bi
 
     def unit_init(self, voice_key, kind, flags, nin, nout, wired, transpose=0, wakefrac=0):
         return self._chk(self._unit_init(self.ctx, voice_key, kind, flags, nin, nout, wired,

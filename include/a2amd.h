@@ -429,7 +429,8 @@ typedef struct a2amd_batch_info {
 	uint32_t recs_voices;      /* voices on the lists the records kernels (k_leaf_recs) were given      */
 	uint32_t win_voices;       /* voices on the lists the window kernels were given                     */
 	uint32_t win_slabs;        /* slabs the window kernels cut the batch into (0: not launched)         */
-	uint32_t n_moving_listed;  /* voices given the stand-in record: gliding, device-seeded noise        */
+	uint32_t n_moving_listed;  /* voices given the stand-in record: gliding ones, and the device-seeded noise voices
+	                            * that k_leaf_noisepan does not render (a2amd_noisepan.h: standin_voices)          */
 	uint32_t general_voices;   /* record-carrying leaf voices sent to the general kernel                */
 } a2amd_batch_info;
 int  a2amd_last_batch(const a2amd_ctx *ctx, a2amd_batch_info *bi);
@@ -440,6 +441,8 @@ int  a2amd_last_batch(const a2amd_ctx *ctx, a2amd_batch_info *bi);
 
 /* The noise generator in closed form: a2amd_fragment_repeat_noise(), a2amd_noise_jump(), a2amd_noise_draws(). */
 #include "a2amd_noise.h"
+/* ... and the quiet kernel of settled noise voices: a2amd_last_batch_noise(), a2amd_noise_window(). */
+#include "a2amd_noisepan.h"
 /* Rendered waves with "normalize" / "xfade", post-processed on the device: a2amd_wave_upload_captured_post(), a2amd_wavepost_host(). */
 #include "a2amd_wavepost.h"
 

@@ -3,8 +3,11 @@
 63 through a2amd_fragment_repeat_noise (the seeds made on the device).  Per batch: the time the recording calls take
 as driven from Python (ctypes overhead included - the same for any library), the a2amd_render() call, and the kernels'
 HIP-event time.  LIB: the liba2amd.so to measure (two builds interleaved: one process each).
+Mode repeat_only: one fragment walked and rendered ahead of everything, then every batch 64 fragments through
+a2amd_fragment_repeat_noise and nothing else - no noise voice has a record of its own, which is where k_leaf_noisepan
+renders them (a library from before it: the stand-in record and the window kernels).
 
-usage: tools/noise_repeat_timing.py LIB calls|repeat [batches] [warm-up batches]  -> one JSON line"""
+usage: tools/noise_repeat_timing.py LIB calls|repeat|repeat_only [batches] [warm-up batches]  -> one JSON line"""
 import ctypes, json, os, sys, time
 lib, mode = sys.argv[1], sys.argv[2]
 batches = int(sys.argv[3]) if len(sys.argv) > 3 else 8
@@ -42,6 +45,9 @@ def walk():
 
 
 rows = []
+if mode == "repeat_only":
+    walk()
+    be.render(64)
 for b in range(warm + batches):
     if b == warm:
         be.lib.a2amd_set_profiling(be.ctx, 1)
@@ -49,6 +55,8 @@ for b in range(warm + batches):
     if mode == "calls":
         for _ in range(64):
             walk()
+    elif mode == "repeat_only":
+        be.fragment_repeat_noise(64, 64)
     else:
         walk()
         t0 = time.perf_counter()      # (the one walked fragment is not what is measured)
@@ -60,12 +68,16 @@ for b in range(warm + batches):
         rows.append((t1 - t0, t2 - t1))
 st = Stats()
 be.lib.a2amd_get_stats(be.ctx, ctypes.byref(st))
+# (who rendered the last batch's noise voices, where the library says)
+quiet = be.last_batch_noise() if hasattr(be.lib, "a2amd_last_batch_noise") else None
 rec = np.array(rows) * 1e3
 print(json.dumps({"lib": os.path.basename(os.path.dirname(lib)) + "/" + os.path.basename(lib), "mode": mode,
                   "batches": batches, "record_ms_median": float(np.median(rec[:, 0])), "record_ms_min": float(rec[:, 0].min()),
                   "record_ms_max": float(rec[:, 0].max()), "render_call_ms_median": float(np.median(rec[:, 1])),
                   "render_call_ms_min": float(rec[:, 1].min()), "render_call_ms_max": float(rec[:, 1].max()),
                   "kernel_ms_per_batch": st.timed_all_ms / max(1, st.timed_batches), "timed_batches": int(st.timed_batches),
+                  "quiet_launched": int(quiet.quiet_launched) if quiet else None,
+                  "quiet_voices": int(quiet.quiet_voices) if quiet else None,
                   "noise": int(be.noise.value), "peak": int(np.abs(out).max()),
                   "sum": int(out.astype(np.int64).sum())}))
 be.close()
