@@ -67,6 +67,7 @@ int a2amd_open(const a2amd_config *cfg, a2amd_ctx **out)
 	c->noise_quiet = !(getenv("A2AMD_NOISE_QUIET") && !atoi(getenv("A2AMD_NOISE_QUIET")));
 	c->win_slabs = getenv("A2AMD_WIN_SLABS") ? std::max(1, atoi(getenv("A2AMD_WIN_SLABS"))) : 1;
 	c->o2f_min = getenv("A2AMD_O2F_MIN") ? atoi(getenv("A2AMD_O2F_MIN")) : 512;
+	c->nzf_min = getenv("A2AMD_NZF_MIN") ? std::max(1, atoi(getenv("A2AMD_NZF_MIN"))) : A2AMD_NZF_MIN_DEFAULT;
 	c->win_min = getenv("A2AMD_WIN_MIN") ? atoi(getenv("A2AMD_WIN_MIN")) : 2048;
 	c->bus_stride_frames = (size_t)c->cfg.max_batch * A2D_FRAG;
 	c->bus_used = c->bus_stride_frames * (size_t)c->cfg.channels;	// master bus at offset 0
@@ -591,6 +592,41 @@ uint32_t a2amd_noise_window(uint32_t seed, uint64_t phase, uint32_t dphase, int3
 	return total;
 }
 
+// One window of a settled noise oscillator and the filter behind it through the arithmetic k_leaf_noisefiltpan renders with
+// (a2amd_noisemap.h: the draws in closed form, a2nm_out, a2nm_filt = filt_step's formula)
+uint32_t a2amd_noise_filter_window(uint32_t seed, uint64_t phase, uint32_t dphase, int32_t held, int32_t avalue,
+		int32_t qvalue, int32_t f1, int32_t lp, int32_t bp, int32_t hp, int32_t *d1, int32_t *d2,
+		unsigned frames, int32_t *values, uint32_t *seed_after, int32_t *held_after)
+{
+	if(frames > A2D_FRAG)
+		frames = A2D_FRAG;
+	int32_t z1 = 0, z2 = 0;
+	if(!d1)
+		d1 = &z1;
+	if(!d2)
+		d2 = &z2;
+	unsigned total = 0;
+	int32_t x = held;
+	for(unsigned s = 0; s < frames; ++s) {
+		const unsigned k = a2nm_upto((uint32_t)phase, dphase, s);
+		uint32_t A, C;
+		a2nm_map(k, &A, &C);
+		x = k ? a2nm_value(a2nm_word(A, C, seed)) : held;
+		const int32_t y = a2nm_filt(a2nm_out(x, avalue) >> 5, qvalue >> 12, f1 >> 12, lp, bp, hp, d1, d2);
+		if(values)
+			values[s] = y;
+		total = k;
+	}
+	if(seed_after) {
+		uint32_t A, C;
+		a2nm_map(total, &A, &C);
+		*seed_after = a2nm_word(A, C, seed);
+	}
+	if(held_after)
+		*held_after = x;
+	return total;
+}
+
 int a2amd_fragment_repeat_noise(a2amd_ctx *c, unsigned frames, unsigned count, uint32_t *noisestate)
 {
 	if(!noisestate)
@@ -937,7 +973,8 @@ int a2amd_unit_write(a2amd_ctx *c, int ui, int reg, int value, unsigned start, u
 				// the wavetable leaf kernels only know mip-mapped waves (and "off"): a
 				// voice that moves between the two kinds changes its launch class
 				const bool was = leaf_mode(u.mode), is = leaf_mode(nmode);
-				// ... and so does one that moves between a wave and the noise generator (CLS_NOISEPAN, a2amd_sched.cpp)
+				// ... and so does one that moves between a wave and the noise generator (CLS_NOISEPAN, CLS_NOISEFILTPAN:
+				// any wtosc of any chain, a2amd_sched.cpp)
 				if(was != is || (c->noise_quiet && (u.mode == A2D_OSC_NOISE) != (nmode == A2D_OSC_NOISE)))
 					c->lists_dirty = true;
 				if(!was || !is)

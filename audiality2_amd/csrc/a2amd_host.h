@@ -211,12 +211,13 @@ struct HVoice {
 };
 
 enum { CLS_GENERIC = 0, CLS_OSCPAN, CLS_OSCFILTPAN, CLS_BUSDRIVER, CLS_BUSGENERIC, CLS_OSC2PAN, CLS_FMPAN, CLS_FBDCHAIN,
-	CLS_OSC2FILTPAN, CLS_NOISEPAN, CLS_N };	// (cls_lists below has a row per class, in this order)
+	CLS_OSC2FILTPAN, CLS_NOISEPAN, CLS_NOISEFILTPAN, CLS_N };	// (cls_lists below has a row per class, in this order)
 
 // ---- the launch lists: one table of ranges ----
 // a2amd_ctx::list_all (on the device: d_list), rebuilt when the voice tree changes, holds every listed voice by launch class:
 //   [ wtosc-panmix | 2 x wtosc-panmix | wtosc-filter12-panmix | fm-panmix | general leaves | 2 x wtosc-filter12-panmix |
-//     wtosc (noise)-panmix | per nesting depth, 0 first: driver chains | delay chains | general bus voices ]
+//     wtosc (noise)-panmix | wtosc (noise)-filter12-panmix | per nesting depth, 0 first: driver chains | delay chains |
+//     general bus voices ]
 // a2amd_ctx::leaf[LEAF_*] are the leaf segments IN LIST ORDER (2 x wtosc-filter12-panmix was appended behind the general
 // leaves in round 6 and stays there: the order shows in d_list offsets and in the device VM's lists), depth_ranges[d] the
 // rest.  The wavetable and general segments are sorted by output bus, so that a wavefront can sum several voices before
@@ -228,7 +229,8 @@ enum { CLS_GENERIC = 0, CLS_OSCPAN, CLS_OSCFILTPAN, CLS_BUSDRIVER, CLS_BUSGENERI
 // a2amd_ctx::dyn[DYN_*] (the first four: the records / window kernels' lists) and depth_ranges[d].dyn are OFFSETS into
 // d_dyn, which moves when the blob grows (a2amd_vm.cpp).
 struct ListRange { int first = 0, count = 0; };
-enum { LEAF_OSCPAN = 0, LEAF_OSC2PAN, LEAF_OSCFILTPAN, LEAF_FMPAN, LEAF_GENERIC, LEAF_OSC2FILTPAN, LEAF_NOISEPAN, LEAF_N };
+enum { LEAF_OSCPAN = 0, LEAF_OSC2PAN, LEAF_OSCFILTPAN, LEAF_FMPAN, LEAF_GENERIC, LEAF_OSC2FILTPAN, LEAF_NOISEPAN, LEAF_NOISEFILTPAN,
+	LEAF_N };
 enum { DYN_OSC1 = 0, DYN_OSC2, DYN_FILT, DYN_FILT2, DYN_REST, DYN_N };
 struct DepthRange { ListRange driver, fbd, generic, dyn; };
 // a launch class's leaf segment and, where k_leaf_recs knows the class, its exception list (-1: a bus owner), in CLS_* order
@@ -236,7 +238,15 @@ static const struct { int8_t leaf, dyn; } cls_lists[CLS_N] = {
 	{ LEAF_GENERIC, DYN_REST }, { LEAF_OSCPAN, DYN_OSC1 }, { LEAF_OSCFILTPAN, DYN_FILT }, { -1, -1 }, { -1, -1 },
 	{ LEAF_OSC2PAN, DYN_OSC2 }, { LEAF_FMPAN, DYN_REST }, { -1, -1 }, { LEAF_OSC2FILTPAN, DYN_FILT2 },
 	// wtosc (noise)-panmix: a segment of its own for k_leaf_noisepan; with records it is a one-oscillator voice like any other
-	{ LEAF_NOISEPAN, DYN_OSC1 } };
+	{ LEAF_NOISEPAN, DYN_OSC1 },
+	// wtosc (noise)-filter12-panmix: likewise, k_leaf_noisefiltpan's; with records a one-oscillator filter voice like any other
+	{ LEAF_NOISEFILTPAN, DYN_FILT } };
+// wtosc (noise)-filter12-panmix voices without a record in a batch from which k_leaf_noisefiltpan takes them (a2amd_ctx::nzf_min,
+// A2AMD_NZF_MIN): a launch lasts as long as its filter wavefront's chain through the batch however few of its lanes are
+// busy, behind the window kernels on the context's one stream, which render a few such voices inside the launch they make
+// anyway (A2AMD_O2F_MIN's lesson, upload()).  Never below 16.  NOT MEASURED: 64 is one filter wavefront with every lane busy
+// (profiles/noise_filt_quiet.md).
+#define A2AMD_NZF_MIN_DEFAULT 64
 
 // host side of an xinsert client slot
 struct XioSlot {
@@ -491,7 +501,7 @@ struct a2amd_ctx {
 	// function-local static (which keeps the value the first context of the process saw; tests/test_switches.py)
 	int f2vpw = 0;				// A2AMD_F2VPW: voices per workgroup of k_leaf_osc2filtpan (0: the launcher's own choice)
 	bool no_moving = false;			// A2AMD_NO_MOVING: gliding voices get no stand-in record (they stay the quiet kernels')
-	bool noise_quiet = true;		// A2AMD_NOISE_QUIET=0: no launch class for wtosc (noise)-panmix voices - they are wtosc-panmix
+	bool noise_quiet = true;		// A2AMD_NOISE_QUIET=0: no launch classes for wtosc (noise)-[filter12-]panmix voices - they are wtosc-[filter12-]panmix
 						// voices, and every noise voice of a device-seeded batch gets the stand-in record (A/B)
 	int win_slabs = 1;			// A2AMD_WIN_SLABS: slabs a batch of 16 fragments or more is cut into for the window kernels
 	int o2f_min = 512;			// A2AMD_O2F_MIN: voices of 2 x wtosc-filter12-panmix from which the class has its quiet kernel
@@ -499,6 +509,11 @@ struct a2amd_ctx {
 	a2amd_batch_info last_batch = {};	// a2amd_last_batch()
 	a2amd_noise_batch_info last_noise = {};	// a2amd_last_batch_noise()
 	uint32_t n_noise_standin = 0, n_noise_quiet = 0;	// upload(): noise voices given the stand-in run / left to k_leaf_noisepan
+	// wtosc (noise)-filter12-panmix: voices left to k_leaf_noisefiltpan this batch, and the number of such voices IN A BATCH
+	// from which the class has its quiet kernel (A2AMD_NZF_MIN; below it every one of them takes the stand-in run)
+	uint32_t n_noise_filt_quiet = 0;
+	int nzf_min = A2AMD_NZF_MIN_DEFAULT;
+	a2amd_noise_filter_batch_info last_noise_filter = {};	// a2amd_last_batch_noise_filter()
 
 	// bus memory allocator (units of int32)
 	size_t bus_stride_frames;

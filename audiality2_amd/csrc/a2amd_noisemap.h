@@ -1,5 +1,6 @@
 // a2amd_noisemap.h - one window of a settled noise oscillator in closed form, for the host and the device alike:
-// k_leaf_noisepan (a2amd_noisepan.hip) renders with it, a2amd_noise_window() (a2amd_host.cpp) exports it for tests.
+// k_leaf_noisepan (a2amd_noisepan.hip) and k_leaf_noisefiltpan (a2amd_noisefiltpan.hip) render with it, a2amd_noise_window()
+// and a2amd_noise_filter_window() (a2amd_host.cpp) export it for tests.
 //
 // wtosc_noise (wtosc.c:129-152) with wtosc_run_pitch returning early (:89-105): a window of n <= 64 frames that the
 // oscillator enters with phase ph, increment d, held sample h, the engine's generator word s0 in front of it.
@@ -57,3 +58,16 @@ NZM int32_t a2nm_value(uint32_t w) { return (int32_t)((w * (w >> 16)) >> 16) - 3
 
 // wtosc.c:148: the held sample at the oscillator's amplitude
 NZM int32_t a2nm_out(int32_t x, int32_t avalue) { return (int32_t)((uint32_t)x * (uint32_t)(avalue >> 10)) >> 6; }
+
+// One step of filter12 at rest (f12_process, filter12.c:98-117) in the formula of filt_step (a2amd_filt.h), which the
+// device runs lane = voice: x5 = the input >> 5, qq = q.value >> 12, ff = f1 >> 12; every sum and product wraps.
+NZM int32_t a2nm_filt(int32_t x5, int32_t qq, int32_t ff, int32_t lp, int32_t bp, int32_t hp, int32_t *d1, int32_t *d2)
+{
+	const int32_t d1s = *d1 >> 4;
+	const int32_t l = (int32_t)((uint32_t)*d2 + (uint32_t)((int32_t)((uint32_t)ff * (uint32_t)d1s) >> 8));
+	const int32_t h = (int32_t)((uint32_t)x5 - (uint32_t)l - (uint32_t)((int32_t)((uint32_t)qq * (uint32_t)d1s) >> 8));
+	const int32_t b = (int32_t)((uint32_t)((int32_t)((uint32_t)ff * (uint32_t)(h >> 4)) >> 8) + (uint32_t)*d1);
+	*d1 = b;
+	*d2 = l;
+	return (int32_t)((uint32_t)l * (uint32_t)lp + (uint32_t)b * (uint32_t)bp + (uint32_t)h * (uint32_t)hp) >> 3;
+}

@@ -454,6 +454,15 @@ int a2amd_last_batch_noise(const a2amd_ctx *c, a2amd_noise_batch_info *out)
 	return A2AMD_OK;
 }
 
+int a2amd_last_batch_noise_filter(const a2amd_ctx *c, a2amd_noise_filter_batch_info *out)
+{
+	if(!c || !out)
+		return A2AMD_EINVAL;
+	*out = c->last_noise_filter;
+	out->min_voices = (uint32_t)c->nzf_min;
+	return A2AMD_OK;
+}
+
 int a2amd_set_profiling(a2amd_ctx *c, int on)
 {
 	if(int r = drain_events(c))

@@ -197,10 +197,11 @@ void sync_voice_mirror(a2amd_ctx *c, int vi)
 	m.own_nch = v.own_nch;
 }
 
-// what the wavetable leaf kernels play: mip-mapped waves, nothing, and - k_leaf_recs / the window kernels and k_leaf_noisepan
-// only - noise.  The quiet kernels of the wavetable classes never see a noise oscillator: every window the engine calls for
-// carries an R_NOISESEED record, and a voice whose noise windows are seeded on the device (a2amd_fragment_repeat_noise) is
-// either k_leaf_noisepan's or given a stand-in record run by upload() in a batch in which it has no record of its own.
+// what the wavetable leaf kernels play: mip-mapped waves, nothing, and - k_leaf_recs / the window kernels, k_leaf_noisepan and
+// k_leaf_noisefiltpan only - noise.  The quiet kernels of the wavetable classes never see a noise oscillator: every window the
+// engine calls for carries an R_NOISESEED record, and a voice whose noise windows are seeded on the device
+// (a2amd_fragment_repeat_noise) is either k_leaf_noisepan's / k_leaf_noisefiltpan's or given a stand-in record run by
+// upload() in a batch in which it has no record of its own.
 
 // wtosc (mip-mapped wave playing) -> panmix 1->2 adding into the output bus
 bool is_oscpan_chain(const a2amd_ctx *c, const HVoice &v)
@@ -328,7 +329,7 @@ int upload(a2amd_ctx *c)
 	// end - records into their lists - and their states go up, a2amd_vm.cpp)
 	if(int r = vm_prepare_batch(c))
 		return r;
-	c->n_noise_standin = c->n_noise_quiet = 0;
+	c->n_noise_standin = c->n_noise_quiet = c->n_noise_filt_quiet = 0;
 	if(c->hosttiming) {
 		// (A2AMD_HOSTTIMING: why a batch did not take the quiet path - first reason that applies)
 		const int why = !c->blob_quiet ? 0 : !c->with_recs.empty() ? 1 : !c->prev_with_recs.empty() ? 2 :
@@ -611,17 +612,35 @@ int upload(a2amd_ctx *c)
 	// records) for any other chain.  The quiet kernels of the wavetable classes know no noise.
 	// (unlike a gliding voice, which the quiet kernels can take the slow way when its class is not known for sure -
 	// lists_dirty, mode_mix - a noise voice gets the run whatever its class: those kernels must never see one)
-	// The one exception is the class with a quiet kernel of its own, wtosc (noise) -> panmix (k_leaf_noisepan, round 7): a
-	// voice is left WITHOUT the run when its remembered class is CLS_NOISEPAN and still stands (a stale one may be any
-	// class once the lists are rebuilt below; one that stands comes out of a rebuild as it went in), its amplitude, volume
-	// and pan are at rest (moving_until, the test of the list above: the kernel renders settled voices only) and
-	// A2AMD_NOISE_QUIET is not 0.
-	// Invariant: a noise oscillator never stands in k_leaf_oscpan's list without a record - a noise-mode voice is classified
-	// CLS_NOISEPAN, never CLS_OSCPAN, and while a remembered CLS_OSCPAN is stale (a 'w' write to noise) it has the run - and a
-	// recordless noise voice is rendered by exactly one kernel, whether or not the lists are rebuilt in this upload():
-	// k_leaf_noisepan takes the voices of its segment whose run is empty, every other kernel those whose run is not.
+	// The exceptions are the two classes with a quiet kernel of their own, wtosc (noise) -> panmix (k_leaf_noisepan, round 7)
+	// and wtosc (noise) -> filter12 -> panmix (k_leaf_noisefiltpan): a voice is left WITHOUT the run when its remembered class
+	// is CLS_NOISEPAN / CLS_NOISEFILTPAN and still stands (a stale one may be any class once the lists are rebuilt below; one
+	// that stands comes out of a rebuild as it went in), its amplitude, q, volume and pan are at rest (moving_until, the test
+	// of the list above: the kernels render settled voices only; a cutoff ramp cannot be in flight in a device-seeded
+	// stretch, a2amd_fragment_repeat_noise refuses it) and A2AMD_NOISE_QUIET is not 0.
+	// The filter class moreover only from nzf_min such voices IN THIS BATCH on (A2AMD_NZF_MIN, a2amd_host.h): they are
+	// counted first - from the remembered classes, so the count is the same whether or not the lists are rebuilt below -
+	// and below the threshold every one of them takes the run, as before the class had a kernel.
+	// Invariant, for both classes: a noise oscillator never stands in k_leaf_oscpan's / k_leaf_oscfiltpan's list without a
+	// record - a noise-mode voice is classified CLS_NOISEPAN / CLS_NOISEFILTPAN, never CLS_OSCPAN / CLS_OSCFILTPAN, and while
+	// a remembered CLS_OSCPAN / CLS_OSCFILTPAN is stale (a 'w' write to noise) it has the run - and a recordless noise voice
+	// is rendered by exactly one kernel, whether or not the lists are rebuilt in this upload(): runs[v].count == 0 <=> the
+	// quiet kernel of its segment - k_leaf_noisepan and k_leaf_noisefiltpan take the voices of their segments whose run is
+	// empty, every other kernel those whose run is not.
 	{
 		const uint64_t t0 = c->vm.batch_time;
+		// a voice a quiet noise kernel may take: which of the two classes (0: neither)
+		auto quiet_cls = [&](const HVoice &v) {
+			return c->noise_quiet && (v.cls == CLS_NOISEPAN || v.cls == CLS_NOISEFILTPAN) && !v.cls_stale && v.resolved &&
+					v.vm < 0 && v.recs.empty() && (v.live || v.dying) && v.moving_until <= t0 ? v.cls : 0;
+		};
+		// (a voice of either class has one oscillator: it is met once)
+		int nfilt = 0;
+		for(const A2DNoiseOsc &o : c->noise_osc) {
+			const HVoice &v = c->voices[c->units[o.unit].voice];
+			nfilt += v.noise_run != c->serial_base && v.moving_run != c->serial_base && quiet_cls(v) == CLS_NOISEFILTPAN;
+		}
+		const bool filt_quiet = nfilt >= c->nzf_min;
 		for(const A2DNoiseOsc &o : c->noise_osc) {
 			const int vi = c->units[o.unit].voice;
 			HVoice &v = c->voices[vi];
@@ -630,12 +649,14 @@ int upload(a2amd_ctx *c)
 			v.noise_run = c->serial_base;
 			if(!v.recs.empty() || !(v.live || v.dying))
 				continue;
-			const bool quiet = c->noise_quiet && v.cls == CLS_NOISEPAN && !v.cls_stale && v.resolved && v.vm < 0 &&
-					v.moving_until <= t0;
+			const int qc = quiet_cls(v);
+			const bool quiet = qc == CLS_NOISEPAN || (qc == CLS_NOISEFILTPAN && filt_quiet);
 			if(v.moving_run != c->serial_base && !quiet)
 				give_stand_in(vi);
 			if(v.moving_run == c->serial_base)
 				++c->n_noise_standin;
+			else if(qc == CLS_NOISEFILTPAN)
+				++c->n_noise_filt_quiet;
 			else
 				++c->n_noise_quiet;
 		}
@@ -701,7 +722,9 @@ int upload(a2amd_ctx *c)
 								// (the noise generator: a class of its own, k_leaf_noisepan - a 'w' write marks the class stale)
 								(c->noise_quiet && c->units[v.unit[0]].mode == A2D_OSC_NOISE ? CLS_NOISEPAN : CLS_OSCPAN) :
 							!(c->no_fast & 8) && is_osc2pan_chain(c, v) ? CLS_OSC2PAN :
-							!(c->no_fast & 2) && is_oscfiltpan_chain(c, v) ? CLS_OSCFILTPAN :
+							!(c->no_fast & 2) && is_oscfiltpan_chain(c, v) ?
+								// (likewise: k_leaf_noisefiltpan's, whatever their number - upload() counts them batch by batch)
+								(c->noise_quiet && c->units[v.unit[0]].mode == A2D_OSC_NOISE ? CLS_NOISEFILTPAN : CLS_OSCFILTPAN) :
 							// (no quiet kernel of its own: k_leaf_recs renders it, records or not - unless an
 							// oscillator leaves the mip-mapped waves somewhere in this batch)
 							!(c->no_fast & 128) && !v.mode_mix && is_osc2filtpan_chain(c, v) ? CLS_OSC2FILTPAN :
@@ -771,7 +794,8 @@ int upload(a2amd_ctx *c)
 					fprintf(stderr, "REC %lld v%d f%u op%u u%u r%u val %d dur %u start %u\n", c->serial_base, vi,
 							A2D_RFRAG(r.head), A2D_ROP(r.head), A2D_RUNIT(r.head), A2D_RREG(r.head), r.value, r.dur, r.start);
 			// (fm-panmix voices execute their own records in k_leaf_fmpan)
-			if(v.cls == CLS_OSCPAN || v.cls == CLS_NOISEPAN || v.cls == CLS_OSCFILTPAN || v.cls == CLS_OSC2PAN || v.cls == CLS_OSC2FILTPAN) {
+			if(v.cls == CLS_OSCPAN || v.cls == CLS_NOISEPAN || v.cls == CLS_OSCFILTPAN || v.cls == CLS_NOISEFILTPAN || v.cls == CLS_OSC2PAN ||
+					v.cls == CLS_OSC2FILTPAN) {
 				// (close_fragment's R_NOP is the one other record k_leaf_recs takes - as nothing)
 				const bool ok = !no_recs_kernel && !v.mode_mix && !v.fancy_recs;
 				// (on a list already, whichever: a voice the general kernel takes - DYN_REST - must not be put on DYN_FILT2 as
@@ -1512,6 +1536,16 @@ static int launch_leaves(a2amd_ctx *c, LeafPass &lp)
 		++c->stats.launches;
 		c->last_noise.quiet_launched = 1;
 	}
+	// wtosc (noise) -> filter12 -> panmix without records, likewise.  A workgroup keeps its voices - at most 64, the lanes of
+	// its filter wavefront - for the whole batch: spread first (one workgroup per CU, 256), then fill.
+	const ListRange noisefilt = c->leaf[LEAF_NOISEFILTPAN];
+	if(noisefilt.count && !c->noise_st.empty() && c->n_noise_filt_quiet) {
+		const int vpg = getenv("A2AMD_NZFVPG") ? atoi(getenv("A2AMD_NZFVPG")) : (noisefilt.count + 255) / 256;
+		if(a2d_launch_leaf_noisefiltpan(c->d_params, c->hparams, list + noisefilt.first, noisefilt.count, vpg, c->stream))
+			return c->fail(A2AMD_EHIP, "noise filter leaf launch failed: %s", hipGetErrorString(hipGetLastError()));
+		++c->stats.launches;
+		c->last_noise_filter.quiet_launched = 1;
+	}
 	const ListRange osc2pan = c->leaf[LEAF_OSC2PAN];
 	if(osc2pan.count && none_quiet(1, osc2pan.count))
 		++c->vm.quiet_skipped;
@@ -1690,6 +1724,10 @@ static int issue_leaf_phase(a2amd_ctx *c, bool consume, bool consume_sub, hipEve
 	c->last_noise.class_voices = (uint32_t)c->leaf[LEAF_NOISEPAN].count;
 	c->last_noise.standin_voices = c->n_noise_standin;
 	c->last_noise.quiet_voices = c->n_noise_quiet;
+	c->last_noise_filter = a2amd_noise_filter_batch_info{};
+	c->last_noise_filter.class_voices = (uint32_t)c->leaf[LEAF_NOISEFILTPAN].count;
+	c->last_noise_filter.quiet_voices = c->n_noise_filt_quiet;
+	c->last_noise_filter.min_voices = (uint32_t)c->nzf_min;
 	// The batch's other leaf kernels - the quiet kernels of the classes, the records kernels where the window kernels
 	// are not in use, the general kernel - as a block that runs once: normally behind the window kernels, and
 	// (round 6) from INSIDE issue_windows, between its control passes and its render passes, when a speculative VM

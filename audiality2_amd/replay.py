@@ -90,6 +90,15 @@ class a2amd_noise_batch_info(C.Structure):
         return "noise_batch_info(" + ", ".join(f"{n}={getattr(self, n)}" for n, _ in self._fields_) + ")"
 
 
+class a2amd_noise_filter_batch_info(C.Structure):
+    """include/a2amd_noisefilt.h: who rendered the noise-filter voices of the most recent batch"""
+    _fields_ = [("quiet_launched", C.c_uint32), ("quiet_voices", C.c_uint32),
+                ("class_voices", C.c_uint32), ("min_voices", C.c_uint32)]
+
+    def __repr__(self):
+        return "noise_filter_batch_info(" + ", ".join(f"{n}={getattr(self, n)}" for n, _ in self._fields_) + ")"
+
+
 class Backend:
     """Thin ctypes veneer over one implementation of the call protocol."""
 
@@ -133,6 +142,9 @@ class Backend:
         self._last_batch_noise = None
         if hasattr(lib, prefix + "last_batch_noise"):
             self._last_batch_noise = fn("last_batch_noise", i32, vp, C.POINTER(a2amd_noise_batch_info))
+        self._last_batch_noise_filter = None
+        if hasattr(lib, prefix + "last_batch_noise_filter"):
+            self._last_batch_noise_filter = fn("last_batch_noise_filter", i32, vp, C.POINTER(a2amd_noise_filter_batch_info))
         # waves built on the device from what it rendered (the product library only)
         self.has_capture = hasattr(lib, prefix + "wave_upload_captured_post")
         if self.has_capture:
@@ -233,6 +245,15 @@ class Backend:
             raise RuntimeError(f"this library has no {self.prefix}last_batch_noise")
         bi = a2amd_noise_batch_info()
         self._chk(self._last_batch_noise(self.ctx, C.byref(bi)), "last_batch_noise")
+        return bi
+
+    def last_batch_noise_filter(self):
+        """a2amd_last_batch_noise_filter: whether k_leaf_noisefiltpan was launched for the most recent batch, the voices
+        left to it, the voices of its launch class, the threshold in force (A2AMD_NZF_MIN)"""
+        if self._last_batch_noise_filter is None:
+            raise RuntimeError(f"this library has no {self.prefix}last_batch_noise_filter")
+        bi = a2amd_noise_filter_batch_info()
+        self._chk(self._last_batch_noise_filter(self.ctx, C.byref(bi)), "last_batch_noise_filter")
         return bi
 
     def unit_init(self, voice_key, kind, flags, nin, nout, wired, transpose=0, wakefrac=0):

@@ -285,17 +285,26 @@ class Scene:
                 if k % 8 == 3:
                     be.unit_write(fm, 1, p + fix(0.5), 0, 1500 << 8)      # pitch glide
                 be.unit_write(fm, 0, (k * 2654435761) % 65536)            # phase
-            elif chain in ("noise-pan", "noise-filter-pan"):
+            elif chain in ("noise-pan", "noise-filter-pan", "noisefilt-pan"):
                 # wtosc playing the noise generator (the engine's 'noise' wave).  Pitches from -2 to +8 octaves:
                 # a phase increment of 1 << 23 - a draw in every frame - is reached 6.5 octaves up at 48 kHz, so
                 # five voices of 31 draw in every frame and the others hold a draw for several (wtosc.c:140-145)
                 p = fix(((k * 7) % 31) / 3.0 - 2.0)
                 units = [be.unit_init(key, K_WTOSC, 0, 0, 1, 0)]
-                if chain == "noise-filter-pan":
+                if chain == "noisefilt-pan":
+                    # wtosc (noise); filter12; panmix as a2_PopulateVoice leaves it - the whole chain before the first
+                    # write: ONE voice of the launch class wtosc-filter12-panmix (hats, snares, cymbals)
                     units.append(be.unit_init(key, K_FILTER12, 0, 1, 1, 0))
+                    units.append(be.unit_init(key, K_PANMIX, PROCADD, 1, 2, 1))
+                if chain != "noise-pan":
+                    # ("noise-filter-pan" writes between its Initialize calls, which ends the voice being built: to a backend
+                    # its panmix is a voice of its own behind a voice wtosc; filter12 - two voices of the general kernel)
+                    if chain == "noise-filter-pan":
+                        units.append(be.unit_init(key, K_FILTER12, 0, 1, 1, 0))
                     be.unit_write(units[1], 0, fix(1.0 + (k % 5) * 0.5))  # cutoff
                     be.unit_write(units[1], 1, fix(4.0))                  # q
-                units.append(be.unit_init(key, K_PANMIX, PROCADD, 1, 2, 1))
+                if chain != "noisefilt-pan":
+                    units.append(be.unit_init(key, K_PANMIX, PROCADD, 1, 2, 1))
                 oscs, pan = [], units[-1]
                 be.unit_write(units[0], 0, self.noise_id)
                 be.unit_write(units[0], 1, p)

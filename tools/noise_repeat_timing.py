@@ -6,12 +6,16 @@ HIP-event time.  LIB: the liba2amd.so to measure (two builds interleaved: one pr
 Mode repeat_only: one fragment walked and rendered ahead of everything, then every batch 64 fragments through
 a2amd_fragment_repeat_noise and nothing else - no noise voice has a record of its own, which is where k_leaf_noisepan
 renders them (a library from before it: the stand-in record and the window kernels).
+CHAIN: noise-pan (default) or noisefilt-pan - synth's wtosc (noise); filter12; panmix voice, k_leaf_noisefiltpan's (from
+A2AMD_NZF_MIN of them on); VOICES: how many (default 16 384).
 
-usage: tools/noise_repeat_timing.py LIB calls|repeat|repeat_only [batches] [warm-up batches]  -> one JSON line"""
+usage: tools/noise_repeat_timing.py LIB calls|repeat|repeat_only [batches] [warm-up batches] [CHAIN] [VOICES]  -> one JSON line"""
 import ctypes, json, os, sys, time
 lib, mode = sys.argv[1], sys.argv[2]
 batches = int(sys.argv[3]) if len(sys.argv) > 3 else 8
 warm = int(sys.argv[4]) if len(sys.argv) > 4 else 3
+chain = sys.argv[5] if len(sys.argv) > 5 else "noise-pan"
+nvoices = int(sys.argv[6]) if len(sys.argv) > 6 else 16384
 os.environ["A2AMD_LIB"] = lib
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -30,7 +34,7 @@ be = audiality2_amd.open_backend(max_batch=64)
 be.noise.value = 0x2545F491
 sc = synth.Scene(be)
 sc.root()
-sc.add_voices(16384, "noise-pan", total=256)
+sc.add_voices(nvoices, chain, total=256)
 heads = [u for u in sc.leaves]
 
 
@@ -70,8 +74,10 @@ st = Stats()
 be.lib.a2amd_get_stats(be.ctx, ctypes.byref(st))
 # (who rendered the last batch's noise voices, where the library says)
 quiet = be.last_batch_noise() if hasattr(be.lib, "a2amd_last_batch_noise") else None
+if chain == "noisefilt-pan":
+    quiet = be.last_batch_noise_filter() if hasattr(be.lib, "a2amd_last_batch_noise_filter") else None
 rec = np.array(rows) * 1e3
-print(json.dumps({"lib": os.path.basename(os.path.dirname(lib)) + "/" + os.path.basename(lib), "mode": mode,
+print(json.dumps({"lib": os.path.basename(os.path.dirname(lib)) + "/" + os.path.basename(lib), "mode": mode, "chain": chain, "voices": nvoices,
                   "batches": batches, "record_ms_median": float(np.median(rec[:, 0])), "record_ms_min": float(rec[:, 0].min()),
                   "record_ms_max": float(rec[:, 0].max()), "render_call_ms_median": float(np.median(rec[:, 1])),
                   "render_call_ms_min": float(rec[:, 1].min()), "render_call_ms_max": float(rec[:, 1].max()),
