@@ -300,7 +300,7 @@ struct A2DCommitSet { A2DCommit c[2]; int n; };
 int a2d_launch_leaf_oscpan(const A2DParams *dparams, const A2DParams &hp, const int *dlist, int nlist,
 		int vpw, int ysplit, int *ustage, void *stream, void *event_after_main, A2DCommit *defer);
 int a2d_launch_bus_driver(const A2DParams *dparams, const int *dlist, int nlist, int nfrags, int consume,
-		const A2DCommitSet *commits, void *stream, int *master_host = nullptr);	// master_host: where the root stores the master bus (pinned host memory) instead of the bus memory
+		const A2DCommitSet *commits, void *stream, int *master_host = nullptr, int ramping = 0);	// ramping: the launch of the drivers still gliding (one workgroup each); master_host: where the root stores the master bus (pinned host memory) instead of the bus memory
 int a2d_launch_commit(const A2DParams &hp, const A2DCommit &cm, void *stream);
 // quiet "inline; fbdelay 2->2 ... ; fbdelay 2->2 >" voices (one workgroup each)
 int a2d_launch_bus_fbdchain(const A2DParams *dparams, const int *dlist, int nlist, int consume, void *stream);

@@ -2781,7 +2781,7 @@ void k_leaf_osc2filtpan(const A2DParams *__restrict__ pp, const int *__restrict_
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(256)
 void k_bus_driver(const A2DParams *__restrict__ pp, const int *__restrict__ list, int nlist, int consume,
-		A2DCommitSet commits, int *__restrict__ master_host)
+		A2DCommitSet commits, int *__restrict__ master_host, int ramping)
 {
 	__shared__ int fr[A2D_MAXBATCH][5];	// per fragment: vol, dvol, pan, dpan, clamp
 	const A2DParams &p = *pp;
@@ -2809,16 +2809,19 @@ void k_bus_driver(const A2DParams *__restrict__ pp, const int *__restrict__ list
 	Ramp vol = ramp_load(w + PW_VOL), pan = ramp_load(w + PW_PAN);
 	// Both rampers at rest (the usual case): the gains are the same for every
 	// fragment, the fragments are independent and the workgroups of this voice
-	// (blockIdx.y) split them.  Otherwise workgroup 0 steps the rampers through
-	// the batch first and renders it alone.
+	// (blockIdx.y) split them.  Otherwise one workgroup steps the rampers through
+	// the batch first and renders it alone - in a launch of its own (ramping,
+	// gridDim.y == 1, the drivers the host knows may glide): it stores the rampers'
+	// end state, which may be a settled one, into the words every workgroup of the
+	// voice decides by, so no workgroup of that launch may share the voice with
+	// another.  The launch over all drivers leaves an unsettled voice alone and
+	// writes no ramper: all its workgroups of a voice decide alike.
 	const bool settled = !(vol.timer | vol.delta | pan.timer | pan.delta) &&
 			vol.value == vol.target && pan.value == pan.target;
-	int fbeg = blockIdx.y * 4 + wv, fstep = gridDim.y * 4;
+	if(settled == (ramping != 0))
+		return;
+	const int fbeg = blockIdx.y * 4 + wv, fstep = gridDim.y * 4;
 	if(!settled) {
-		if(blockIdx.y)
-			return;
-		fbeg = wv;
-		fstep = 4;
 		if(threadIdx.x == 0) {
 			// panmix_process22's rampers (panmix.c:192-249)
 			for(int f = 0; f < p.nfrags; ++f) {
@@ -3608,10 +3611,18 @@ int a2d_launch_commit(const A2DParams &hp, const A2DCommit &cm, void *stream)
 }
 
 int a2d_launch_bus_driver(const A2DParams *dparams, const int *dlist, int nlist, int nfrags, int consume,
-		const A2DCommitSet *commits, void *stream, int *master_host)
+		const A2DCommitSet *commits, void *stream, int *master_host, int ramping)
 {
 	if(nlist <= 0)
 		return 0;
+	if(ramping) {
+		// the drivers still gliding: one workgroup each
+		A2DCommitSet none;
+		none.n = 0;
+		hipLaunchKernelGGL(k_bus_driver, dim3(nlist, 1), dim3(256), 0, (hipStream_t)stream, dparams, dlist, nlist, consume,
+				none, master_host, 1);
+		return (int)hipGetLastError();
+	}
 	A2DCommitSet cs;
 	cs.n = 0;
 	int extra = 0;
@@ -3623,6 +3634,6 @@ int a2d_launch_bus_driver(const A2DParams *dparams, const int *dlist, int nlist,
 			}
 	// grid.y: workgroups per voice, 4 fragments in flight each
 	hipLaunchKernelGGL(k_bus_driver, dim3(nlist + extra, nfrags >= 16 ? 16 : (nfrags + 3) / 4), dim3(256), 0,
-			(hipStream_t)stream, dparams, dlist, nlist, consume, cs, master_host);
+			(hipStream_t)stream, dparams, dlist, nlist, consume, cs, master_host, 0);
 	return (int)hipGetLastError();
 }

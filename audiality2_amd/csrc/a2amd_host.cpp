@@ -938,8 +938,13 @@ int a2amd_unit_write(a2amd_ctx *c, int ui, int reg, int value, unsigned start, u
 		return c->fail(A2AMD_ESTATE, "write to unit %d of a voice the device VM runs: a2amd_vm_recall() first", ui);
 	c->building = -1;
 	start &= 255;		// a2_VoiceControl, core.c:148
-	if(dur >= 256 && ((u.kind == A2AMD_WTOSC && (reg == 1 || reg == 2)) || u.kind == A2AMD_PANMIX ||
-			(u.kind == A2AMD_FILTER12 && reg == 1))) {
+	// (a bus owner's panmix: ANY write.  a2_SetRamper starts a ramp from start + dur >= 256 on, whatever dur is, and below
+	// that still leaves the timer set until the next window's a2_PrepareRamper: a write behind the voice's last window of
+	// a batch leaves the rampers unsettled for the next one, and k_bus_driver renders an unsettled driver only in its
+	// launch of the drivers listed here - a2amd_sched.cpp, DepthRange::ramp.  The leaf kernels step an unsettled voice
+	// that is not listed themselves.)
+	if((dur >= 256 && ((u.kind == A2AMD_WTOSC && (reg == 1 || reg == 2)) || u.kind == A2AMD_PANMIX ||
+			(u.kind == A2AMD_FILTER12 && reg == 1))) || (u.kind == A2AMD_PANMIX && c->voices[u.voice].inline_pos >= 0)) {
 		// a glide: the ramp lasts (start + dur) >> 8 frames from the frame the open window starts at (somewhere in
 		// the open fragment), then one more window settles the ramper (a2_PrepareRamper's first branch,
 		// a2_dsp.h:131-135; wtosc's extra pitch update, wtosc.c:99-100) - a margin of three fragments covers both

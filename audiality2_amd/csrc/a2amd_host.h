@@ -232,7 +232,9 @@ struct ListRange { int first = 0, count = 0; };
 enum { LEAF_OSCPAN = 0, LEAF_OSC2PAN, LEAF_OSCFILTPAN, LEAF_FMPAN, LEAF_GENERIC, LEAF_OSC2FILTPAN, LEAF_NOISEPAN, LEAF_NOISEFILTPAN,
 	LEAF_N };
 enum { DYN_OSC1 = 0, DYN_OSC2, DYN_FILT, DYN_FILT2, DYN_REST, DYN_N };
-struct DepthRange { ListRange driver, fbd, generic, dyn; };
+// (ramp: in d_dyn, this batch's driver chains without records whose volume or pan may still glide - k_bus_driver's
+// second launch of the depth, one workgroup a voice)
+struct DepthRange { ListRange driver, fbd, generic, dyn, ramp; };
 // a launch class's leaf segment and, where k_leaf_recs knows the class, its exception list (-1: a bus owner), in CLS_* order
 static const struct { int8_t leaf, dyn; } cls_lists[CLS_N] = {
 	{ LEAF_GENERIC, DYN_REST }, { LEAF_OSCPAN, DYN_OSC1 }, { LEAF_OSCFILTPAN, DYN_FILT }, { -1, -1 }, { -1, -1 },
@@ -514,6 +516,10 @@ struct a2amd_ctx {
 	uint32_t n_noise_filt_quiet = 0;
 	int nzf_min = A2AMD_NZF_MIN_DEFAULT;
 	a2amd_noise_filter_batch_info last_noise_filter = {};	// a2amd_last_batch_noise_filter()
+	// a2amd_last_batch_buses(): upload() fills in who renders the bus owners, launch_depth() what it was told to
+	// consume (a graph: gconsume, as at its capture); master_direct is the context's own flag
+	a2amd_bus_info last_bus = {};
+	uint32_t n_bus_windows_dropped = 0;	// upload(): driver chains at rest whose windows-only records were dropped
 
 	// bus memory allocator (units of int32)
 	size_t bus_stride_frames;
@@ -580,6 +586,7 @@ struct a2amd_ctx {
 	hipGraphExec_t gexec[12] = {};
 	const int32_t *gdst[12] = {};
 	bool gdirect[12] = {};		// (the captured root launch stored there)
+	uint32_t gconsume[12] = {};	// (what the captured bus launches were told to consume: a2amd_bus_info)
 	// channel 0 of what this context renders, kept on the device (a2amd_capture_begin)
 	struct Capture { int32_t *d = nullptr; size_t cap = 0, n = 0; bool on = false; uint32_t *d_fragpos = nullptr; } capture;
 	DevBuf<uint32_t> d_wavepost;	// a2amd_wave_upload_captured_post: the gain word and the chunks' peaks (a2amd_wavepost.hip)

@@ -164,6 +164,7 @@ int a2amd_render(a2amd_ctx *c, unsigned phases, int32_t *const *out, unsigned ca
 						return r;
 				HIPCHK(c, hipGraphLaunch(c->gexec[gi], c->stream));
 				c->master_direct = c->gdirect[gi];	// (what the captured launch did)
+				c->last_bus.consume = c->gconsume[gi];
 				if(c->hosttiming)
 					dbg_counters()[5] += 1;
 				if(slot == 1)
@@ -460,6 +461,15 @@ int a2amd_last_batch_noise_filter(const a2amd_ctx *c, a2amd_noise_filter_batch_i
 		return A2AMD_EINVAL;
 	*out = c->last_noise_filter;
 	out->min_voices = (uint32_t)c->nzf_min;
+	return A2AMD_OK;
+}
+
+int a2amd_last_batch_buses(const a2amd_ctx *c, a2amd_bus_info *out)
+{
+	if(!c || !out)
+		return A2AMD_EINVAL;
+	*out = c->last_bus;
+	out->master_direct = c->master_direct;
 	return A2AMD_OK;
 }
 

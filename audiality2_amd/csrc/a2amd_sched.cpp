@@ -330,6 +330,9 @@ int upload(a2amd_ctx *c)
 	if(int r = vm_prepare_batch(c))
 		return r;
 	c->n_noise_standin = c->n_noise_quiet = c->n_noise_filt_quiet = 0;
+	// (a2amd_last_batch_buses(): the lists of a quiet batch are the last upload's - nobody ramps, nothing is dropped)
+	c->n_bus_windows_dropped = 0;
+	c->last_bus.driver_ramping = c->last_bus.driver_windows_dropped = 0;
 	if(c->hosttiming) {
 		// (A2AMD_HOSTTIMING: why a batch did not take the quiet path - first reason that applies)
 		const int why = !c->blob_quiet ? 0 : !c->with_recs.empty() ? 1 : !c->prev_with_recs.empty() ? 2 :
@@ -546,6 +549,7 @@ int upload(a2amd_ctx *c)
 					break;
 				}
 			if(only_windows) {
+				++c->n_bus_windows_dropped;
 				v.recs.clear();
 				v.listed_recs = false;
 				continue;
@@ -855,6 +859,34 @@ int upload(a2amd_ctx *c)
 			if(!dyn_bus[d].empty())
 				c->consume_ok = false;	// a bus owner carries records: the general kernel renders it
 		}
+		// a2amd_last_batch_buses(): the bus owners by the kernel that renders them this batch.  k_bus_driver and
+		// k_bus_fbdchain leave a listed voice whose run is not empty to the general kernel (the depth's exception list).
+		a2amd_bus_info &bi = c->last_bus;
+		bi = a2amd_bus_info{};
+		bi.driver_windows_dropped = c->n_bus_windows_dropped;
+		// The drivers among them whose rampers may not be at rest (HVoice::moving_until: a2amd_unit_write sets it for every
+		// write to a bus owner's panmix, gliding or not - nothing else leaves these rampers unsettled: the host's records
+		// alone write them, the device VM adopts no bus owner) are listed once more, for k_bus_driver's launch of one
+		// workgroup a voice: the launch over all drivers leaves an unsettled one alone.
+		std::vector<int> ramp;
+		for(size_t d = 0; d < c->depth_ranges.size(); ++d) {
+			DepthRange &r = c->depth_ranges[d];
+			ramp.clear();
+			for(int k = 0; k < r.driver.count; ++k) {
+				const int vi = c->list_all[r.driver.first + k];
+				const HVoice &v = c->voices[vi];
+				if(!v.recs.empty())
+					continue;
+				++bi.driver_voices;
+				if(v.moving_until > c->vm.batch_time)
+					ramp.push_back(vi);
+			}
+			bi.driver_ramping += (uint32_t)ramp.size();
+			r.ramp = append_range(dyn_all, ramp);
+			for(int k = 0; k < r.fbd.count; ++k)
+				bi.fbd_voices += c->voices[c->list_all[r.fbd.first + k]].recs.empty();
+			bi.generic_voices += (uint32_t)(r.generic.count + r.dyn.count);
+		}
 	}
 
 	A2DParams p;
@@ -974,6 +1006,7 @@ void pick_fast_shape(int n, int nfrags, int *vpw, int *ysplit, int ymax = 32)
 int launch_depth(a2amd_ctx *c, int d, int consume, A2DCommitSet *pend)	// consume: 1 zero what is read, 2 root stores the master bus
 {
 	const DepthRange &r = c->depth_ranges[d];
+	c->last_bus.consume = (uint32_t)consume;	// (a2amd_last_batch_buses(): the last launch is the one nearest the root)
 	if(r.driver.count) {
 		// (state commits the time-sliced leaf kernels left behind ride along)
 		// (the root, a plain driver chain that stores the master bus: into the host's buffer where asked)
@@ -988,6 +1021,13 @@ int launch_depth(a2amd_ctx *c, int d, int consume, A2DCommitSet *pend)	// consum
 			return c->fail(A2AMD_EHIP, "bus driver launch failed: %s", hipGetErrorString(hipGetLastError()));
 		pend->n = 0;
 		++c->stats.launches;
+		// ... and those of them that may still glide, one workgroup each (upload(): DepthRange::ramp)
+		if(r.ramp.count) {
+			if(a2d_launch_bus_driver(c->d_params, c->d_dyn + r.ramp.first, r.ramp.count, c->nfrags, consume,
+					nullptr, c->stream, direct ? c->master_dst : nullptr, 1))
+				return c->fail(A2AMD_EHIP, "bus driver launch failed: %s", hipGetErrorString(hipGetLastError()));
+			++c->stats.launches;
+		}
 	}
 	if(r.fbd.count) {
 		if(a2d_launch_bus_fbdchain(c->d_params, c->d_list.d + r.fbd.first, r.fbd.count, consume & 1, c->stream))
@@ -1889,6 +1929,7 @@ int build_graph(a2amd_ctx *c, int slot, int steps, unsigned phases)
 		return c->fail(A2AMD_EHIP, "hipGraphInstantiate: %s", hipGetErrorString(e));
 	c->gdst[slot] = c->master_dst;
 	c->gdirect[slot] = c->master_direct;
+	c->gconsume[slot] = c->last_bus.consume;
 	return 0;
 }
 

@@ -99,6 +99,15 @@ class a2amd_noise_filter_batch_info(C.Structure):
         return "noise_filter_batch_info(" + ", ".join(f"{n}={getattr(self, n)}" for n, _ in self._fields_) + ")"
 
 
+class a2amd_bus_info(C.Structure):
+    """include/a2amd_bus.h: who rendered the bus owners - the root and the group voices - of the most recent batch"""
+    _fields_ = [(n, C.c_uint32) for n in ("driver_voices", "driver_ramping", "driver_windows_dropped", "fbd_voices",
+                                          "generic_voices", "consume", "master_direct")]
+
+    def __repr__(self):
+        return "bus_info(" + ", ".join(f"{n}={getattr(self, n)}" for n, _ in self._fields_) + ")"
+
+
 class Backend:
     """Thin ctypes veneer over one implementation of the call protocol."""
 
@@ -145,6 +154,9 @@ class Backend:
         self._last_batch_noise_filter = None
         if hasattr(lib, prefix + "last_batch_noise_filter"):
             self._last_batch_noise_filter = fn("last_batch_noise_filter", i32, vp, C.POINTER(a2amd_noise_filter_batch_info))
+        self._last_batch_buses = None
+        if hasattr(lib, prefix + "last_batch_buses"):
+            self._last_batch_buses = fn("last_batch_buses", i32, vp, C.POINTER(a2amd_bus_info))
         # waves built on the device from what it rendered (the product library only)
         self.has_capture = hasattr(lib, prefix + "wave_upload_captured_post")
         if self.has_capture:
@@ -254,6 +266,16 @@ class Backend:
             raise RuntimeError(f"this library has no {self.prefix}last_batch_noise_filter")
         bi = a2amd_noise_filter_batch_info()
         self._chk(self._last_batch_noise_filter(self.ctx, C.byref(bi)), "last_batch_noise_filter")
+        return bi
+
+    def last_batch_buses(self):
+        """a2amd_last_batch_buses: the bus owners of the most recent batch by the kernel that rendered them - k_bus_driver
+        (and how many of those ramping, how many with their cut windows dropped), k_bus_fbdchain, the general kernel -
+        what the bus launches were told to consume, whether the root stored into the host's buffer"""
+        if self._last_batch_buses is None:
+            raise RuntimeError(f"this library has no {self.prefix}last_batch_buses")
+        bi = a2amd_bus_info()
+        self._chk(self._last_batch_buses(self.ctx, C.byref(bi)), "last_batch_buses")
         return bi
 
     def unit_init(self, voice_key, kind, flags, nin, nout, wired, transpose=0, wakefrac=0):

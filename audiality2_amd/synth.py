@@ -193,28 +193,50 @@ class Scene:
     FMTEST4 = (((631.25, 756.25, 1003.75), (0.03, 0.05, 0.05)),
                ((868.75, 1126.25, 1378.75), (0.03, 0.05, 0.05)))
 
-    def add_group(self, fb=(63.1, 75.6, 100.4), gains=(0.3, 0.25, 0.25), preset=None):
+    def add_group(self, fb=(63.1, 75.6, 100.4), gains=(0.3, 0.25, 0.25), preset=None, delays=2, mid_add=False,
+                  parent=None):
         """inline 0 *; fbdelay * *; fbdelay * >   (benchmark/fmtest4.a2s shape);
-        preset="fmtest4": that song's own delay times and gains (BASELINE configs[3])"""
+        preset="fmtest4": that song's own delay times and gains (BASELINE configs[3]).
+        delays: fbdelay units in the chain, positions 0 .. delays - 1 - the last one wired and adding, the others in
+        place.  mid_add: which of the others add to what they read instead of replacing it - True: the ones between the
+        first and the last, positions 1 .. delays - 2; or the positions themselves, of 0 .. delays - 2.
+        fb / gains: one triple for every delay, or a list with a triple per delay (the preset has two).
+        parent: the bus or delay group that holds this one, instead of the root."""
+        if delays < 1:
+            raise ValueError("a delay group has at least one delay")
+        if preset == "fmtest4" and delays != len(self.FMTEST4):
+            raise ValueError(f"preset fmtest4 is a chain of {len(self.FMTEST4)} delays")
+        for what in (fb, gains):
+            if isinstance(what, list) and len(what) != delays:
+                raise ValueError(f"{len(what)} triples for {delays} delays")
+        if mid_add not in (True, False, None) and not set(mid_add) <= set(range(delays - 1)):
+            raise ValueError(f"mid_add positions are 0 .. {delays - 2}")
         be, k = self.be, self._key()
-        u = [be.unit_init(k, K_INLINE, 0, 0, 2, 0),
-             be.unit_init(k, K_FBDELAY, 0, 2, 2, 0),
-             be.unit_init(k, K_FBDELAY, PROCADD, 2, 2, 1)]
-        for i, d in enumerate((u[1], u[2])):
-            dfb, dg = self.FMTEST4[i] if preset == "fmtest4" else (fb, gains)
+        if mid_add is True:
+            mid_add = range(1, delays - 1)
+        adding = set(mid_add or ())
+        u = [be.unit_init(k, K_INLINE, 0, 0, 2, 0)]
+        u += [be.unit_init(k, K_FBDELAY, PROCADD if i in adding else 0, 2, 2, 0) for i in range(delays - 1)]
+        u.append(be.unit_init(k, K_FBDELAY, PROCADD, 2, 2, 1))
+        for i, d in enumerate(u[1:]):
+            if preset == "fmtest4":
+                dfb, dg = self.FMTEST4[i]
+            else:
+                dfb = fb[i] if isinstance(fb, list) else fb
+                dg = gains[i] if isinstance(gains, list) else gains
             for reg, ms in enumerate(dfb):
                 be.unit_write(d, reg, fix(ms))
             be.unit_write(d, 4, fix(dg[0]))
             be.unit_write(d, 5, fix(dg[1]))
             be.unit_write(d, 6, fix(dg[2]))
         g = dict(units=u, leaves=[])
-        self.groups.append(g)
+        (self.groups if parent is None else parent.setdefault("subs", [])).append(g)
         return g
 
     def add_bus_group(self, parent=None):
         """A group voice as a2_NewGroup makes it (src/interface.c:888: the program
         a2_groupdriver, audiality2.c:292-302): inline 0 *; panmix * *; xinsert * > -
-        under the root voice or under another such group."""
+        under the root voice, under another such group or under a delay group (add_group)."""
         be, k = self.be, self._key()
         u = [be.unit_init(k, K_INLINE, 0, 0, 2, 0),
              be.unit_init(k, K_PANMIX, 0, 2, 2, 0),

@@ -445,6 +445,8 @@ int  a2amd_last_batch(const a2amd_ctx *ctx, a2amd_batch_info *bi);
 #include "a2amd_noisepan.h"
 /* ... and of settled noise voices with a filter: a2amd_last_batch_noise_filter(), a2amd_noise_filter_window(). */
 #include "a2amd_noisefilt.h"
+/* Who rendered the bus owners - the root and the group voices - of the most recent batch: a2amd_last_batch_buses(). */
+#include "a2amd_bus.h"
 /* Rendered waves with "normalize" / "xfade", post-processed on the device: a2amd_wave_upload_captured_post(), a2amd_wavepost_host(). */
 #include "a2amd_wavepost.h"
 

@@ -1624,11 +1624,13 @@ def test_config3_full_size_is_linear_in_the_voice_subsets():
 
 @pytest.mark.parametrize("batch", [16, 64, 256])
 def test_delay_chain_kernel_rounds_match_oracle(oracle_lib, batch):
-    """k_bus_fbdchain: group voices inline->fbdelay->fbdelay with taps of 1.4 .. 29
-    fragments (rounds of 1, 3 and 9 fragments, several rounds per batch), one chain of
-    a single delay, one of three, one with a tap shorter than a fragment (general
-    kernel), delay times rewritten half way; the frame-parallel rounds must give what
-    the oracle's sample-by-sample loop gives."""
+    """k_bus_fbdchain: five group voices inline->fbdelay->fbdelay - every chain has exactly
+    two delays - with taps of 1.4 .. 29 fragments (rounds of 1, 3 and 9 fragments, several
+    rounds per batch) and fmtest4's (one round), one with a tap shorter than a fragment
+    (general kernel), delay times rewritten half way; the frame-parallel rounds must give
+    what the oracle's sample-by-sample loop gives.  Chains of one, three, four and five
+    delays, an adding middle delay and the taps at the edges of the class are in
+    tests/test_gpu_bus_paths.py."""
     outs = []
     for be in (make_gpu(max_batch=batch), make_oracle(oracle_lib)):
         sc = synth.Scene(be)

@@ -32,6 +32,9 @@ def test_library_exports_every_declared_symbol(gpu_lib):
     assert "a2amd_vm_adopt" in vm and "a2amd_vm_recall" in vm and "a2amd_vm_analyze" in vm
     for s in vm:
         assert hasattr(gpu_lib, s), f"liba2amd.so lacks {s}"
+    # who rendered the bus owners (tests/test_gpu_bus_paths.py)
+    assert declared_symbols("a2amd_bus.h") == ["a2amd_last_batch_buses"]
+    assert hasattr(gpu_lib, "a2amd_last_batch_buses")
 
 
 def test_walk_and_units_libraries_export_their_interface():
