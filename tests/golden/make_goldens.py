@@ -47,6 +47,8 @@ CASES = [
     ("fmtest4", f"{REF}/benchmark/fmtest4.a2s", "Song", 5 * 48000, []),
     # dc, waveshaper, dcblock, limiter
     ("fx", f"{A2S}/fx.a2s", "Main", 3 * 48000, ["0.1"]),
+    # gain-domain registers outside the musical range: negative, wrapping in 8.24, products that change sign
+    ("loud", f"{A2S}/loud.a2s", "Main", 2 * 48000, ["0.2"]),
     ("dctest", f"{REF}/benchmark/dctest.a2s", "Song", 5 * 48000, []),
     ("wstest", f"{REF}/benchmark/wstest.a2s", "Song", 5 * 48000, []),
     # the engine's own env unit (stays on the CPU) wired to replaced units
