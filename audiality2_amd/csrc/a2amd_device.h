@@ -215,6 +215,10 @@ struct A2DParams {
 					// the batch has device-seeded fragments (a2amd_fragment_repeat_noise; k_noise_seeds), or null
 	const int32_t  *nslot;		// [unit]: the oscillator's column of nseed + 1 (0: none; only read where nseed is set)
 	int32_t         nnoise;
+	const int32_t  *cutf;		// [fragment][ncut]: the coefficient behind a sweeping filter12's default window, or a negative word
+					// ("no ramp in this window"), where the batch has stretches with cutoff sweeps (k_cut_sweep), or null
+	const int32_t  *cslot;		// [unit]: the filter's column of cutf + 1 (0: none; only read where cutf is set)
+	int32_t         ncut;
 	int32_t         nfrags;
 	int32_t         samplerate;
 	int32_t         debug;		// A2AMD_DEBUG ablation bits (perf experiments only)
@@ -240,6 +244,61 @@ static inline __host__ __device__ bool a2d_noise_seed(const A2DParams &p, int f,
 	return true;
 }
 #endif
+
+// A filter12's default window - a fragment without records for its voice - takes what an R_F1RAMP record would have
+// brought from the batch's sweep table: true and *f1 = the coefficient behind the window when the cutoff ramper moved in
+// it (the caller sets f1next and ramp, as for the record), false - nothing changes - when it did not, or the filter has
+// no column.
+// Invariant (the host's: a2amd_fragment_repeat[_noise], upload()): a filter with cutoff_moving() meets a fragment
+// without records for its voice only inside a stretch that lists it - in a fragment walked by calls its Process call
+// leaves an R_F1RAMP record whenever the ramper moves, and a window in which it only snaps changes no coefficient - and
+// the quiet kernels, which never ask, never see its voice (upload() gives it the stand-in run).  Every cell of the table
+// is set to the marker and cslot is cleared for every batch that has a table, before the pass fills them in: a filter
+// without a column in THIS batch reads 0 here, and a column's cells outside the stretches that list it say "no ramp".
+#ifdef __HIPCC__
+static inline __host__ __device__ bool a2d_cut_coeff(const A2DParams &p, int f, int ui, int *f1)
+{
+	if(p.ncut <= 0)		// (set with cutf)
+		return false;
+#if defined(__HIP_DEVICE_COMPILE__)
+	// Through the CONSTANT address space (as a2amd_fast.hip's rec_issue): where the unit is the same in every lane these
+	// are scalar loads, which take no vector registers from the kernels that ask - the parameter block is the host's, the
+	// table and the columns are written by the sweep pass alone, before any kernel that reads them starts.
+	// (... and behind the asm: the table's pointers are read here, where a batch has sweeps, instead of riding through
+	// the callers' loops over fragments and voices in registers batch after batch)
+	typedef const __attribute__((address_space(4))) A2DParams *CP;
+	typedef const __attribute__((address_space(4))) int32_t *CI;
+	uintptr_t qa = (uintptr_t)&p;
+	asm volatile("" : "+s"(qa));
+	const CP q = (CP)qa;
+	const int ncut = q->ncut;
+	const int k = *((CI)(uintptr_t)q->cslot + ui);
+	if(k <= 0 || k > ncut)
+		return false;
+	const int v = *((CI)(uintptr_t)q->cutf + ((size_t)f * (size_t)ncut + (size_t)(k - 1)));
+#else
+	const int k = p.cslot[ui];
+	if(k <= 0 || k > p.ncut)
+		return false;
+	const int v = p.cutf[(size_t)f * (size_t)p.ncut + (size_t)(k - 1)];
+#endif
+	if(v < 0)
+		return false;
+	*f1 = v;
+	return true;
+}
+#endif
+
+// a2amd_cutsweep.hip: the sweep pass.  One sweeping filter12 of a stretch of repeated fragments: its cutoff ramper
+// {value, target, delta, timer} as the stretch finds it, its unit, its column of the batch's sweep table.
+struct A2DCutSweep { int32_t ramper[4]; int32_t unit, slot, pad[2]; };
+// k_cut_sweep: cutf[(f0 + j) * stride + list[k].slot] = the pitch argument of the coefficient behind window j of the
+// stretch (count fragments of 'frames' frames each), or the marker; cslot[list[k].unit] = slot + 1.  cutf holds 'words'
+// words, cslot nunits entries: an entry that would land outside is dropped.
+int a2d_launch_cut_sweep(const A2DCutSweep *list, int n, int f0, int count, unsigned frames, int32_t *cutf, int stride,
+		size_t words, int32_t *cslot, int nunits, void *stream);
+// k_cut_resolve, once per batch behind every stretch's k_cut_sweep: pitch arguments -> coefficients (f1tab: [32][65536])
+int a2d_launch_cut_resolve(int32_t *cutf, size_t words, const int32_t *f1tab, void *stream);
 
 // a2amd_noise.hip: the seed pass.  One settled noise oscillator of a stretch of device-seeded fragments, in walk order:
 // phase and increment as the stretch finds them, its unit, its column of the batch's seed table.

@@ -1571,6 +1571,13 @@ DEV void recs_body(const A2DParams *__restrict__ pp, const int *__restrict__ lis
 										os[o].seed = sd;
 								}
 						}
+						// (a sweeping filter's: what an R_F1RAMP record would have brought - the batch's sweep table)
+						if(FILT) {
+							int f1n = 0;
+							const bool hit = a2d_cut_coeff(p, f, rdl(uu[NOSC], v), &f1n);
+							fs.f1next = hit ? f1n : fs.f1next;
+							fs.ramp = hit ? 1 : fs.ramp;
+						}
 						window(0, n);
 					}
 				} else {

@@ -15,6 +15,7 @@
 // run first and each parent picks the sum up where its inline unit sits.
 #include "a2amd_host.h"
 #include "a2amd_noisemap.h"
+#include "a2amd_cutsweep.h"
 
 namespace a2h { thread_local char g_err[256] = ""; }
 
@@ -117,6 +118,7 @@ void a2amd_close(a2amd_ctx *c)
 	hipFree(c->d_voices.d); hipFree(c->d_vext.d); hipFree(c->d_udesc.d); hipFree(c->d_ustate.d); hipFree(c->d_ustage.d);
 	hipFree(c->d_vactive.d); hipFree(c->d_runs.d); hipFree(c->d_recs.d);
 	hipFree(c->d_nseed.d); hipFree(c->d_nslot.d);
+	hipFree(c->d_cutf.d); hipFree(c->d_cslot.d);
 	hipFree(c->d_win.d); hipFree(c->d_wext.d); hipFree(c->d_wscr.d); hipFree(c->d_wrc.d); hipFree(c->d_widx.d); hipFree(c->d_wtop);
 	if(c->h_wtop)
 		hipHostFree(c->h_wtop);
@@ -521,14 +523,105 @@ int a2amd_fragment_offset(a2amd_ctx *c, unsigned offset)
 	return A2AMD_OK;
 }
 
+// ---- cutoff sweeps in repeated fragments (a2amd_cutsweep.h, a2amd_cutsweep.hip) ----------
+namespace {
+// May a stretch of 'count' repeated fragments begin?  Only asked while a filter sweeps: what a2amd_fragment() would
+// refuse halfway through the stretch - the shadow rampers are stepped over all of it before the first fragment is made -
+// and a record made for a listed filter's voice since the last fragment was closed (a write between two stretches):
+// it belongs to the first fragment of this one, where the voice would then have records, no default window and no
+// coefficient from the table.  (A cutoff write with a duration makes no record: the ramper it set is listed as it is.)
+int sweep_stretch_check(a2amd_ctx *c, const char *who, unsigned frames, unsigned count)
+{
+	if(!frames || frames > A2D_FRAG)
+		return c->fail(A2AMD_EINVAL, "fragment of %u frames", frames);
+	if(!c->stack.empty())
+		return c->fail(A2AMD_ESTATE, "fragment inside an inline window");
+	if(c->uploaded)
+		return c->fail(A2AMD_ESTATE, "batch already uploaded; finish the render first");
+	if((uint64_t)c->nfrags + count > c->cfg.max_batch)
+		return c->fail(A2AMD_ESTATE, "more than max_batch=%u fragments without a render", c->cfg.max_batch);
+	for(int ui : c->sweeping) {
+		const HUnit &u = c->units[ui];
+		const HVoice &v = c->voices[u.voice];
+		if(v.vm >= 0)
+			continue;	// (the device VM's: it runs the ramper itself)
+		if(!c->frag_open && !v.recs.empty() && (int)A2D_RFRAG(v.recs.back().head) >= c->nfrags)
+			return c->fail(A2AMD_ESTATE, "%s: a write to the voice of filter %d, whose cutoff is sweeping, since the last "
+					"fragment was closed: walk a fragment by calls first", who, ui);
+	}
+	return 0;
+}
+
+// The stretch's list for the sweep pass - every live filter12 with cutoff_moving() on a voice the host drives, its
+// ramper as the stretch finds it, its column of the batch's table (kept over the stretches of one batch) - and the
+// host's shadow rampers stepped over the stretch with the pass's own arithmetic: integers only, no coefficient is
+// evaluated here.  The books are kept as a2amd_unit_process keeps them.
+void sweep_stretch(a2amd_ctx *c, unsigned frames, unsigned count)
+{
+	a2amd_ctx::CutStretch st = { c->nfrags, (int)count, frames, c->cut_list.size(), 0 };
+	// (a filter that arrives leaves c->sweeping: walked backwards, the swap-remove only moves entries already seen)
+	for(size_t i = c->sweeping.size(); i-- > 0;) {
+		const int ui = c->sweeping[i];
+		HUnit &u = c->units[ui];
+		HVoice &v = c->voices[u.voice];
+		if(v.vm >= 0)
+			continue;
+		if(u.cslot_batch != c->serial_base) {
+			u.cslot_batch = c->serial_base;
+			u.cslot = c->cut_slots++;
+		}
+		int32_t r[4] = { u.cutoff.value, u.cutoff.target, u.cutoff.delta, u.cutoff.timer };
+		const A2DCutSweep e = { { r[0], r[1], r[2], r[3] }, ui, u.cslot, { 0, 0 } };
+		c->cut_list.push_back(e);
+		const bool was = u.cutoff.timer != 0;
+		for(unsigned j = 0; j < count && a2cs_moving(r); ++j) {
+			int32_t pitch;
+			c->n_cut_windows += a2cs_step(r, (int)frames, &pitch);
+		}
+		u.cutoff.value = r[0];
+		u.cutoff.target = r[1];
+		u.cutoff.delta = r[2];
+		u.cutoff.timer = r[3];
+		c->n_cutoff_ramps += (int)(u.cutoff.timer != 0) - (int)was;
+		if(!cutoff_moving(u))
+			v.plain = 0;	// (arrived and snapped: the voice may be plain again)
+		sweep_track(c, ui);
+	}
+	st.n = c->cut_list.size() - st.first;
+	if(st.n)
+		c->cut_st.push_back(st);
+}
+} // namespace
+
+int a2amd_cutoff_sweep(int32_t ramper[4], unsigned frames, unsigned count, const uint32_t *ptab128, int samplerate,
+		int32_t *coef)
+{
+	if(!ramper || !ptab128 || !frames || frames > A2D_FRAG || samplerate <= 0)
+		return A2AMD_EINVAL;
+	int moved = 0;
+	for(unsigned j = 0; j < count; ++j) {
+		int32_t pitch;
+		const bool m = a2cs_step(ramper, (int)frames, &pitch);
+		moved += m;
+		if(coef)
+			coef[j] = m ? f12_coeff(ptab128, ramper[0], samplerate) : A2AMD_SWEEP_NONE;
+	}
+	return moved;
+}
+
 int a2amd_fragment_repeat(a2amd_ctx *c, unsigned frames, unsigned count)
 {
-	if(c->n_noise || c->n_cutoff_ramps)
-		return c->fail(A2AMD_EUNSUPPORTED, "fragment_repeat with %d noise oscillators / %d cutoff ramps "
-				"in flight", c->n_noise, c->n_cutoff_ramps);
+	if(c->n_noise)
+		return c->fail(A2AMD_EUNSUPPORTED, "fragment_repeat with %d noise oscillators in flight", c->n_noise);
 	if(c->n_clients)
 		return c->fail(A2AMD_EUNSUPPORTED, "fragment_repeat with clients on %d xinsert / xsink / xsource "
 				"unit(s): their callbacks need every window", c->n_clients);
+	// (filters whose cutoff is sweeping: their coefficients for the stretch are made on the device)
+	if(!c->sweeping.empty() && count) {
+		if(int r = sweep_stretch_check(c, "fragment_repeat", frames, count))
+			return r;
+		sweep_stretch(c, frames, count);
+	}
 	const long long walked = c->walk_serial;
 	for(unsigned i = 0; i < count; ++i) {
 		if(int r = a2amd_fragment(c, frames)) {
@@ -634,8 +727,6 @@ int a2amd_fragment_repeat_noise(a2amd_ctx *c, unsigned frames, unsigned count, u
 	if(c->comm || c->dist_local)
 		return c->fail(A2AMD_EUNSUPPORTED, "fragment_repeat_noise in a distributed or grouped context: one generator, "
 				"several contexts, no defined order");
-	if(c->n_cutoff_ramps)
-		return c->fail(A2AMD_EUNSUPPORTED, "fragment_repeat_noise with %d cutoff ramps in flight", c->n_cutoff_ramps);
 	if(c->n_clients)
 		return c->fail(A2AMD_EUNSUPPORTED, "fragment_repeat_noise with clients on %d xinsert / xsink / xsource "
 				"unit(s): their callbacks need every window", c->n_clients);
@@ -669,8 +760,14 @@ int a2amd_fragment_repeat_noise(a2amd_ctx *c, unsigned frames, unsigned count, u
 	if(listed != c->n_noise)
 		return c->fail(A2AMD_ESTATE, "fragment_repeat_noise: %d of %d live noise oscillators were processed by calls in "
 				"the last walked fragment: their place in the walk is not known", listed, c->n_noise);
+	if(!c->sweeping.empty())
+		if(int r = sweep_stretch_check(c, "fragment_repeat_noise", frames, count))
+			return r;
 	if(!count)
 		return A2AMD_OK;
+	// (filters whose cutoff is sweeping: their coefficients for the stretch are made on the device)
+	if(!c->sweeping.empty())
+		sweep_stretch(c, frames, count);
 	if(listed) {
 		const uint64_t span = (uint64_t)frames * count;
 		uint64_t draws = 0;
@@ -904,6 +1001,7 @@ int a2amd_unit_deinit(a2amd_ctx *c, int ui)
 	if(u.xio_mode)
 		--c->n_clients;
 	u.live = false;
+	sweep_track(c, ui);
 	c->deferred_free_units.push_back(ui);
 	--c->stats.live_units;
 	if(--v.nlive == 0) {
@@ -1027,6 +1125,7 @@ int a2amd_unit_write(a2amd_ctx *c, int ui, int reg, int value, unsigned start, u
 			ramp_set(u.cutoff, value + transpose, (int)start, (int)dur);
 			bool is = u.cutoff.timer != 0;
 			c->n_cutoff_ramps += (int)is - (int)was;
+			sweep_track(c, ui);
 			c->voices[u.voice].plain = 0;
 			if(dur < 256)
 				push_rec(c, u.voice, R_F1SET, u.chainpos, 0,
@@ -1402,6 +1501,8 @@ int a2amd_unit_process(a2amd_ctx *c, int ui, unsigned offset, unsigned frames, u
 					f12_coeff(c->ptab, u.cutoff.value, c->cfg.samplerate), 0, 0);
 		}
 		c->n_cutoff_ramps += (int)(u.cutoff.timer != 0) - (int)was;
+		if(moving)
+			sweep_track(c, ui);
 		if(moving && !cutoff_moving(u))
 			v.plain = 0;	// (the ramp has arrived and the ramper has snapped to its target: the voice may be plain again)
 		break;

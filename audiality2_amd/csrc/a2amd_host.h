@@ -151,8 +151,12 @@ struct HUnit {
 	long long noise_serial = -1, nslot_batch = -1;
 	int nslot = -1;
 	// --- second line ---
-	// filter12 shadow: the cutoff ramper never leaves the host
+	// filter12 shadow: the cutoff ramper is the host's - stepped by its Process calls, and over a stretch of repeated
+	// fragments by a2amd_fragment_repeat[_noise] in step with the device's sweep pass (a2amd_cutsweep.h)
 	Ramp cutoff = {0, 0, 0, 0};
+	int sweep_idx = -1;		// its place in a2amd_ctx::sweeping while cutoff_moving(), else -1
+	long long cslot_batch = -1;	// its column of the sweep table of the batch with this serial_base
+	int cslot = -1;
 	unsigned flags = 0;
 	int nin = 0, nout = 0, wired = 0;
 	// fbdelay: delay line pair index, and the three tap lengths in frames (what the
@@ -208,6 +212,7 @@ struct HVoice {
 					// noise voice whose windows are seeded on the device and that has no record of its own)
 	long long dynf2_run = -1;	// ... in which it was put on the records kernels' list of 2 x wtosc-filter12-panmix voices
 	long long noise_run = -1;	// ... in which upload() decided who renders its device-seeded noise windows (once per voice)
+	long long cut_run = -1;		// ... in which a filter of its chain has a column of the sweep table (a2amd_fragment_repeat[_noise])
 };
 
 enum { CLS_GENERIC = 0, CLS_OSCPAN, CLS_OSCFILTPAN, CLS_BUSDRIVER, CLS_BUSGENERIC, CLS_OSC2PAN, CLS_FMPAN, CLS_FBDCHAIN,
@@ -450,6 +455,20 @@ struct a2amd_ctx {
 	int noise_slots = 0;
 	DevBuf<uint32_t> d_nseed;	// [fragment][noise_slots]
 	DevBuf<int32_t> d_nslot;	// [unit]
+	// Cutoff sweeps in repeated fragments (a2amd_fragment_repeat[_noise], a2amd_cutsweep.hip).  sweeping: the live filter12
+	// units with cutoff_moving(), kept where a cutoff ramper changes (sweep_track) - empty in a scene without sweeps, which
+	// then takes no step of this path.  This batch's stretches with a sweep: fragments [f0, f0 + count) of 'frames' frames,
+	// their filters in cut_list[first, first + n); cut_slots: columns of the batch's sweep table.
+	std::vector<int> sweeping;
+	struct CutStretch { int f0, count; unsigned frames; size_t first, n; };
+	std::vector<CutStretch> cut_st;
+	std::vector<A2DCutSweep> cut_list;
+	int cut_slots = 0;
+	DevBuf<int32_t> d_cutf;		// [fragment][cut_slots]
+	DevBuf<int32_t> d_cslot;	// [unit]
+	a2amd_sweep_batch_info last_sweeps = {};	// a2amd_last_batch_sweeps()
+	uint32_t n_cut_standin = 0;		// upload(): voices of listed filters given the stand-in run
+	uint32_t n_cut_windows = 0;		// cells of this batch's table that hold a coefficient (the host's shadow steps count them)
 	// Self-cleaning buses: when every bus is read by k_bus_driver (its owner is a plain
 	// driver chain without records this batch), that kernel zeroes what it read and the
 	// root stores the master bus instead of adding to it - the batch needs no memset.
@@ -715,6 +734,26 @@ static inline void unhold(a2amd_ctx *c, int vi)
 // and the next a2_SetRamper starts from that value.  Only a ramper that has snapped may be left alone
 // (the voice "plain", its default windows reported through the map).
 inline bool cutoff_moving(const HUnit &u) { return u.cutoff.timer || u.cutoff.delta || u.cutoff.value != u.cutoff.target; }
+// ... and the list of the filters for which it is true (a2amd_ctx::sweeping): called wherever a cutoff ramper changes or
+// its unit goes away - a2amd_unit_write, a2amd_unit_process, a2amd_unit_deinit, the device VM handing a voice back, the
+// shadow steps of a2amd_fragment_repeat[_noise]
+inline void sweep_track(a2amd_ctx *c, int ui)
+{
+	HUnit &u = c->units[ui];
+	const bool on = u.live && u.kind == A2AMD_FILTER12 && cutoff_moving(u);
+	if(on == (u.sweep_idx >= 0))
+		return;
+	if(on) {
+		u.sweep_idx = (int)c->sweeping.size();
+		c->sweeping.push_back(ui);
+	} else {
+		const int last = c->sweeping.back();
+		c->sweeping[u.sweep_idx] = last;
+		c->units[last].sweep_idx = u.sweep_idx;
+		c->sweeping.pop_back();
+		u.sweep_idx = -1;
+	}
+}
 // (the wavetable leaf kernels only know mip-mapped waves, "off" and noise)
 inline bool leaf_mode(int mode) { return mode == A2D_OSC_MIPWAVE || mode == A2D_OSC_OFF || mode == A2D_OSC_NOISE; }
 // a tap the frame-parallel delay kernel can take: at least one fragment long, and
@@ -759,6 +798,7 @@ int vm_speculate(a2amd_ctx *c);			// ... k_vm_win for the batch after this one, 
 int vm_take_back(a2amd_ctx *c, int vi, bool inclusive, a2amd_vm_state *out, a2amd_vm_env *envs_out = nullptr);	// the voice is the host's again
 void vm_end_batch(a2amd_ctx *c);
 void vm_close(a2amd_ctx *c);
+void vm_build_f1tab(a2amd_ctx *c);		// ... made now, for the context's pitch table as it stands (vm_prepare_batch sends it up)
 void vm_start_f1tab(a2amd_ctx *c);		// the cutoff -> coefficient table, made on a thread of its own
 int vm_blob_room(a2amd_ctx *c);			// records the VM's region of the blob should hold
 

@@ -1106,6 +1106,18 @@ void k_voices(const A2DParams *__restrict__ pp, const int *__restrict__ list, in
 							}
 						lds_sync();
 					}
+					// (a sweeping filter's: what an R_F1RAMP record would have brought - the batch's sweep table)
+					if(p.ncut > 0) {
+						for(int u = 0; u < v.nunits; ++u)
+							if(A2D_KIND(p.udesc[v.unit[u]]) == A2D_FILTER12) {
+								int f1n;
+								if(lane == 0 && a2d_cut_coeff(p, f, v.unit[u], &f1n)) {
+									c.l->us[u][FW_F1NEXT] = f1n;
+									c.l->us[u][FW_RAMP] = 1;
+								}
+							}
+						lds_sync();
+					}
 					process_window(c, v, 0, nframes);
 				}
 			} else {

@@ -26,7 +26,8 @@
 //
 // A voice with records this batch (runs[v].count != 0) is the window / records kernels' and is skipped untouched.  The
 // host (upload(), a2amd_sched.cpp) leaves a voice without the stand-in run only while amplitude, q, volume and pan are at
-// rest; a stretch of device-seeded fragments only exists while every noise oscillator's pitch and every cutoff is.  A
+// rest and no filter of it has a column of the batch's sweep table (a cutoff sweeping in a stretch: a2d_cut_coeff); a
+// stretch of device-seeded fragments only exists while every noise oscillator's pitch is at rest.  A
 // voice that is not at rest all the same is left alone here, as one with records is: every wavefront of the workgroup
 // reads the same words and comes to the same answer.
 #include <hip/hip_runtime.h>

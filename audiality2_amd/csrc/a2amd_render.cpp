@@ -60,6 +60,9 @@ int a2amd_render(a2amd_ctx *c, unsigned phases, int32_t *const *out, unsigned ca
 	if((phases & A2AMD_RENDER_KEEP) && !c->noise_st.empty())
 		return c->fail(A2AMD_EUNSUPPORTED, "A2AMD_RENDER_KEEP on a batch with device-seeded noise windows "
 				"(a2amd_fragment_repeat_noise): a re-run would need a new generator word");
+	if((phases & A2AMD_RENDER_KEEP) && !c->cut_st.empty())
+		return c->fail(A2AMD_EUNSUPPORTED, "A2AMD_RENDER_KEEP on a batch with a cutoff sweep table "
+				"(a2amd_fragment_repeat with a sweeping filter): a re-run would need the ramp to go on");
 	close_fragment(c);
 	unsigned total = 0;
 	for(int f = 0; f < c->nfrags; ++f)
@@ -360,6 +363,9 @@ int a2amd_replay(a2amd_ctx *c, unsigned steps)
 	if(!c->noise_st.empty())
 		return c->fail(A2AMD_EUNSUPPORTED, "replay of a batch with device-seeded noise windows "
 				"(a2amd_fragment_repeat_noise): a re-run would need a new generator word");
+	if(!c->cut_st.empty())
+		return c->fail(A2AMD_EUNSUPPORTED, "replay of a batch with a cutoff sweep table "
+				"(a2amd_fragment_repeat with a sweeping filter): a re-run would need the ramp to go on");
 	for(int vi = 0; vi < (int)c->voices.size(); ++vi)
 		if(!c->voices[vi].recs.empty())
 			return c->fail(A2AMD_ESTATE, "replay of a batch that carries command records");
@@ -461,6 +467,14 @@ int a2amd_last_batch_noise_filter(const a2amd_ctx *c, a2amd_noise_filter_batch_i
 		return A2AMD_EINVAL;
 	*out = c->last_noise_filter;
 	out->min_voices = (uint32_t)c->nzf_min;
+	return A2AMD_OK;
+}
+
+int a2amd_last_batch_sweeps(const a2amd_ctx *c, a2amd_sweep_batch_info *out)
+{
+	if(!c || !out)
+		return A2AMD_EINVAL;
+	*out = c->last_sweeps;
 	return A2AMD_OK;
 }
 

@@ -3,6 +3,7 @@
 // the launch shapes, hipGraphs of quiet batches, and the end of a batch.  (Split out of
 // a2amd_host.cpp in round 3; the design notes are at the top of that file.)
 #include "a2amd_host.h"
+#include "a2amd_cutsweep.h"
 #include <functional>
 
 namespace a2h {
@@ -238,8 +239,9 @@ bool is_oscfiltpan_chain(const a2amd_ctx *c, const HVoice &v)
 	return o.kind == A2AMD_WTOSC && !(o.flags & A2AMD_PROCADD) && !o.wired &&
 			leaf_mode(o.mode) &&
 			f.kind == A2AMD_FILTER12 && f.nin == 1 && !f.wired && !(f.flags & A2AMD_PROCADD) &&
-			// (a ramping cutoff means an R_F1RAMP record per window: such a voice is never
-			// without records, and the quiet kernel skips voices with records)
+			// (a ramping cutoff means an R_F1RAMP record per window walked by calls, and in a stretch of repeated
+			// fragments a column of the batch's sweep table, whose voices upload() gives the stand-in run: such a
+			// voice is never without a run, and the quiet kernel skips voices that have one)
 			pm.kind == A2AMD_PANMIX && pm.nin == 1 && pm.nout == 2 && pm.wired &&
 			(pm.flags & A2AMD_PROCADD);
 }
@@ -327,8 +329,15 @@ int upload(a2amd_ctx *c)
 {
 	// (voices the device VM took over during this batch: the host's interpreter carries them to its
 	// end - records into their lists - and their states go up, a2amd_vm.cpp)
+	// (a batch with cutoff sweeps in repeated fragments: the sweep pass reads the coefficient table the device VM reads -
+	// made here for the pitch table as it stands where it is not yet, with or without the device VM in use;
+	// vm_prepare_batch sends it up)
+	if(!c->cut_st.empty())
+		vm_build_f1tab(c);
 	if(int r = vm_prepare_batch(c))
 		return r;
+	c->last_sweeps = a2amd_sweep_batch_info{};
+	c->n_cut_standin = 0;
 	c->n_noise_standin = c->n_noise_quiet = c->n_noise_filt_quiet = 0;
 	// (a2amd_last_batch_buses(): the lists of a quiet batch are the last upload's - nobody ramps, nothing is dropped)
 	c->n_bus_windows_dropped = 0;
@@ -342,7 +351,7 @@ int upload(a2amd_ctx *c)
 				memcmp(c->fragframes, c->blob_frames, (size_t)c->nfrags * sizeof(unsigned)) ? 10 : 12;
 		dbg_why()[why] += 1;
 	}
-	if(c->blob_quiet && c->with_recs.empty() && c->prev_with_recs.empty() && c->moving.empty() && c->noise_st.empty() && !c->voices_dirty &&
+	if(c->blob_quiet && c->with_recs.empty() && c->prev_with_recs.empty() && c->moving.empty() && c->noise_st.empty() && c->cut_st.empty() && !c->voices_dirty &&
 			!c->udesc_dirty && !c->waves_dirty && !c->lists_dirty && !c->ptab_dirty && !c->vm.list_dirty &&
 			c->dirty_voices.empty() && c->fbd_to_zero.empty() && c->bus_used <= c->d_busmem.cap) {
 		bool inject = false;
@@ -370,6 +379,8 @@ int upload(a2amd_ctx *c)
 			p.nfrags = c->nfrags;
 			p.nseed = nullptr;	// (no device-seeded noise windows in a quiet batch)
 			p.nnoise = 0;
+			p.cutf = nullptr;	// (... and no cutoff sweeps)
+			p.ncut = 0;
 			memset(p.fragframes, 0, sizeof(p.fragframes));
 			memset(p.fragstart, 0, sizeof(p.fragstart));
 			for(int f = 0, acc = 0; f < c->nfrags; ++f) {
@@ -419,6 +430,11 @@ int upload(a2amd_ctx *c)
 		// device-seeded noise windows (a2amd_fragment_repeat_noise): the batch's seed table and the oscillators' columns
 		if(int r = grow(c, c->d_nseed, (size_t)c->nfrags * (size_t)c->noise_slots, 1, false)) return r;
 		if(int r = grow(c, c->d_nslot, c->d_ustate.cap, 1, false)) return r;
+	}
+	if(!c->cut_st.empty()) {
+		// cutoff sweeps in repeated fragments (a2amd_fragment_repeat[_noise]): the batch's sweep table and the filters' columns
+		if(int r = grow(c, c->d_cutf, (size_t)c->nfrags * (size_t)c->cut_slots, 1, false)) return r;
+		if(int r = grow(c, c->d_cslot, c->d_ustate.cap, 1, false)) return r;
 	}
 	{
 		const int32_t *before = c->d_busmem.d;
@@ -610,6 +626,23 @@ int upload(a2amd_ctx *c)
 			give_stand_in(vi);
 		}
 	}
+	// Voices with a filter in this batch's sweep table (a2amd_fragment_repeat[_noise] with a cutoff sweeping) and no record
+	// in the whole batch: the same stand-in run keeps them with the kernels that read the table - the window kernels /
+	// k_leaf_recs for the wavetable classes, the general kernel (which takes its voices with or without records) for any
+	// other chain.  The quiet kernels render settled filters only and skip a voice that has a run: they never see one,
+	// whatever its class (as for noise below, the run is given whether or not the class is known for sure).
+	for(const A2DCutSweep &e : c->cut_list) {
+		const int vi = c->units[e.unit].voice;
+		HVoice &v = c->voices[vi];
+		if(v.cut_run == c->serial_base)
+			continue;	// (a voice with two sweeping filters, a filter listed by two stretches)
+		v.cut_run = c->serial_base;
+		if(!v.recs.empty() || !(v.live || v.dying))
+			continue;
+		if(v.moving_run != c->serial_base)
+			give_stand_in(vi);
+		++c->n_cut_standin;
+	}
 	// Voices with a noise oscillator in a device-seeded stretch (a2amd_fragment_repeat_noise) and no record in the whole
 	// batch: the same stand-in run keeps them with the kernels that regenerate a window's draws from a seed - the window
 	// kernels / k_leaf_recs for the four wavetable classes, the general kernel (which takes its voices with or without
@@ -620,8 +653,9 @@ int upload(a2amd_ctx *c)
 	// and wtosc (noise) -> filter12 -> panmix (k_leaf_noisefiltpan): a voice is left WITHOUT the run when its remembered class
 	// is CLS_NOISEPAN / CLS_NOISEFILTPAN and still stands (a stale one may be any class once the lists are rebuilt below; one
 	// that stands comes out of a rebuild as it went in), its amplitude, q, volume and pan are at rest (moving_until, the test
-	// of the list above: the kernels render settled voices only; a cutoff ramp cannot be in flight in a device-seeded
-	// stretch, a2amd_fragment_repeat_noise refuses it) and A2AMD_NOISE_QUIET is not 0.
+	// of the list above: the kernels render settled voices only), no filter of it has a column of this batch's sweep table
+	// (cut_run: a cutoff sweeping in a device-seeded stretch - such a voice has taken the run above) and A2AMD_NOISE_QUIET
+	// is not 0.
 	// The filter class moreover only from nzf_min such voices IN THIS BATCH on (A2AMD_NZF_MIN, a2amd_host.h): they are
 	// counted first - from the remembered classes, so the count is the same whether or not the lists are rebuilt below -
 	// and below the threshold every one of them takes the run, as before the class had a kernel.
@@ -636,7 +670,8 @@ int upload(a2amd_ctx *c)
 		// a voice a quiet noise kernel may take: which of the two classes (0: neither)
 		auto quiet_cls = [&](const HVoice &v) {
 			return c->noise_quiet && (v.cls == CLS_NOISEPAN || v.cls == CLS_NOISEFILTPAN) && !v.cls_stale && v.resolved &&
-					v.vm < 0 && v.recs.empty() && (v.live || v.dying) && v.moving_until <= t0 ? v.cls : 0;
+					v.vm < 0 && v.recs.empty() && (v.live || v.dying) && v.moving_until <= t0 && v.cut_run != c->serial_base ?
+					v.cls : 0;
 		};
 		// (a voice of either class has one oscillator: it is met once)
 		int nfilt = 0;
@@ -911,6 +946,11 @@ int upload(a2amd_ctx *c)
 		p.nslot = c->d_nslot.d;
 		p.nnoise = c->noise_slots;
 	}
+	if(!c->cut_st.empty()) {
+		p.cutf = c->d_cutf.d;
+		p.cslot = c->d_cslot.d;
+		p.ncut = c->cut_slots;
+	}
 	p.nfrags = c->nfrags;
 	p.samplerate = c->cfg.samplerate;
 	p.debug = getenv("A2AMD_DEBUG") ? atoi(getenv("A2AMD_DEBUG")) : 0;
@@ -920,7 +960,8 @@ int upload(a2amd_ctx *c)
 		acc += (int)c->fragframes[f];
 	}
 
-	// the blob: [params | records | scatter indices | scatter runs | exception lists | noise oscillators of the seed pass]
+	// the blob: [params | records | scatter indices | scatter runs | exception lists | noise oscillators of the seed pass |
+	// filters of the sweep pass]
 	auto up256 = [](size_t x) { return (x + 255) & ~(size_t)255; };
 	const size_t nsc = sc_idx.size();
 	const size_t o_recs = up256(sizeof(A2DParams));
@@ -929,7 +970,8 @@ int upload(a2amd_ctx *c)
 	const size_t o_dyn = o_val + up256(nsc * sizeof(A2DRun));
 	// ... and behind what the host makes, room for the records the device VM writes (a2amd_vm.cpp)
 	const size_t o_noise = o_dyn + up256(dyn_all.size() * sizeof(int));
-	const size_t host_total = o_noise + up256(c->noise_osc.size() * sizeof(A2DNoiseOsc));
+	const size_t o_cut = o_noise + up256(c->noise_osc.size() * sizeof(A2DNoiseOsc));
+	const size_t host_total = o_cut + up256(c->cut_list.size() * sizeof(A2DCutSweep));
 	const size_t vm_room = (size_t)vm_blob_room(c);
 	const size_t total = host_total;
 	if(int r = grow(c, c->d_blob, host_total + vm_room * sizeof(A2DRec), 1, false)) return r;
@@ -963,6 +1005,8 @@ int upload(a2amd_ctx *c)
 		memcpy(hb + o_dyn, dyn_all.data(), dyn_all.size() * sizeof(int));
 	if(!c->noise_osc.empty())
 		memcpy(hb + o_noise, c->noise_osc.data(), c->noise_osc.size() * sizeof(A2DNoiseOsc));
+	if(!c->cut_list.empty())
+		memcpy(hb + o_cut, c->cut_list.data(), c->cut_list.size() * sizeof(A2DCutSweep));
 	HIPCHK(c, hipMemcpyAsync(c->d_blob.d, hb, total, hipMemcpyHostToDevice, c->stream));
 	HIPCHK(c, hipEventRecord(c->blob_ev[bi], c->stream));
 	c->blob_busy[bi] = true;
@@ -980,6 +1024,26 @@ int upload(a2amd_ctx *c)
 		if(const int e = a2d_launch_noise_seeds((const A2DNoiseOsc *)(c->d_blob.d + o_noise) + st.first, (int)st.n, st.start, st.f0,
 				st.count, st.frames, c->d_nseed.d, c->noise_slots, c->d_nseed.cap, c->d_nslot.d, (int)c->d_nslot.cap, c->stream))
 			return c->fail(A2AMD_EHIP, "noise seed launch failed: %s", hipGetErrorString((hipError_t)e));
+	// the sweep pass: every cell of the batch's table says "no ramp" and no filter has a column (a2d_cut_coeff), then each
+	// stretch's rampers are stepped over it (k_cut_sweep) and, once for the batch, what they left is looked up in the
+	// coefficient table (k_cut_resolve) - in front of the kernels that render the windows
+	if(!c->cut_st.empty()) {
+		const size_t words = (size_t)c->nfrags * (size_t)c->cut_slots;
+		if(!c->vm.d_f1tab || !c->vm.f1tab_up)
+			return c->fail(A2AMD_ESTATE, "cutoff sweep: the coefficient table is not on the device");
+		HIPCHK(c, hipMemsetAsync(c->d_cutf.d, A2CS_NONE_BYTE, words * sizeof(int32_t), c->stream));
+		HIPCHK(c, hipMemsetAsync(c->d_cslot.d, 0, c->d_cslot.cap * sizeof(int32_t), c->stream));
+		for(const a2amd_ctx::CutStretch &st : c->cut_st)
+			if(const int e = a2d_launch_cut_sweep((const A2DCutSweep *)(c->d_blob.d + o_cut) + st.first, (int)st.n, st.f0, st.count,
+					st.frames, c->d_cutf.d, c->cut_slots, words, c->d_cslot.d, (int)c->d_cslot.cap, c->stream))
+				return c->fail(A2AMD_EHIP, "cutoff sweep launch failed: %s", hipGetErrorString((hipError_t)e));
+		if(const int e = a2d_launch_cut_resolve(c->d_cutf.d, words, c->vm.d_f1tab, c->stream))
+			return c->fail(A2AMD_EHIP, "cutoff sweep launch failed: %s", hipGetErrorString((hipError_t)e));
+		c->last_sweeps.pass_launched = 1;
+		c->last_sweeps.filters = (uint32_t)c->cut_slots;
+		c->last_sweeps.ramp_windows = c->n_cut_windows;
+		c->last_sweeps.standin_voices = c->n_cut_standin;
+	}
 	c->uploaded = true;
 	c->blob_quiet = recs.empty() && dyn_all.empty();
 	c->blob_nfrags = c->nfrags;
@@ -1149,6 +1213,10 @@ void end_batch(a2amd_ctx *c)
 	c->noise_st.clear();
 	c->noise_osc.clear();
 	c->noise_slots = 0;
+	c->cut_st.clear();
+	c->cut_list.clear();
+	c->cut_slots = 0;
+	c->n_cut_windows = 0;
 	c->nfrags = 0;
 	c->cur_frag = 0;
 	c->frag_open = false;

@@ -493,6 +493,7 @@ int vm_take_back(a2amd_ctx *c, int vi, bool inclusive, a2amd_vm_state *out, a2am
 		u.cutoff.delta = st.cut[k][2];
 		u.cutoff.timer = st.cut[k][3];
 		c->n_cutoff_ramps += (int)(u.cutoff.timer != 0) - (int)was;
+		sweep_track(c, vv.unit[st.cutpos[k]]);
 	}
 	vv.plain = 0;
 	if(envs_out)
@@ -544,6 +545,12 @@ void vm_start_f1tab(a2amd_ctx *c)
 	if((m.f1_future.valid() && m.f1_future_sum == ptab_sum(c->ptab)) || (!m.f1tab.empty() && m.f1tab_sum == ptab_sum(c->ptab)))
 		return;
 	start_f1tab(c);
+}
+
+// the sweep pass reads the same table (a2amd_cutsweep.hip), whether or not the device VM is in use
+void vm_build_f1tab(a2amd_ctx *c)
+{
+	build_f1tab(c);
 }
 
 int vm_blob_room(a2amd_ctx *c)

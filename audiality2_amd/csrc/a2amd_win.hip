@@ -148,6 +148,13 @@ DEV void win_ctl_body(const A2DParams *__restrict__ pp, const int *__restrict__ 
 					if(cv.os[o].mode == A2D_OSC_NOISE)
 						a2d_noise_seed(p, f, cv.uu[o], &cv.os[o].seed);
 			}
+			// (a sweeping filter's: what an R_F1RAMP record would have brought - the batch's sweep table)
+			if(FILT && !inrec && cv.active) {
+				int f1n = 0;
+				const bool hit = a2d_cut_coeff(p, f, cv.uu[NOSC], &f1n);
+				cv.fs.f1next = hit ? f1n : cv.fs.f1next;
+				cv.fs.ramp = hit ? 1 : cv.fs.ramp;
+			}
 			if(inrec && !op)
 				op = R_NOP;
 		}

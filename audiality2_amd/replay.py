@@ -99,6 +99,15 @@ class a2amd_noise_filter_batch_info(C.Structure):
         return "noise_filter_batch_info(" + ", ".join(f"{n}={getattr(self, n)}" for n, _ in self._fields_) + ")"
 
 
+class a2amd_sweep_batch_info(C.Structure):
+    """include/a2amd_sweep.h: the cutoff sweeps of the most recent batch's repeated fragments"""
+    _fields_ = [("pass_launched", C.c_uint32), ("filters", C.c_uint32),
+                ("ramp_windows", C.c_uint32), ("standin_voices", C.c_uint32)]
+
+    def __repr__(self):
+        return "sweep_batch_info(" + ", ".join(f"{n}={getattr(self, n)}" for n, _ in self._fields_) + ")"
+
+
 class a2amd_bus_info(C.Structure):
     """include/a2amd_bus.h: who rendered the bus owners - the root and the group voices - of the most recent batch"""
     _fields_ = [(n, C.c_uint32) for n in ("driver_voices", "driver_ramping", "driver_windows_dropped", "fbd_voices",
@@ -154,6 +163,12 @@ class Backend:
         self._last_batch_noise_filter = None
         if hasattr(lib, prefix + "last_batch_noise_filter"):
             self._last_batch_noise_filter = fn("last_batch_noise_filter", i32, vp, C.POINTER(a2amd_noise_filter_batch_info))
+        self._fragment_repeat = None
+        if hasattr(lib, prefix + "fragment_repeat"):
+            self._fragment_repeat = fn("fragment_repeat", i32, vp, u32, u32)
+        self._last_batch_sweeps = None
+        if hasattr(lib, prefix + "last_batch_sweeps"):
+            self._last_batch_sweeps = fn("last_batch_sweeps", i32, vp, C.POINTER(a2amd_sweep_batch_info))
         self._last_batch_buses = None
         if hasattr(lib, prefix + "last_batch_buses"):
             self._last_batch_buses = fn("last_batch_buses", i32, vp, C.POINTER(a2amd_bus_info))
@@ -240,6 +255,22 @@ class Backend:
 
     def fragment(self, frames):
         return self._chk(self._fragment(self.ctx, frames), "fragment")
+
+    def fragment_repeat(self, frames, count):
+        """`count` further fragments of default windows (a2amd_fragment_repeat): no noise oscillators; the
+        coefficients of filters whose cutoff is sweeping are made on the device."""
+        if self._fragment_repeat is None:
+            raise RuntimeError(f"this library has no {self.prefix}fragment_repeat")
+        return self._chk(self._fragment_repeat(self.ctx, frames, count), "fragment_repeat")
+
+    def last_batch_sweeps(self):
+        """a2amd_last_batch_sweeps: whether the sweep pass ran for the most recent batch, the filters it listed,
+        the windows in which a cutoff moved, the voices given the stand-in record for it"""
+        if self._last_batch_sweeps is None:
+            raise RuntimeError(f"this library has no {self.prefix}last_batch_sweeps")
+        bi = a2amd_sweep_batch_info()
+        self._chk(self._last_batch_sweeps(self.ctx, C.byref(bi)), "last_batch_sweeps")
+        return bi
 
     def fragment_repeat_noise(self, frames, count):
         """`count` further fragments of default windows, settled noise oscillators seeded on the device

@@ -386,11 +386,13 @@ int  a2amd_render_group(a2amd_ctx *const *ctxs, int n, unsigned phases, int32_t 
 /* Begin 'count' further fragments of 'frames' frames in which the engine's
  * voice walk finds every VM asleep: each live voice gets exactly one
  * Process(0, frames) per unit and nothing else happens (src/core.c:1852-1878
- * with no wake-ups).  Fails with A2AMD_EUNSUPPORTED while a noise oscillator,
- * a ramping filter cutoff or a unit with clients (a2amd_unit_clients) needs
- * per-call host work.  (An oscillator may be switched to noise after such a
- * stretch: the host keeps no copy of a wavetable oscillator's phase, it fetches
- * the device's when the switch comes.) */
+ * with no wake-ups).  Fails with A2AMD_EUNSUPPORTED while a noise oscillator
+ * or a unit with clients (a2amd_unit_clients) needs per-call host work.  A
+ * filter12 whose cutoff is ramping does not: its coefficients for the stretch
+ * are made on the device (include/a2amd_sweep.h, included below).  (An
+ * oscillator may be switched to noise after such a stretch: the host keeps no
+ * copy of a wavetable oscillator's phase, it fetches the device's when the
+ * switch comes.) */
 int  a2amd_fragment_repeat(a2amd_ctx *ctx, unsigned frames, unsigned count);
 
 /* ... and with settled noise oscillators, seeded on the device: a2amd_fragment_repeat_noise(),
@@ -445,6 +447,8 @@ int  a2amd_last_batch(const a2amd_ctx *ctx, a2amd_batch_info *bi);
 #include "a2amd_noisepan.h"
 /* ... and of settled noise voices with a filter: a2amd_last_batch_noise_filter(), a2amd_noise_filter_window(). */
 #include "a2amd_noisefilt.h"
+/* Filter cutoff sweeps in repeated fragments: a2amd_last_batch_sweeps(), a2amd_cutoff_sweep(). */
+#include "a2amd_sweep.h"
 /* Who rendered the bus owners - the root and the group voices - of the most recent batch: a2amd_last_batch_buses(). */
 #include "a2amd_bus.h"
 /* Rendered waves with "normalize" / "xfade", post-processed on the device: a2amd_wave_upload_captured_post(), a2amd_wavepost_host(). */
