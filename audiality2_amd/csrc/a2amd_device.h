@@ -354,10 +354,13 @@ int a2d_launch_voices(const A2DParams *dparams, const int *dlist, int nlist, int
 // (needs the staging copy 'ustage' of the unit state array)
 // a state commit a time-sliced leaf kernel left to be done (ustage -> ustate for its
 // voices): rides along with the next driver-chain launch instead of one of its own
-struct A2DCommit { const int *list; int nlist, nosc; const int *ustage; };
+// staged[e]: what the kernel staged for entry e of its list in this batch - nothing (the voice carried records), the
+// oscillators' phases (a settled voice: nothing else moved), or every word (a voice with something still moving)
+enum { A2D_STAGED_NONE = 0, A2D_STAGED_PHASES, A2D_STAGED_FULL };
+struct A2DCommit { const int *list; int nlist, nosc; const int *ustage; const unsigned char *staged; };
 struct A2DCommitSet { A2DCommit c[2]; int n; };
 int a2d_launch_leaf_oscpan(const A2DParams *dparams, const A2DParams &hp, const int *dlist, int nlist,
-		int vpw, int ysplit, int *ustage, void *stream, void *event_after_main, A2DCommit *defer);
+		int vpw, int ysplit, int *ustage, unsigned char *staged, void *stream, void *event_after_main, A2DCommit *defer);
 int a2d_launch_bus_driver(const A2DParams *dparams, const int *dlist, int nlist, int nfrags, int consume,
 		const A2DCommitSet *commits, void *stream, int *master_host = nullptr, int ramping = 0);	// ramping: the launch of the drivers still gliding (one workgroup each); master_host: where the root stores the master bus (pinned host memory) instead of the bus memory
 int a2d_launch_commit(const A2DParams &hp, const A2DCommit &cm, void *stream);
@@ -388,7 +391,7 @@ int a2d_launch_leaf_oscfiltpan(const A2DParams *dparams, const A2DParams &hp, co
 // runs[idx[i]] = val[i] for the few voices whose record run changed this batch
 int a2d_launch_scatter_runs(const int *didx, const A2DRun *dval, int n, A2DRun *druns, void *stream);
 int a2d_launch_leaf_osc2pan(const A2DParams *dparams, const A2DParams &hp, const int *dlist, int nlist,
-		int vpw, int ysplit, int *ustage, void *stream, A2DCommit *defer);
+		int vpw, int ysplit, int *ustage, unsigned char *staged, void *stream, A2DCommit *defer);
 // wtosc[+wtosc] [-> filter12] -> panmix voices that carry records this batch (nosc = 1 | 2, filt = 0 | 1)
 // skip_empty: the list's voices get their records from the device VM (a2amd_vm.hip); those it left
 // without any this batch are rendered by their class's quiet kernel

@@ -338,13 +338,25 @@ DEV void osc_to_mem(int *w, const OscS &o)
 	w[OW_A] = o.a.value; w[OW_A + 1] = o.a.target; w[OW_A + 2] = o.a.delta; w[OW_A + 3] = o.a.timer;
 }
 
+// What a time-sliced launch staged for the voice at one entry of its list, for the commit: every entry is
+// written in every batch, by exactly one wavefront - the slice that walked the voice if it had something
+// moving, the last slice otherwise.
+DEV void stage_mark(unsigned char *m, bool mine, bool settled, bool last_slice, bool walker)
+{
+	if(mine && !settled) {
+		if(walker)
+			*m = A2D_STAGED_FULL;
+	} else if(last_slice)
+		*m = mine ? A2D_STAGED_PHASES : A2D_STAGED_NONE;
+}
+
 #define OSC1_WPE 4
 __global__ __launch_bounds__(64 * FAST_WPB) __attribute__((amdgpu_waves_per_eu(OSC1_WPE, OSC1_WPE)))
 void k_leaf_oscpan(const A2DParams *__restrict__ pp, const int *__restrict__ list, int nlist, int vpw,
 		int ysplit, const A2DVoice *__restrict__ voices, const int *ustate,
 		int *ustage, const int16_t *__restrict__ wavepool,
 		const A2DWave *__restrict__ waves, const uint32_t *__restrict__ ptab, int *__restrict__ busmem,
-		const int *__restrict__ wavecoef)
+		const int *__restrict__ wavecoef, unsigned char *__restrict__ staged)
 {
 	const A2DParams &p = *pp;
 	const int wv = rfl((int)(threadIdx.x >> 6));	// (wave-uniform, and known to the compiler as such)
@@ -640,55 +652,52 @@ void k_leaf_oscpan(const A2DParams *__restrict__ pp, const int *__restrict__ lis
 	// slices are still reading the old state, so it is staged and committed by
 	// k_commit_oscpan afterwards.  The last slice owns the settled voices (their
 	// end phase), the slice that walked it each of the others.
-	// (a settled voice: as it was, the phase moved on; the others were stored by the loop above)
+	// (a settled voice: only its phase moved on, and only the phase is staged; the others
+	// were stored, every word, by the loop above.  staged[] tells the commit which it was.)
 	if(mine && dv[DV_SETTLED] && last_slice) {
-		const int *wi0 = ustate + (size_t)u0 * A2D_USTATE, *wi1 = ustate + (size_t)u1 * A2D_USTATE;
 		int *w0 = ustage + (size_t)u0 * A2D_USTATE;
-		int *w1 = ustage + (size_t)u1 * A2D_USTATE;
-		if(w0 != wi0) {
-			w0[OW_MODE] = wi0[OW_MODE]; w0[OW_WAVE] = wi0[OW_WAVE]; w0[OW_DPHASE] = wi0[OW_DPHASE];
-			w0[OW_PRAMPING] = wi0[OW_PRAMPING];
-#pragma unroll
-			for(int k = 0; k < 4; ++k) {
-				w0[OW_P + k] = wi0[OW_P + k];
-				w0[OW_A + k] = wi0[OW_A + k];
-				w1[PW_VOL + k] = wi1[PW_VOL + k];
-				w1[PW_PAN + k] = wi1[PW_PAN + k];
-			}
-		}
 		w0[OW_PHASE_LO] = phlo_l;
 		w0[OW_PHASE_HI] = phhi_l;
 	}
+	if(ustage != ustate && lane < nv)
+		stage_mark(staged + first + lane, mine, dv[DV_SETTLED] != 0, last_slice, lane % nslices == slice);
 }
 
-// staged state of the fast leaf voices (nosc oscillators + panmix) -> the unit
-// state array
-DEV void commit_block(const A2DCommit &cm, int block, const A2DVoice *__restrict__ voices,
-		const A2DRun *__restrict__ runs, int *__restrict__ ustate)
+// staged state of the fast leaf voices (nosc oscillators + panmix) -> the unit state array: one thread per
+// oscillator of a list entry.  What the kernel says it staged (A2DCommit::staged) decides: the phase, or
+// the phase and every other word (the panmix with the first oscillator's thread), or nothing.
+DEV void commit_block(const A2DCommit &cm, int block, const A2DVoice *__restrict__ voices, int *__restrict__ ustate)
 {
-	const int per = (cm.nosc + 1) * 16;
-	int i = block * 256 + threadIdx.x;
-	if(i >= cm.nlist * per)
+	const int i = block * 256 + threadIdx.x;
+	if(i >= cm.nlist * cm.nosc)
 		return;
-	const int slot = cm.list[i / per];
-	if(runs[slot].count)
-		return;		// not rendered by the fast kernel this batch: nothing staged
-	const A2DVoice &vc = voices[slot];
-	const int u = (i % per) >> 4, k = i & 15;
+	const int e = i / cm.nosc, o = i - e * cm.nosc;
+	const int what = cm.staged[e];
+	if(what == A2D_STAGED_NONE)
+		return;
+	const A2DVoice &vc = voices[cm.list[e]];
+	const size_t a = (size_t)vc.unit[o] * A2D_USTATE;
+	ustate[a + OW_PHASE_LO] = cm.ustage[a + OW_PHASE_LO];
+	ustate[a + OW_PHASE_HI] = cm.ustage[a + OW_PHASE_HI];
+	if(what != A2D_STAGED_FULL)
+		return;
 	// the words the kernels stage: wtosc 0..14 except the noise sample, panmix 0..7
-	if(u < cm.nosc ? (k != OW_NOISE && k < 15) : (k < 8)) {
-		size_t a = (size_t)vc.unit[u] * A2D_USTATE + k;
-		ustate[a] = cm.ustage[a];
+	for(int k = 0; k < 15; ++k)
+		if(k != OW_NOISE && k != OW_PHASE_LO && k != OW_PHASE_HI)
+			ustate[a + k] = cm.ustage[a + k];
+	if(o == 0) {
+		const size_t ap = (size_t)vc.unit[cm.nosc] * A2D_USTATE;
+		for(int k = 0; k < 8; ++k)
+			ustate[ap + k] = cm.ustage[ap + k];
 	}
 }
 
-DEV int commit_blocks(const A2DCommit &cm) { return (cm.nlist * (cm.nosc + 1) * 16 + 255) / 256; }
+DEV int commit_blocks(const A2DCommit &cm) { return (cm.nlist * cm.nosc + 255) / 256; }
 
 __global__ __launch_bounds__(256)
-void k_commit_oscpan(A2DCommit cm, const A2DVoice *__restrict__ voices, const A2DRun *__restrict__ runs,
-		int *__restrict__ ustate)
+void k_commit_oscpan(A2DCommit cm, const A2DVoice *__restrict__ voices, int *__restrict__ ustate)
 {
-	commit_block(cm, blockIdx.x, voices, runs, ustate);
+	commit_block(cm, blockIdx.x, voices, ustate);
 }
 
 // ---------------------------------------------------------------------------
@@ -737,7 +746,8 @@ __global__ __launch_bounds__(64 * FAST_WPB) __attribute__((amdgpu_waves_per_eu(O
 void k_leaf_osc2pan(const A2DParams *__restrict__ pp, const int *__restrict__ list, int nlist, int vpw,
 		int ysplit, const A2DVoice *__restrict__ voices, const int *ustate, int *ustage,
 		const int16_t *__restrict__ wavepool, const A2DWave *__restrict__ waves,
-		const uint32_t *__restrict__ ptab, int *__restrict__ busmem, const int *__restrict__ wavecoef)
+		const uint32_t *__restrict__ ptab, int *__restrict__ busmem, const int *__restrict__ wavecoef,
+		unsigned char *__restrict__ staged)
 {
 	const A2DParams &p = *pp;
 	const int wv = rfl((int)(threadIdx.x >> 6));	// (wave-uniform, and known to the compiler as such)
@@ -994,32 +1004,19 @@ void k_leaf_osc2pan(const A2DParams *__restrict__ pp, const int *__restrict__ li
 		}
 	}
 
-	// A settled voice's state after the batch: as it was, with the oscillators' phases moved on (the
-	// last slice writes it; voices that were not settled were stored by the loop above).
+	// A settled voice's state after the batch: as it was, with the oscillators' phases moved on - the only
+	// words stored, and so the only ones staged (the last slice writes them; voices that were not settled
+	// were stored, every word, by the loop above).  staged[] tells the commit which it was.
 	if(mine && settled_l && last_slice) {
 #pragma unroll
 		for(int o = 0; o < 2; ++o) {
-			const int *wi = ustate + (size_t)uu[o] * A2D_USTATE;
 			int *w = ustage + (size_t)uu[o] * A2D_USTATE;
-			if(w != wi) {
-				w[OW_MODE] = wi[OW_MODE]; w[OW_WAVE] = wi[OW_WAVE]; w[OW_DPHASE] = wi[OW_DPHASE];
-				w[OW_PRAMPING] = wi[OW_PRAMPING];
-#pragma unroll
-				for(int k = 0; k < 4; ++k) {
-					w[OW_P + k] = wi[OW_P + k];
-					w[OW_A + k] = wi[OW_A + k];
-				}
-			}
 			w[OW_PHASE_LO] = phlo_l[o];
 			w[OW_PHASE_HI] = phhi_l[o];
 		}
-		const int *wpi = ustate + (size_t)uu[2] * A2D_USTATE;
-		int *wp = ustage + (size_t)uu[2] * A2D_USTATE;
-		if(wp != wpi)
-#pragma unroll
-			for(int k = 0; k < 8; ++k)
-				wp[k] = wpi[k];
 	}
+	if(ustage != ustate && lane < nv)
+		stage_mark(staged + first + lane, mine, settled_l != 0, last_slice, lane % nslices == slice);
 }
 
 // ---------------------------------------------------------------------------
@@ -2787,38 +2784,37 @@ void k_leaf_osc2filtpan(const A2DParams *__restrict__ pp, const int *__restrict_
 // inline -> panmix 2->2 -> xinsert (add, wired): root / group driver voices
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(256)
-void k_bus_driver(const A2DParams *__restrict__ pp, const int *__restrict__ list, int nlist, int consume,
+void k_bus_driver(const A2DParams *__restrict__ pp, const int *__restrict__ list, int nlist, int ny, int consume,
 		A2DCommitSet commits, int *__restrict__ master_host, int ramping)
 {
 	__shared__ int fr[A2D_MAXBATCH][5];	// per fragment: vol, dvol, pan, dpan, clamp
 	const A2DParams &p = *pp;
-	if((int)blockIdx.x >= nlist) {
-		// workgroups past the voices: state commits the leaf kernels left behind
-		// (different voices than the ones rendered here)
-		if(blockIdx.y)
-			return;
-		int b = (int)blockIdx.x - nlist;
+	// One index: ny workgroups per voice (by * nlist + voice), then the state commits the leaf kernels
+	// left behind (different voices than the ones rendered here), each of their workgroups once.
+	const int by = (int)blockIdx.x / nlist, vi = (int)blockIdx.x - by * nlist;
+	if(by >= ny) {
+		int b = (int)blockIdx.x - nlist * ny;
 		for(int k = 0; k < commits.n; ++k) {
 			const int nb = commit_blocks(commits.c[k]);
 			if(b < nb) {
-				commit_block(commits.c[k], b, p.voices, p.runs, p.ustate);
+				commit_block(commits.c[k], b, p.voices, p.ustate);
 				return;
 			}
 			b -= nb;
 		}
 		return;
 	}
-	if(p.runs[list[blockIdx.x]].count)
+	if(p.runs[list[vi]].count)
 		return;		// carries records this batch: the general kernel renders it
-	const A2DVoice &vc = p.voices[list[blockIdx.x]];
+	const A2DVoice &vc = p.voices[list[vi]];
 	const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
 	int *w = p.ustate + (size_t)vc.unit[1] * A2D_USTATE;
 	Ramp vol = ramp_load(w + PW_VOL), pan = ramp_load(w + PW_PAN);
 	// Both rampers at rest (the usual case): the gains are the same for every
 	// fragment, the fragments are independent and the workgroups of this voice
-	// (blockIdx.y) split them.  Otherwise one workgroup steps the rampers through
+	// (by, ny of them) split them.  Otherwise one workgroup steps the rampers through
 	// the batch first and renders it alone - in a launch of its own (ramping,
-	// gridDim.y == 1, the drivers the host knows may glide): it stores the rampers'
+	// ny == 1, the drivers the host knows may glide): it stores the rampers'
 	// end state, which may be a settled one, into the words every workgroup of the
 	// voice decides by, so no workgroup of that launch may share the voice with
 	// another.  The launch over all drivers leaves an unsettled voice alone and
@@ -2827,7 +2823,7 @@ void k_bus_driver(const A2DParams *__restrict__ pp, const int *__restrict__ list
 			vol.value == vol.target && pan.value == pan.target;
 	if(settled == (ramping != 0))
 		return;
-	const int fbeg = blockIdx.y * 4 + wv, fstep = gridDim.y * 4;
+	const int fbeg = by * 4 + wv, fstep = ny * 4;
 	if(!settled) {
 		if(threadIdx.x == 0) {
 			// panmix_process22's rampers (panmix.c:192-249)
@@ -3003,22 +2999,22 @@ int a2d_launch_bus_fbdchain(const A2DParams *dparams, const int *dlist, int nlis
 }
 
 int a2d_launch_leaf_oscpan(const A2DParams *dparams, const A2DParams &hp, const int *dlist, int nlist,
-		int vpw, int ysplit, int *ustage, void *stream, void *event_after_main, A2DCommit *defer)
+		int vpw, int ysplit, int *ustage, unsigned char *staged, void *stream, void *event_after_main, A2DCommit *defer)
 {
 	if(nlist <= 0)
 		return 0;
 	vpw = vpw < 1 ? 1 : (vpw > 64 ? 64 : vpw);
-	if(ysplit < 1 || !ustage)
+	if(ysplit < 1 || !ustage || !staged)
 		ysplit = 1;
 	int nwaves = (nlist + vpw - 1) / vpw;
 	int nblocks = (nwaves + FAST_WPB - 1) / FAST_WPB;
 	hipLaunchKernelGGL(k_leaf_oscpan, dim3(nblocks, ysplit), dim3(64 * FAST_WPB), 0, (hipStream_t)stream,
 			dparams, dlist, nlist, vpw, ysplit, hp.voices, (const int *)hp.ustate,
-			ysplit > 1 ? ustage : hp.ustate, hp.wavepool, hp.waves, hp.ptab, hp.busmem, hp.wavecoef);
+			ysplit > 1 ? ustage : hp.ustate, hp.wavepool, hp.waves, hp.ptab, hp.busmem, hp.wavecoef, staged);
 	if(event_after_main)
 		hipEventRecord((hipEvent_t)event_after_main, (hipStream_t)stream);
 	if(ysplit > 1) {
-		A2DCommit cm = { dlist, nlist, 1, ustage };
+		A2DCommit cm = { dlist, nlist, 1, ustage, staged };
 		if(defer)
 			*defer = cm;
 		else
@@ -3029,20 +3025,20 @@ int a2d_launch_leaf_oscpan(const A2DParams *dparams, const A2DParams &hp, const 
 }
 
 int a2d_launch_leaf_osc2pan(const A2DParams *dparams, const A2DParams &hp, const int *dlist, int nlist,
-		int vpw, int ysplit, int *ustage, void *stream, A2DCommit *defer)
+		int vpw, int ysplit, int *ustage, unsigned char *staged, void *stream, A2DCommit *defer)
 {
 	if(nlist <= 0)
 		return 0;
 	vpw = vpw < 1 ? 1 : (vpw > 64 ? 64 : vpw);
-	if(ysplit < 1 || !ustage)
+	if(ysplit < 1 || !ustage || !staged)
 		ysplit = 1;
 	int nwaves = (nlist + vpw - 1) / vpw;
 	int nblocks = (nwaves + FAST_WPB - 1) / FAST_WPB;
 	hipLaunchKernelGGL(k_leaf_osc2pan, dim3(nblocks, ysplit), dim3(64 * FAST_WPB), 0, (hipStream_t)stream,
 			dparams, dlist, nlist, vpw, ysplit, hp.voices, (const int *)hp.ustate,
-			ysplit > 1 ? ustage : hp.ustate, hp.wavepool, hp.waves, hp.ptab, hp.busmem, hp.wavecoef);
+			ysplit > 1 ? ustage : hp.ustate, hp.wavepool, hp.waves, hp.ptab, hp.busmem, hp.wavecoef, staged);
 	if(ysplit > 1) {
-		A2DCommit cm = { dlist, nlist, 2, ustage };
+		A2DCommit cm = { dlist, nlist, 2, ustage, staged };
 		if(defer)
 			*defer = cm;
 		else
@@ -3612,8 +3608,8 @@ int a2d_launch_commit(const A2DParams &hp, const A2DCommit &cm, void *stream)
 {
 	if(cm.nlist <= 0)
 		return 0;
-	hipLaunchKernelGGL(k_commit_oscpan, dim3((cm.nlist * (cm.nosc + 1) * 16 + 255) / 256), dim3(256), 0,
-			(hipStream_t)stream, cm, hp.voices, hp.runs, hp.ustate);
+	hipLaunchKernelGGL(k_commit_oscpan, dim3((cm.nlist * cm.nosc + 255) / 256), dim3(256), 0,
+			(hipStream_t)stream, cm, hp.voices, hp.ustate);
 	return (int)hipGetLastError();
 }
 
@@ -3626,7 +3622,7 @@ int a2d_launch_bus_driver(const A2DParams *dparams, const int *dlist, int nlist,
 		// the drivers still gliding: one workgroup each
 		A2DCommitSet none;
 		none.n = 0;
-		hipLaunchKernelGGL(k_bus_driver, dim3(nlist, 1), dim3(256), 0, (hipStream_t)stream, dparams, dlist, nlist, consume,
+		hipLaunchKernelGGL(k_bus_driver, dim3(nlist), dim3(256), 0, (hipStream_t)stream, dparams, dlist, nlist, 1, consume,
 				none, master_host, 1);
 		return (int)hipGetLastError();
 	}
@@ -3637,10 +3633,11 @@ int a2d_launch_bus_driver(const A2DParams *dparams, const int *dlist, int nlist,
 		for(int k = 0; k < commits->n; ++k)
 			if(commits->c[k].nlist > 0) {
 				cs.c[cs.n++] = commits->c[k];
-				extra += (commits->c[k].nlist * (commits->c[k].nosc + 1) * 16 + 255) / 256;
+				extra += (commits->c[k].nlist * commits->c[k].nosc + 255) / 256;
 			}
-	// grid.y: workgroups per voice, 4 fragments in flight each
-	hipLaunchKernelGGL(k_bus_driver, dim3(nlist + extra, nfrags >= 16 ? 16 : (nfrags + 3) / 4), dim3(256), 0,
-			(hipStream_t)stream, dparams, dlist, nlist, consume, cs, master_host, 0);
+	// ny: workgroups per voice, 4 fragments in flight each; the commits' workgroups behind them, once
+	const int ny = nfrags >= 16 ? 16 : (nfrags + 3) / 4;
+	hipLaunchKernelGGL(k_bus_driver, dim3(nlist * ny + extra), dim3(256), 0,
+			(hipStream_t)stream, dparams, dlist, nlist, ny, consume, cs, master_host, 0);
 	return (int)hipGetLastError();
 }

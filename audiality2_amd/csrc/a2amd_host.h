@@ -582,6 +582,7 @@ struct a2amd_ctx {
 	DevBuf<int32_t> d_xio;		// cap in slots of A2D_XIO_SLOT words
 	uint32_t *d_fmsine = nullptr;
 	DevBuf<int> d_list;
+	DevBuf<unsigned char> d_staged;	// per entry of d_list: what a time-sliced leaf kernel staged there (A2D_STAGED_*)
 	DevBuf<int> d_scatter;	// idx[k] then A2DRun[k] for k_scatter_runs
 	uint32_t *d_ptab = nullptr;
 	A2DParams *d_params = nullptr;	// = start of the device blob of the uploaded batch

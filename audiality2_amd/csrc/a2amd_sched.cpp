@@ -804,6 +804,7 @@ int upload(a2amd_ctx *c)
 			r.generic = append_range(c->list_all, bydepth[d].second);
 		}
 		if(int r = grow(c, c->d_list, c->list_all.size() + 64, 1, false)) return r;
+		if(int r = grow(c, c->d_staged, c->d_list.cap, 1, false)) return r;	// (one marker per list entry)
 		if(!c->list_all.empty())
 			HIPCHK(c, hipMemcpyAsync(c->d_list.d, c->list_all.data(), c->list_all.size() * sizeof(int),
 					hipMemcpyHostToDevice, c->stream));
@@ -1625,7 +1626,8 @@ static int launch_leaves(a2amd_ctx *c, LeafPass &lp)
 		int vpw, ysplit;
 		pick_fast_shape(oscpan.count, c->nfrags, &vpw, &ysplit);
 		if(a2d_launch_leaf_oscpan(c->d_params, c->hparams, list + oscpan.first, oscpan.count,
-				vpw, ysplit, c->d_ustage.d, c->stream, lp.solo ? (void *)lp.e1 : nullptr, &pend.c[pend.n]))
+				vpw, ysplit, c->d_ustage.d, c->d_staged.d + oscpan.first, c->stream, lp.solo ? (void *)lp.e1 : nullptr,
+				&pend.c[pend.n]))
 			return c->fail(A2AMD_EHIP, "fast leaf launch failed: %s", hipGetErrorString(hipGetLastError()));
 		if(pend.c[pend.n].nlist)
 			++pend.n;
@@ -1662,7 +1664,7 @@ static int launch_leaves(a2amd_ctx *c, LeafPass &lp)
 		// (its own chunk length; 16 time slices: 2.19 ms against 2.25 with 32 at configs[3], round 3)
 		pick_fast_shape(osc2pan.count, c->nfrags * A2D_FAST_FCH / A2D_OSC2_FCH, &vpw, &ysplit, 16);
 		if(a2d_launch_leaf_osc2pan(c->d_params, c->hparams, list + osc2pan.first, osc2pan.count,
-				vpw, ysplit, c->d_ustage.d, c->stream, &pend.c[pend.n]))
+				vpw, ysplit, c->d_ustage.d, c->d_staged.d + osc2pan.first, c->stream, &pend.c[pend.n]))
 			return c->fail(A2AMD_EHIP, "2-osc leaf launch failed: %s", hipGetErrorString(hipGetLastError()));
 		if(pend.c[pend.n].nlist)
 			++pend.n;
