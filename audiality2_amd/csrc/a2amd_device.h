@@ -395,7 +395,8 @@ int a2d_launch_leaf_osc2pan(const A2DParams *dparams, const A2DParams &hp, const
 // wtosc[+wtosc] [-> filter12] -> panmix voices that carry records this batch (nosc = 1 | 2, filt = 0 | 1)
 // skip_empty: the list's voices get their records from the device VM (a2amd_vm.hip); those it left
 // without any this batch are rendered by their class's quiet kernel
-int a2d_launch_leaf_recs(const A2DParams *dparams, const A2DParams &hp, int nosc, int filt, const int *dlist,
+struct A2Switches;	// (a2amd_switches.h: the launchers' forced shapes)
+int a2d_launch_leaf_recs(const A2Switches &sw, const A2DParams *dparams, const A2DParams &hp, int nosc, int filt, const int *dlist,
 		int nlist, int vpw, void *stream, int skip_empty = 0);
 // Round 5 (a2amd_win.hip): the same voices in two passes.  The control pass (lane = voice) walks the
 // records of fragments [fa, fb) and leaves closed-form window entries: the first window of fragment f for
@@ -409,11 +410,11 @@ int a2d_launch_leaf_recs(const A2DParams *dparams, const A2DParams &hp, int nosc
 int a2d_launch_win_ctl(const A2DParams *dparams, const A2DParams &hp, int nosc, int filt, const int *dlist, int nlist,
 		int skip_empty, int fa, int fb, int *wslot, int *wext, unsigned *widx, unsigned *wtop, unsigned wcap, int *wrc,
 		void *stream);
-int a2d_launch_win_render(const A2DParams &hp, int nosc, int filt, const int *dlist, int nlist, int fa, int fb,
+int a2d_launch_win_render(const A2Switches &sw, const A2DParams &hp, int nosc, int filt, const int *dlist, int nlist, int fa, int fb,
 		const int *wslot, const int *wext, const unsigned *widx, void *stream);
 // ... all four kinds in one launch: lists[k] / counts[k] for (nosc, filt) = (1,0) (2,0) (1,1) (2,1)
 // skip_mask bit k: list k may hold voices without records this batch - their quiet kernel renders those (skip_empty)
-int a2d_launch_leaf_recs_all(const A2DParams *dparams, const A2DParams &hp, const int *const *lists, const int *counts,
+int a2d_launch_leaf_recs_all(const A2Switches &sw, const A2DParams *dparams, const A2DParams &hp, const int *const *lists, const int *counts,
 		int vpw, void *stream, int skip_mask = 0);
 // fm -> panmix leaf voices of ONE unit kind (a2amd_unitkind A2AMD_FM1..FM4R)
 int a2d_launch_leaf_fmpan(const A2DParams *dparams, const A2DParams &hp, int kind, const int *dlist, int nlist,

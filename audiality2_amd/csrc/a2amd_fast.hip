@@ -29,6 +29,7 @@
 #include <algorithm>
 #include <stdlib.h>
 #include "a2amd_device.h"
+#include "a2amd_switches.h"
 #include "a2amd_dsp.h"
 #include "a2amd_fm.h"
 #include "a2amd_filt.h"
@@ -1850,15 +1851,15 @@ void k_leaf_recs_all(const A2DParams *__restrict__ pp, RecsSegs segs, int vpw,
 // chunk to chunk, and the sum of the chunks' maxima was 15-20 % more than the slowest voice's
 // own time; 64 fragments of 512 / 1 024 / 2 048 scripted filter voices: 0.49 / 0.52 / 1.21 ms
 // with one wavefront per workgroup, 0.61 / 0.62 / 0.63 with eight).
-static int recs_wpb(int nwaves)
+static_assert(RECS_WPB == 8, "A2AMD_RECS_WPB's range in a2amd_switches.h");
+static int recs_wpb(int nwaves, int force)
 {
-	static const int force = getenv("A2AMD_RECS_WPB") ? atoi(getenv("A2AMD_RECS_WPB")) : 0;
 	if(force >= 1 && force <= RECS_WPB)
 		return force;
 	return nwaves <= 1024 ? 1 : RECS_WPB;
 }
 
-int a2d_launch_leaf_recs_all(const A2DParams *dparams, const A2DParams &hp, const int *const *lists, const int *counts,
+int a2d_launch_leaf_recs_all(const A2Switches &sw, const A2DParams *dparams, const A2DParams &hp, const int *const *lists, const int *counts,
 		int vpw, void *stream, int skip_mask)
 {
 	RecsSegs segs;
@@ -1866,7 +1867,7 @@ int a2d_launch_leaf_recs_all(const A2DParams *dparams, const A2DParams &hp, cons
 	vpw = min(max(vpw, 1), 64);
 	for(int k = 0; k < 4; ++k)
 		nwaves += (counts[k] + vpw - 1) / vpw;
-	const int wpb = recs_wpb(nwaves);
+	const int wpb = recs_wpb(nwaves, sw.recs_wpb);
 	for(int k = 0; k < 4; ++k) {
 		segs.list[k] = lists[k];
 		segs.count[k] = counts[k];
@@ -1881,7 +1882,7 @@ int a2d_launch_leaf_recs_all(const A2DParams *dparams, const A2DParams &hp, cons
 	return (int)hipGetLastError();
 }
 
-int a2d_launch_leaf_recs(const A2DParams *dparams, const A2DParams &hp, int nosc, int filt, const int *dlist,
+int a2d_launch_leaf_recs(const A2Switches &sw, const A2DParams *dparams, const A2DParams &hp, int nosc, int filt, const int *dlist,
 		int nlist, int vpw, void *stream, int skip_empty)
 {
 	if(nlist <= 0)
@@ -1896,15 +1897,13 @@ int a2d_launch_leaf_recs(const A2DParams *dparams, const A2DParams &hp, int nosc
 	// 16 384: 2.58 / 2.21, 32 768: 4.97 / 5.00, 65 536: 9.7 with it; two oscillators 16 384: 4.29 / 3.88,
 	// 32 768: 8.24 / 6.58 (profiles/r04_jfilt_ab.txt) - hence the threshold.  A2AMD_VFILT=0 / 1
 	// forces it off / on: A/B measurements, and the tests run the path at sizes an oracle can follow.)
-	const char *fv = getenv("A2AMD_VFILT");
-	const int force_vf = fv ? atoi(fv) : -1;
-	const bool vf = filt && (force_vf >= 0 ? force_vf != 0 : nlist >= 16384);
-	if(vf && !getenv("A2AMD_RVPW"))
+	const bool vf = filt && (sw.vfilt >= 0 ? sw.vfilt != 0 : nlist >= 16384);
+	if(vf && !sw.rvpw_set)
 		vpw = min(max((nlist + 4095) / 4096, 4), 8);
 	if(vf)
 		vpw = min(vpw, 16);
 	const int nwaves = (nlist + vpw - 1) / vpw;
-	int wpb = recs_wpb(nwaves);
+	int wpb = recs_wpb(nwaves, sw.recs_wpb);
 	size_t dyn = 0;
 	if(vf) {
 		// the workgroup's static 32 KB (bus sums) + its wavefronts' rows and pools within 64 KB

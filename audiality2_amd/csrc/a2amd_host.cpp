@@ -61,15 +61,7 @@ int a2amd_open(const a2amd_config *cfg, a2amd_ctx **out)
 		c->cfg.max_batch = A2D_MAXBATCH;
 	memset(&c->stats, 0, sizeof(c->stats));
 	build_pitch_table(c->ptab);
-	c->no_fast = getenv("A2AMD_NO_FAST") ? atoi(getenv("A2AMD_NO_FAST")) : 0;
-	c->hosttiming = getenv("A2AMD_HOSTTIMING") != nullptr;
-	c->f2vpw = getenv("A2AMD_F2VPW") ? atoi(getenv("A2AMD_F2VPW")) : 0;
-	c->no_moving = getenv("A2AMD_NO_MOVING") != nullptr;
-	c->noise_quiet = !(getenv("A2AMD_NOISE_QUIET") && !atoi(getenv("A2AMD_NOISE_QUIET")));
-	c->win_slabs = getenv("A2AMD_WIN_SLABS") ? std::max(1, atoi(getenv("A2AMD_WIN_SLABS"))) : 1;
-	c->o2f_min = getenv("A2AMD_O2F_MIN") ? atoi(getenv("A2AMD_O2F_MIN")) : 512;
-	c->nzf_min = getenv("A2AMD_NZF_MIN") ? std::max(1, atoi(getenv("A2AMD_NZF_MIN"))) : A2AMD_NZF_MIN_DEFAULT;
-	c->win_min = getenv("A2AMD_WIN_MIN") ? atoi(getenv("A2AMD_WIN_MIN")) : 2048;
+	a2amd_read_switches(&c->sw);
 	c->bus_stride_frames = (size_t)c->cfg.max_batch * A2D_FRAG;
 	c->bus_used = c->bus_stride_frames * (size_t)c->cfg.channels;	// master bus at offset 0
 #define OPENCHK(call) do { hipError_t e_ = (call); if(e_ != hipSuccess) { \
@@ -176,9 +168,8 @@ int a2amd_get_pitch_table(const a2amd_ctx *c, uint32_t *t)
 namespace a2h {
 void wave_tap_policy(a2amd_ctx *c)
 {
-	const char *e = getenv("A2AMD_RAW"), *m = getenv("A2AMD_COEF_CACHE_MB");
-	const int force = (e && *e) ? atoi(e) : -1;
-	const size_t budget = (size_t)((m && *m) ? atoi(m) : 192) << 20;
+	const int force = c->sw.raw;
+	const size_t budget = (size_t)c->sw.coef_cache_mb << 20;
 	const bool big = c->wavepool_used * (4 * A2D_COEF_WORDS) > budget;
 	for(size_t i = 0; i < c->waves.size(); ++i) {
 		HWave &w = c->waves[i];
@@ -1078,7 +1069,7 @@ int a2amd_unit_write(a2amd_ctx *c, int ui, int reg, int value, unsigned start, u
 				const bool was = leaf_mode(u.mode), is = leaf_mode(nmode);
 				// ... and so does one that moves between a wave and the noise generator (CLS_NOISEPAN, CLS_NOISEFILTPAN:
 				// any wtosc of any chain, a2amd_sched.cpp)
-				if(was != is || (c->noise_quiet && (u.mode == A2D_OSC_NOISE) != (nmode == A2D_OSC_NOISE)))
+				if(was != is || (c->sw.noise_quiet && (u.mode == A2D_OSC_NOISE) != (nmode == A2D_OSC_NOISE)))
 					c->lists_dirty = true;
 				if(!was || !is)
 					c->voices[u.voice].mode_mix = true;
@@ -1480,8 +1471,7 @@ int a2amd_unit_process(a2amd_ctx *c, int ui, unsigned offset, unsigned frames, u
 			shadow_run_pitch(c, u, frames);
 			uint64_t end = u.phase + (uint64_t)frames * u.dphase;
 			uint64_t draws = u.dphase >= (1u << 23) ? frames : (end >> 23) - (u.phase >> 23);
-			static const bool trace = getenv("A2AMD_DEBUG_NOISE") != nullptr;	// (debugging aid: the test
-			if(trace)								// suite's checker prints the same line)
+			if(c->sw.debug_noise)		// (debugging aid: the test suite's checker prints the same line)
 				fprintf(stderr, "NOISE phase %llx dphase %x frames %u\n", (unsigned long long)u.phase, u.dphase, frames);
 			uint32_t st = *noisestate;
 			for(uint64_t i = 0; i < draws; ++i)
@@ -1570,7 +1560,7 @@ int a2amd_voice_process(a2amd_ctx *c, int head, unsigned offset, unsigned frames
 	unhold(c, vi);
 	if(!pv.plain)
 		classify_plain(c, pv);
-	static const int dbgw = getenv("A2AMD_DBG_WALK") ? atoi(getenv("A2AMD_DBG_WALK")) : 0;
+	const int dbgw = c->sw.dbg_walk;
 	if(pv.plain == 1 && !(dbgw & 1)) {
 		// The short path: one pass of bookkeeping for the whole chain (what
 		// a2amd_unit_process does unit by unit) and the window - unrecorded if it is

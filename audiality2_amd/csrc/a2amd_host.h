@@ -23,6 +23,7 @@
 #include "../../include/a2amd.h"
 #include "../../include/a2amd_vm.h"
 #include "a2amd_device.h"
+#include "a2amd_switches.h"
 
 #ifndef M_PI
 #define M_PI 3.14159265358979323846
@@ -248,12 +249,11 @@ static const struct { int8_t leaf, dyn; } cls_lists[CLS_N] = {
 	{ LEAF_NOISEPAN, DYN_OSC1 },
 	// wtosc (noise)-filter12-panmix: likewise, k_leaf_noisefiltpan's; with records a one-oscillator filter voice like any other
 	{ LEAF_NOISEFILTPAN, DYN_FILT } };
-// wtosc (noise)-filter12-panmix voices without a record in a batch from which k_leaf_noisefiltpan takes them (a2amd_ctx::nzf_min,
-// A2AMD_NZF_MIN): a launch lasts as long as its filter wavefront's chain through the batch however few of its lanes are
+// wtosc (noise)-filter12-panmix voices without a record in a batch from which k_leaf_noisefiltpan takes them (A2Switches::nzf_min,
+// A2AMD_NZF_MIN, 64): a launch lasts as long as its filter wavefront's chain through the batch however few of its lanes are
 // busy, behind the window kernels on the context's one stream, which render a few such voices inside the launch they make
 // anyway (A2AMD_O2F_MIN's lesson, upload()).  Never below 16.  NOT MEASURED: 64 is one filter wavefront with every lane busy
 // (profiles/noise_filt_quiet.md).
-#define A2AMD_NZF_MIN_DEFAULT 64
 
 // host side of an xinsert client slot
 struct XioSlot {
@@ -516,24 +516,13 @@ struct a2amd_ctx {
 	int fm_kind_count[8] = { 0 };		// ... and leaf[LEAF_FMPAN]'s voices by unit kind
 	std::vector<DepthRange> depth_ranges;	// index = depth
 	ListRange dyn[DYN_N];			// this batch's leaf exceptions in d_dyn
-	bool hosttiming = false;		// A2AMD_HOSTTIMING
-	int no_fast = 0;			// A2AMD_NO_FAST bit mask: 1 wtosc-panmix, 2 wtosc-filter12-panmix, 4 driver chains -> general kernel (debugging / A-B tests)
-	// Switches the tests vary from context to context inside one process: read in a2amd_open(), never through a
-	// function-local static (which keeps the value the first context of the process saw; tests/test_switches.py)
-	int f2vpw = 0;				// A2AMD_F2VPW: voices per workgroup of k_leaf_osc2filtpan (0: the launcher's own choice)
-	bool no_moving = false;			// A2AMD_NO_MOVING: gliding voices get no stand-in record (they stay the quiet kernels')
-	bool noise_quiet = true;		// A2AMD_NOISE_QUIET=0: no launch classes for wtosc (noise)-[filter12-]panmix voices - they are wtosc-[filter12-]panmix
-						// voices, and every noise voice of a device-seeded batch gets the stand-in record (A/B)
-	int win_slabs = 1;			// A2AMD_WIN_SLABS: slabs a batch of 16 fragments or more is cut into for the window kernels
-	int o2f_min = 512;			// A2AMD_O2F_MIN: voices of 2 x wtosc-filter12-panmix from which the class has its quiet kernel
-	int win_min = 2048;			// A2AMD_WIN_MIN: record-carrying voices from which the window kernels take over from k_leaf_recs
+	A2Switches sw;				// the A2AMD_* switches as a2amd_open() found them (a2amd_switches.h)
 	a2amd_batch_info last_batch = {};	// a2amd_last_batch()
 	a2amd_noise_batch_info last_noise = {};	// a2amd_last_batch_noise()
 	uint32_t n_noise_standin = 0, n_noise_quiet = 0;	// upload(): noise voices given the stand-in run / left to k_leaf_noisepan
-	// wtosc (noise)-filter12-panmix: voices left to k_leaf_noisefiltpan this batch, and the number of such voices IN A BATCH
-	// from which the class has its quiet kernel (A2AMD_NZF_MIN; below it every one of them takes the stand-in run)
+	// wtosc (noise)-filter12-panmix: voices left to k_leaf_noisefiltpan this batch (from sw.nzf_min such voices IN A BATCH on;
+	// below it every one of them takes the stand-in run)
 	uint32_t n_noise_filt_quiet = 0;
-	int nzf_min = A2AMD_NZF_MIN_DEFAULT;
 	a2amd_noise_filter_batch_info last_noise_filter = {};	// a2amd_last_batch_noise_filter()
 	// a2amd_last_batch_buses(): upload() fills in who renders the bus owners, launch_depth() what it was told to
 	// consume (a graph: gconsume, as at its capture); master_direct is the context's own flag

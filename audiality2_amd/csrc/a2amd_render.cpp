@@ -14,11 +14,12 @@ static double now_us()
 static double g_t[4], g_n;
 static double g_why[13];
 static double g_cnt[6];		// quiet uploads, records shipped, walk scans, R_NOPs, voices with records, graph launches
-struct TimingDump { ~TimingDump() { if(getenv("A2AMD_HOSTTIMING") && g_n) fprintf(stderr,
+struct TimingDump { ~TimingDump() {	// (at process exit, no context left: the one read of the switches outside a2amd_open())
+	A2Switches sw; a2amd_read_switches(&sw); if(sw.hosttiming && g_n) fprintf(stderr,
 	"a2amd host timing per render: upload %.1f us, issue %.1f us, readback %.1f us (%g renders; %g quiet uploads, "
 	"%g graph launches, %g records, %g voices with records, %g walk scans, %g R_NOPs)\n",
 	g_t[0] / g_n, g_t[1] / g_n, g_t[2] / g_n, g_n, g_cnt[0], g_cnt[5], g_cnt[1], g_cnt[4], g_cnt[2], g_cnt[3]);
-	if(getenv("A2AMD_HOSTTIMING") && g_n) { fprintf(stderr, "a2amd uploads by first reason against the quiet path "
+	if(sw.hosttiming && g_n) { fprintf(stderr, "a2amd uploads by first reason against the quiet path "
 	"(blob, recs, prev recs, voices, udesc, waves, lists, ptab, dirty voices, fbd, nfrags, bus, none):");
 	for(int k = 0; k < 13; ++k) fprintf(stderr, " %g", g_why[k]); fprintf(stderr, "\n"); } } } g_timing_dump;
 
@@ -53,7 +54,7 @@ extern "C" {
 int a2amd_render(a2amd_ctx *c, unsigned phases, int32_t *const *out, unsigned cap)
 {
 	use_device(c);
-	const bool timing = c->hosttiming;	// (debug aid; the accumulators are process-wide and not thread safe)
+	const bool timing = c->sw.hosttiming;	// (debug aid; the accumulators are process-wide and not thread safe)
 	double t0 = timing ? now_us() : 0;
 	if(!c->stack.empty())
 		return c->fail(A2AMD_ESTATE, "render inside an inline window");
@@ -106,12 +107,11 @@ int a2amd_render(a2amd_ctx *c, unsigned phases, int32_t *const *out, unsigned ca
 	int gv = 0;		// graph variant: the destination is an argument of the root's kernel
 	{
 		const unsigned both = A2AMD_RENDER_SUBTREES | A2AMD_RENDER_ROOT;
-		static const bool off = getenv("A2AMD_NO_DIRECT") != nullptr;
 		bool taps = false;
 		for(const XioSlot &x : c->xio)
 			if(x.unit >= 0 && x.tapped)
 				taps = true;
-		if(!off && (phases & A2AMD_RENDER_READBACK) && (phases & both) == both && !(phases & A2AMD_RENDER_KEEP) &&
+		if(!c->sw.no_direct && (phases & A2AMD_RENDER_READBACK) && (phases & both) == both && !(phases & A2AMD_RENDER_KEEP) &&
 				!(phases & A2AMD_RENDER_TAPS) && !c->comm && !c->dist_local && c->uploaded && c->with_recs.empty() &&
 				c->consume_ok && c->sub_resume < 0 && !c->paused_at && !taps) {
 			const size_t n = (size_t)c->nfrags * c->cfg.channels * A2D_FRAG;
@@ -150,7 +150,7 @@ int a2amd_render(a2amd_ctx *c, unsigned phases, int32_t *const *out, unsigned ca
 	auto run_phases = [&](unsigned kphases) -> int {
 		if(!kphases)
 			return 0;
-		if(c->uploaded && !c->profiling && c->stream && c->with_recs.empty() && !getenv("A2AMD_NO_GRAPH") &&
+		if(c->uploaded && !c->profiling && c->stream && c->with_recs.empty() && !c->sw.no_graph &&
 				c->vm.list.empty() &&	// (the VM's passes meet the host in between: not for a graph)
 				!(phases & A2AMD_RENDER_TAPS) && c->sub_resume < 0 && !c->paused_at &&
 				((phases & A2AMD_RENDER_KEEP) ? (phases & ~A2AMD_RENDER_KEEP) ==
@@ -168,7 +168,7 @@ int a2amd_render(a2amd_ctx *c, unsigned phases, int32_t *const *out, unsigned ca
 				HIPCHK(c, hipGraphLaunch(c->gexec[gi], c->stream));
 				c->master_direct = c->gdirect[gi];	// (what the captured launch did)
 				c->last_bus.consume = c->gconsume[gi];
-				if(c->hosttiming)
+				if(c->sw.hosttiming)
 					dbg_counters()[5] += 1;
 				if(slot == 1)
 					c->others_clean = c->root_clean = c->consume_ok;
@@ -307,8 +307,7 @@ int a2amd_render(a2amd_ctx *c, unsigned phases, int32_t *const *out, unsigned ca
 		HIPCHK(c, hipStreamSynchronize(c->stream));
 		if(timing) {
 			g_t[2] += now_us() - t2;
-			static const int trace = getenv("A2AMD_HOSTTIMING") ? atoi(getenv("A2AMD_HOSTTIMING")) : 0;
-			if(trace >= 2)
+			if(c->sw.hosttiming_level >= 2)
 				fprintf(stderr, "a2amd render: %d fragments, upload %.1f us, issue %.1f us, readback %.1f us\n",
 						c->nfrags, t1 - t0, t2 - t1, now_us() - t2);
 		}
@@ -369,7 +368,7 @@ int a2amd_replay(a2amd_ctx *c, unsigned steps)
 	for(int vi = 0; vi < (int)c->voices.size(); ++vi)
 		if(!c->voices[vi].recs.empty())
 			return c->fail(A2AMD_ESTATE, "replay of a batch that carries command records");
-	bool graphs = c->stream != nullptr && !c->profiling && !getenv("A2AMD_NO_GRAPH") && c->vm.list.empty();
+	bool graphs = c->stream != nullptr && !c->profiling && !c->sw.no_graph && c->vm.list.empty();
 	c->master_dst = nullptr;	// (replayed steps are not read back: the master bus stays in the bus memory)
 	c->master_direct = false;
 	if(graphs && (!c->gexec[0] || !c->gexec[1])) {
@@ -466,7 +465,7 @@ int a2amd_last_batch_noise_filter(const a2amd_ctx *c, a2amd_noise_filter_batch_i
 	if(!c || !out)
 		return A2AMD_EINVAL;
 	*out = c->last_noise_filter;
-	out->min_voices = (uint32_t)c->nzf_min;
+	out->min_voices = (uint32_t)c->sw.nzf_min;
 	return A2AMD_OK;
 }
 

@@ -115,7 +115,7 @@ int close_fragment(a2amd_ctx *c)
 	}
 	c->walked_started += (int)c->n_held;
 	if(c->walked_started != c->n_started_live) {
-		if(c->hosttiming)
+		if(c->sw.hosttiming)
 			dbg_counters()[2] += 1;
 		// a live voice got no Process call this fragment: say so, or
 		// the kernel would apply the default
@@ -134,7 +134,7 @@ int close_fragment(a2amd_ctx *c)
 				}
 				v.recs.push_back(r);
 				v.touched = c->serial_base + f;
-				if(c->hosttiming)
+				if(c->sw.hosttiming)
 					dbg_counters()[3] += 1;
 			}
 		}
@@ -342,7 +342,7 @@ int upload(a2amd_ctx *c)
 	// (a2amd_last_batch_buses(): the lists of a quiet batch are the last upload's - nobody ramps, nothing is dropped)
 	c->n_bus_windows_dropped = 0;
 	c->last_bus.driver_ramping = c->last_bus.driver_windows_dropped = 0;
-	if(c->hosttiming) {
+	if(c->sw.hosttiming) {
 		// (A2AMD_HOSTTIMING: why a batch did not take the quiet path - first reason that applies)
 		const int why = !c->blob_quiet ? 0 : !c->with_recs.empty() ? 1 : !c->prev_with_recs.empty() ? 2 :
 				c->voices_dirty ? 3 : c->udesc_dirty ? 4 : c->waves_dirty ? 5 : c->lists_dirty ? 6 : c->ptab_dirty ? 7 :
@@ -362,7 +362,7 @@ int upload(a2amd_ctx *c)
 				!memcmp(c->fragframes, c->blob_frames, (size_t)c->nfrags * sizeof(unsigned));
 		if(!inject && same) {
 			// the same quiet batch again: the device has it all (graphs stay valid)
-			if(c->hosttiming)
+			if(c->sw.hosttiming)
 				dbg_counters()[0] += 1;
 			++c->quiet_streak;
 			c->uploaded = true;
@@ -407,7 +407,7 @@ int upload(a2amd_ctx *c)
 					++c->quiet_streak;
 				c->blob_nfrags = c->nfrags;
 				memcpy(c->blob_frames, c->fragframes, (size_t)c->nfrags * sizeof(unsigned));
-				if(c->hosttiming)
+				if(c->sw.hosttiming)
 					dbg_counters()[0] += 1;
 				c->uploaded = true;
 				return 0;
@@ -544,7 +544,6 @@ int upload(a2amd_ctx *c)
 		now.resize(c->with_recs.size());
 	}
 	size_t nsc_used = 0, nnow = 0;
-	static const bool keep_bus_windows = getenv("A2AMD_BUS_WINDOWS") != nullptr;	// (A/B: round 4's routing)
 	for(int vi : c->with_recs) {
 		HVoice &v = c->voices[vi];
 		if(v.recs.empty()) {
@@ -556,7 +555,7 @@ int upload(a2amd_ctx *c)
 		// rest: the windows change nothing (a2_PrepareRamper with no ramp under way sets the same gains for every window,
 		// a2_dsp.h:128-133; inline, panmix and xinsert keep no state from frame to frame), so it stays with the bus
 		// kernel of its depth instead of going to the general kernel - one wavefront that is as long as the batch.
-		if(!keep_bus_windows && v.inline_pos >= 0 && v.vm < 0 && v.moving_until <= c->vm.batch_time && !(c->no_fast & 4) &&
+		if(!c->sw.bus_windows && v.inline_pos >= 0 && v.vm < 0 && v.moving_until <= c->vm.batch_time && !(c->sw.no_fast & 4) &&
 				v.resolved && is_driver_chain(c, v)) {
 			bool only_windows = true;
 			for(const A2DRec &r : v.recs)
@@ -581,7 +580,6 @@ int upload(a2amd_ctx *c)
 	// unsettled voice fragment by fragment on the scalar unit for the whole batch; the window kernels resolve its
 	// rampers in closed form.  They are given ONE shared stand-in record that belongs to no fragment - a run the
 	// quiet kernels skip and the control pass never consumes: default windows throughout.
-	const bool no_moving = c->no_moving;
 	c->n_moving_listed = 0;
 	int nop_at = -1;
 	// the stand-in run for voice vi (no records of its own this batch): used for gliding voices here and for
@@ -620,7 +618,7 @@ int upload(a2amd_ctx *c)
 			// (a voice slot that was recycled while it stood in the list stands in it twice)
 			if(v.moving_run == c->serial_base)
 				continue;
-			if(no_moving || !v.recs.empty() || v.vm >= 0 || c->lists_dirty || v.mode_mix || !v.resolved ||
+			if(c->sw.no_moving || !v.recs.empty() || v.vm >= 0 || c->lists_dirty || v.mode_mix || !v.resolved ||
 					!(v.cls == CLS_OSCPAN || v.cls == CLS_OSC2PAN || v.cls == CLS_OSCFILTPAN || v.cls == CLS_OSC2FILTPAN))
 				continue;
 			give_stand_in(vi);
@@ -669,7 +667,7 @@ int upload(a2amd_ctx *c)
 		const uint64_t t0 = c->vm.batch_time;
 		// a voice a quiet noise kernel may take: which of the two classes (0: neither)
 		auto quiet_cls = [&](const HVoice &v) {
-			return c->noise_quiet && (v.cls == CLS_NOISEPAN || v.cls == CLS_NOISEFILTPAN) && !v.cls_stale && v.resolved &&
+			return c->sw.noise_quiet && (v.cls == CLS_NOISEPAN || v.cls == CLS_NOISEFILTPAN) && !v.cls_stale && v.resolved &&
 					v.vm < 0 && v.recs.empty() && (v.live || v.dying) && v.moving_until <= t0 && v.cut_run != c->serial_base ?
 					v.cls : 0;
 		};
@@ -679,7 +677,7 @@ int upload(a2amd_ctx *c)
 			const HVoice &v = c->voices[c->units[o.unit].voice];
 			nfilt += v.noise_run != c->serial_base && v.moving_run != c->serial_base && quiet_cls(v) == CLS_NOISEFILTPAN;
 		}
-		const bool filt_quiet = nfilt >= c->nzf_min;
+		const bool filt_quiet = nfilt >= c->sw.nzf_min;
 		for(const A2DNoiseOsc &o : c->noise_osc) {
 			const int vi = c->units[o.unit].voice;
 			HVoice &v = c->voices[vi];
@@ -716,15 +714,15 @@ int upload(a2amd_ctx *c)
 	sc_val.resize(nsc_used);
 	c->prev_with_recs.clear();
 	c->stats.records += recs.size();
-	if(c->hosttiming) {
+	if(c->sw.hosttiming) {
 		dbg_counters()[1] += (double)recs.size();
 		dbg_counters()[4] += (double)c->with_recs.size();
 	}
 
 	// Launch lists (a2amd_host.h: ListRange).  Static part, rebuilt when the voice tree changes: every listed voice by class.
 	if(c->lists_dirty) {
-		static const bool cls_check = getenv("A2AMD_CLS_CHECK") != nullptr;
-		bool owners_ok = !getenv("A2AMD_NO_SELFCLEAN"), root_driver = false;
+		const bool cls_check = c->sw.cls_check;
+		bool owners_ok = !c->sw.no_selfclean, root_driver = false;
 		std::vector<int> leaf[LEAF_N];
 		std::map<int, std::pair<std::vector<int>, std::vector<int>>> bydepth;
 		std::map<int, std::vector<int>> fbd_bydepth;
@@ -746,8 +744,8 @@ int upload(a2amd_ctx *c)
 			if(v.inline_pos >= 0) {
 				auto &d = bydepth[v.depth];
 				if(classify)
-					v.cls = !(c->no_fast & 4) && is_driver_chain(c, v) ? CLS_BUSDRIVER :
-							!(c->no_fast & 32) && v.depth > 0 && is_fbdchain(c, v) ? CLS_FBDCHAIN : CLS_BUSGENERIC;
+					v.cls = !(c->sw.no_fast & 4) && is_driver_chain(c, v) ? CLS_BUSDRIVER :
+							!(c->sw.no_fast & 32) && v.depth > 0 && is_fbdchain(c, v) ? CLS_FBDCHAIN : CLS_BUSGENERIC;
 				// (the master bus at offset 0 is the root's alone)
 				if(v.cls == CLS_BUSGENERIC || (v.out_off == 0) != (v.depth == 0))
 					owners_ok = false;
@@ -757,17 +755,17 @@ int upload(a2amd_ctx *c)
 				maxdepth = std::max(maxdepth, v.depth);
 			} else {
 				if(classify)
-					v.cls = !(c->no_fast & 1) && is_oscpan_chain(c, v) ?
+					v.cls = !(c->sw.no_fast & 1) && is_oscpan_chain(c, v) ?
 								// (the noise generator: a class of its own, k_leaf_noisepan - a 'w' write marks the class stale)
-								(c->noise_quiet && c->units[v.unit[0]].mode == A2D_OSC_NOISE ? CLS_NOISEPAN : CLS_OSCPAN) :
-							!(c->no_fast & 8) && is_osc2pan_chain(c, v) ? CLS_OSC2PAN :
-							!(c->no_fast & 2) && is_oscfiltpan_chain(c, v) ?
+								(c->sw.noise_quiet && c->units[v.unit[0]].mode == A2D_OSC_NOISE ? CLS_NOISEPAN : CLS_OSCPAN) :
+							!(c->sw.no_fast & 8) && is_osc2pan_chain(c, v) ? CLS_OSC2PAN :
+							!(c->sw.no_fast & 2) && is_oscfiltpan_chain(c, v) ?
 								// (likewise: k_leaf_noisefiltpan's, whatever their number - upload() counts them batch by batch)
-								(c->noise_quiet && c->units[v.unit[0]].mode == A2D_OSC_NOISE ? CLS_NOISEFILTPAN : CLS_OSCFILTPAN) :
+								(c->sw.noise_quiet && c->units[v.unit[0]].mode == A2D_OSC_NOISE ? CLS_NOISEFILTPAN : CLS_OSCFILTPAN) :
 							// (no quiet kernel of its own: k_leaf_recs renders it, records or not - unless an
 							// oscillator leaves the mip-mapped waves somewhere in this batch)
-							!(c->no_fast & 128) && !v.mode_mix && is_osc2filtpan_chain(c, v) ? CLS_OSC2FILTPAN :
-							!(c->no_fast & 16) && is_fmpan_chain(c, v) ? CLS_FMPAN : CLS_GENERIC;
+							!(c->sw.no_fast & 128) && !v.mode_mix && is_osc2filtpan_chain(c, v) ? CLS_OSC2FILTPAN :
+							!(c->sw.no_fast & 16) && is_fmpan_chain(c, v) ? CLS_FMPAN : CLS_GENERIC;
 				if(v.out_off == 0)
 					owners_ok = false;	// adds straight into the master bus
 				leaf[cls_lists[v.cls].leaf].push_back((int)vi);
@@ -825,11 +823,10 @@ int upload(a2amd_ctx *c)
 		// general kernel.
 		std::vector<int> dyn[DYN_N];
 		std::vector<std::vector<int>> dyn_bus(c->depth_ranges.size());
-		const bool no_recs_kernel = (c->no_fast & 64) != 0;
-		static const bool dump = getenv("A2AMD_VM_DUMP") != nullptr;	// (debugging aid: the records of a batch, host-made ...)
+		const bool no_recs_kernel = (c->sw.no_fast & 64) != 0;
 		for(int vi : c->with_recs) {
 			HVoice &v = c->voices[vi];
-			if(dump)
+			if(c->sw.vm_dump)	// (debugging aid: the records of a batch, host-made ...)
 				for(const A2DRec &r : v.recs)
 					fprintf(stderr, "REC %lld v%d f%u op%u u%u r%u val %d dur %u start %u\n", c->serial_base, vi,
 							A2D_RFRAG(r.head), A2D_ROP(r.head), A2D_RUNIT(r.head), A2D_RREG(r.head), r.value, r.dur, r.start);
@@ -845,8 +842,7 @@ int upload(a2amd_ctx *c)
 				dyn[ok ? cls_lists[v.cls].dyn : DYN_REST].push_back(vi);
 			} else if((v.cls == CLS_BUSDRIVER || v.cls == CLS_FBDCHAIN) && v.depth < (int)dyn_bus.size()) {
 				dyn_bus[v.depth].push_back(vi);
-				static const int trace = getenv("A2AMD_HOSTTIMING") ? atoi(getenv("A2AMD_HOSTTIMING")) : 0;
-				if(trace >= 3 && !v.recs.empty())
+				if(c->sw.hosttiming_level >= 3 && !v.recs.empty())
 					fprintf(stderr, "a2amd: bus voice %d (depth %d, class %d) carries %zu records, first: frag %u op %u unit %u reg %u value %d\n",
 							vi, v.depth, v.cls, v.recs.size(), A2D_RFRAG(v.recs[0].head), A2D_ROP(v.recs[0].head),
 							A2D_RUNIT(v.recs[0].head), A2D_RREG(v.recs[0].head), v.recs[0].value);
@@ -872,7 +868,7 @@ int upload(a2amd_ctx *c)
 		// profiles/r06_song_timing.jsonl).  Below A2AMD_O2F_MIN voices of the class (default 512) every voice of it is the
 		// records / window kernels', as in rounds 2 - 5.
 		const ListRange o2f = c->leaf[LEAF_OSC2FILTPAN];
-		c->o2f_quiet = o2f.count >= c->o2f_min;
+		c->o2f_quiet = o2f.count >= c->sw.o2f_min;
 		if(!c->o2f_quiet)
 			for(int k = 0; k < o2f.count; ++k) {
 				const int vi = c->list_all[o2f.first + k];
@@ -954,7 +950,7 @@ int upload(a2amd_ctx *c)
 	}
 	p.nfrags = c->nfrags;
 	p.samplerate = c->cfg.samplerate;
-	p.debug = getenv("A2AMD_DEBUG") ? atoi(getenv("A2AMD_DEBUG")) : 0;
+	p.debug = c->sw.debug;
 	for(int f = 0, acc = 0; f < c->nfrags; ++f) {
 		p.fragframes[f] = (uint8_t)c->fragframes[f];
 		p.fragstart[f] = (uint16_t)acc;
@@ -1057,12 +1053,12 @@ int upload(a2amd_ctx *c)
 // (up to 8), then give a wavefront enough voices that about 4096 wavefronts
 // (one resident round of 256 CUs x 16) share the work; at least 4 voices, so
 // that their sum reaches the bus in one atomic instead of four, at most 32.
-void pick_fast_shape(int n, int nfrags, int *vpw, int *ysplit, int ymax = 32)
+void pick_fast_shape(const A2Switches &sw, int n, int nfrags, int *vpw, int *ysplit, int ymax = 32)
 {
 	const int nchunks = (nfrags + A2D_FAST_FCH - 1) / A2D_FAST_FCH;
-	int y = getenv("A2AMD_YSPLIT") ? atoi(getenv("A2AMD_YSPLIT")) : ymax;
+	int y = sw.ysplit_set ? sw.ysplit : ymax;
 	y = std::min(std::max(y, 1), nchunks);
-	int v = getenv("A2AMD_VPW") ? atoi(getenv("A2AMD_VPW")) :
+	int v = sw.vpw_set ? sw.vpw :
 			std::min(std::max((int)(((long long)n * y + 4095) / 4096), 4), 32);
 	*vpw = std::min(std::max(v, 1), 64);
 	*ysplit = y;
@@ -1306,19 +1302,17 @@ static int issue_windows(a2amd_ctx *c, const int *d_dyn, const ListRange *dyn, c
 					c->h_wtop[0], c->h_wtop[2], c->d_wext.cap);
 		}
 	}
-	static const size_t budget = (size_t)(getenv("A2AMD_WIN_MB") ? atoi(getenv("A2AMD_WIN_MB")) : 1024) * (1u << 20) /
-			(A2D_WIN_WORDS * sizeof(int)) / 2;
+	const size_t budget = (size_t)c->sw.win_mb * (1u << 20) / (A2D_WIN_WORDS * sizeof(int)) / 2;
 	// Slabs: the control pass (lane = voice: a few hundred wavefronts, each as long as its voices' walk) of slab
 	// k + 1 runs on a stream of its own beside the render pass of slab k - two sets of slots and pools.  A batch
 	// of 16 fragments or more is cut into four slabs (A2AMD_WIN_SLABS), a shorter one is one slab.
 	// (measured, 16 384 scripted voices x 64 fragments: 0.50 ms as one slab, 0.76 as four - the control pass is as
 	// long as ONE wavefront's walk, and a wavefront that shares its SIMD with seven render wavefronts walks at a
 	// fraction of its pace - so slabs are what the memory bound asks for, not the default)
-	const int want_slabs = c->win_slabs;
 	const int nfrags = c->nfrags;
 	// (a taken speculative pass covers the batch in one piece: with it, the lists that do take slots here are not cut
 	// into slabs for the asking - A2AMD_WIN_SLABS - only where the memory bound demands it)
-	int per = nfrags >= 16 && !spec ? (nfrags + want_slabs - 1) / want_slabs : nfrags;
+	int per = nfrags >= 16 && !spec ? (nfrags + c->sw.win_slabs - 1) / c->sw.win_slabs : nfrags;
 	if(nvoices && nvoices * (size_t)per > budget)
 		per = (int)std::max<size_t>(1, budget / nvoices);
 	const int nslabs = (nfrags + per - 1) / per;
@@ -1390,9 +1384,7 @@ static int issue_windows(a2amd_ctx *c, const int *d_dyn, const ListRange *dyn, c
 					wslot, wext, wscr, widx, wtop, wcap, st);
 		} else
 			r = a2d_launch_win_ctl(c->d_params, c->hparams, b.nosc, b.filt, b.list, b.n, b.skip, fa, fb, wslot, wext, widx, wtop, wcap, wrc, st);
-		// (A2AMD_WIN_SYNC=1, debugging: wait for every launch and say so - the last line names the kernel that faulted)
-		static const bool dbgsync = getenv("A2AMD_WIN_SYNC") != nullptr;
-		if(dbgsync && !r && !c->capturing) {
+		if(c->sw.win_sync && !r && !c->capturing) {
 			const hipError_t e = hipStreamSynchronize(st);
 			fprintf(stderr, "a2amd windows: control pass <%d,%d> %s of %d voices, fragments [%d, %d): %s\n", b.nosc, b.filt,
 					b.spec ? "k_vm_commit (speculative pass taken)" : b.vmk >= 0 ? "k_vm_win" : "k_win_ctl", b.n, fa, fb,
@@ -1400,15 +1392,14 @@ static int issue_windows(a2amd_ctx *c, const int *d_dyn, const ListRange *dyn, c
 		}
 		return r;
 	};
-	static const bool wtiming = getenv("A2AMD_WIN_TIMING") != nullptr;
+	const bool wtiming = c->sw.win_timing;
 	static hipEvent_t tev[3] = { nullptr, nullptr, nullptr };
 	// Several lists, one slab (a song: a few dozen voices of four classes): each list's control pass and render
 	// pass are kernels of a few wavefronts that take as long as one voice's walk / one filter chain - on one stream
 	// they would run back to back; here every list gets a stream of its own between a fork and a join (the render
 	// passes only ever ADD to the buses).  A2AMD_WIN_FORK=0: one stream.
-	static const bool fork_ok = !(getenv("A2AMD_WIN_FORK") && !atoi(getenv("A2AMD_WIN_FORK")));
 	bool forked = false;
-	if(nj > 1 && nslabs == 1 && fork_ok && !wtiming) {
+	if(nj > 1 && nslabs == 1 && c->sw.win_fork && !wtiming) {
 		if(!c->win_fork[0]) {
 			if(c->capturing)
 				return c->fail(A2AMD_ESTATE, "window streams missing inside a graph capture");
@@ -1429,9 +1420,9 @@ static int issue_windows(a2amd_ctx *c, const int *d_dyn, const ListRange *dyn, c
 			if(control(b, 0, nfrags, c->d_win.d + atw, c->d_wext.d, c->d_widx.d + at, c->d_wtop,
 					(unsigned)std::min<size_t>(c->d_wext.cap, 0xffffffffu), c->d_wrc.d + atv, sj))
 				return c->fail(A2AMD_EHIP, "window control launch failed: %s", hipGetErrorString(hipGetLastError()));
-			if(b.spec ? a2d_launch_win_render(c->hparams, b.nosc, b.filt, b.list, b.n, 0, nfrags, c->vm.d_swin[sset].d + b.satw,
+			if(b.spec ? a2d_launch_win_render(c->sw, c->hparams, b.nosc, b.filt, b.list, b.n, 0, nfrags, c->vm.d_swin[sset].d + b.satw,
 						c->vm.d_swext[sset].d, c->vm.d_swidx[sset].d + b.sat, sj) :
-					a2d_launch_win_render(c->hparams, b.nosc, b.filt, b.list, b.n, 0, nfrags, c->d_win.d + atw,
+					a2d_launch_win_render(c->sw, c->hparams, b.nosc, b.filt, b.list, b.n, 0, nfrags, c->d_win.d + atw,
 						c->d_wext.d, c->d_widx.d + at, sj))
 				return c->fail(A2AMD_EHIP, "window render launch failed: %s", hipGetErrorString(hipGetLastError()));
 			HIPCHK(c, hipEventRecord(c->win_fev[j], sj));
@@ -1496,14 +1487,14 @@ static int issue_windows(a2amd_ctx *c, const int *d_dyn, const ListRange *dyn, c
 			const Job &b = jobs[j];
 			if(b.spec) {
 				// (the whole batch at once, behind the first slab's control passes - the commit among them)
-				if(fa == 0 && a2d_launch_win_render(c->hparams, b.nosc, b.filt, b.list, b.n, 0, nfrags, c->vm.d_swin[sset].d + b.satw,
+				if(fa == 0 && a2d_launch_win_render(c->sw, c->hparams, b.nosc, b.filt, b.list, b.n, 0, nfrags, c->vm.d_swin[sset].d + b.satw,
 						c->vm.d_swext[sset].d, c->vm.d_swidx[sset].d + b.sat, c->stream))
 					return c->fail(A2AMD_EHIP, "window render launch failed: %s", hipGetErrorString(hipGetLastError()));
 				if(fa == 0)
 					++c->stats.launches;
 				continue;
 			}
-			if(a2d_launch_win_render(c->hparams, b.nosc, b.filt, b.list, b.n, fa, fb, wslot + atw,
+			if(a2d_launch_win_render(c->sw, c->hparams, b.nosc, b.filt, b.list, b.n, fa, fb, wslot + atw,
 					wext, widx + at, c->stream))
 				return c->fail(A2AMD_EHIP, "window render launch failed: %s", hipGetErrorString(hipGetLastError()));
 			at += (size_t)b.n * (size_t)(fb - fa);
@@ -1539,8 +1530,7 @@ static int issue_windows(a2amd_ctx *c, const int *d_dyn, const ListRange *dyn, c
 	if(c->vm.fused && !c->vm.spec_use)	// (a pass that met a fault is not taken: vm_issue)
 		if(int r = vm_fused_done(c))
 			return r;
-	static const bool check = getenv("A2AMD_WIN_CHECK") != nullptr;
-	if(check && !c->capturing && plain_jobs) {
+	if(c->sw.win_check && !c->capturing && plain_jobs) {
 		unsigned top[4] = { 0, 0, 0, 0 };
 		HIPCHK(c, hipMemcpyAsync(top, c->d_wtop, sizeof(top), hipMemcpyDeviceToHost, c->stream));
 		HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1567,8 +1557,8 @@ static int launch_recs(a2amd_ctx *c, int nosc, int filt, const int *list, int n,
 {
 	if(!n)
 		return 0;
-	const int vpw = getenv("A2AMD_RVPW") ? atoi(getenv("A2AMD_RVPW")) : (n + 8191) / 8192;
-	if(a2d_launch_leaf_recs(c->d_params, c->hparams, nosc, filt, list, n, vpw, c->stream, skip_empty))
+	const int vpw = c->sw.rvpw_set ? c->sw.rvpw : (n + 8191) / 8192;
+	if(a2d_launch_leaf_recs(c->sw, c->d_params, c->hparams, nosc, filt, list, n, vpw, c->stream, skip_empty))
 		return c->fail(A2AMD_EHIP, "leaf records launch failed: %s", hipGetErrorString(hipGetLastError()));
 	++c->stats.launches;
 	return 0;
@@ -1611,9 +1601,8 @@ static int launch_leaves(a2amd_ctx *c, LeafPass &lp)
 	// a2_Run(4096) 1 398 -> 1 416 us per buffer, a2_Run(1024) 399 -> 416; with the pass held back behind the render
 	// pass instead 1 370 and 408 (profiles/r06_go_skip_ab.txt).  A2AMD_VMSKIP: bit 0 the classes without filter12,
 	// bit 1 the one with.
-	static const int vmskip = getenv("A2AMD_VMSKIP") ? atoi(getenv("A2AMD_VMSKIP")) : 1;
 	auto none_quiet = [&](int k, int nleaf) {
-		return (vmskip & (k == 2 ? 2 : 1)) && c->vm.spec_use && !c->vm.list.empty() && c->vm.n_cls[k] == nleaf && c->vm.spec_idle[k] == 0;
+		return (c->sw.vmskip & (k == 2 ? 2 : 1)) && c->vm.spec_use && !c->vm.list.empty() && c->vm.n_cls[k] == nleaf && c->vm.spec_idle[k] == 0;
 	};
 	// e1 right behind the main kernel when it is the only leaf kernel
 	// of the batch (lp.solo): "leaf" time is then that kernel alone
@@ -1624,7 +1613,7 @@ static int launch_leaves(a2amd_ctx *c, LeafPass &lp)
 		++c->vm.quiet_skipped;
 	} else if(oscpan.count) {
 		int vpw, ysplit;
-		pick_fast_shape(oscpan.count, c->nfrags, &vpw, &ysplit);
+		pick_fast_shape(c->sw, oscpan.count, c->nfrags, &vpw, &ysplit);
 		if(a2d_launch_leaf_oscpan(c->d_params, c->hparams, list + oscpan.first, oscpan.count,
 				vpw, ysplit, c->d_ustage.d, c->d_staged.d + oscpan.first, c->stream, lp.solo ? (void *)lp.e1 : nullptr,
 				&pend.c[pend.n]))
@@ -1640,7 +1629,7 @@ static int launch_leaves(a2amd_ctx *c, LeafPass &lp)
 	// (n_noise_quiet: the voices upload() left without the stand-in run - none, and every voice of the segment has records)
 	const ListRange noisepan = c->leaf[LEAF_NOISEPAN];
 	if(noisepan.count && !c->noise_st.empty() && c->n_noise_quiet) {
-		const int vpw = getenv("A2AMD_NZVPW") ? atoi(getenv("A2AMD_NZVPW")) : (noisepan.count + 1023) / 1024;
+		const int vpw = c->sw.nzvpw_set ? c->sw.nzvpw : (noisepan.count + 1023) / 1024;
 		if(a2d_launch_leaf_noisepan(c->d_params, c->hparams, list + noisepan.first, noisepan.count, vpw, c->stream))
 			return c->fail(A2AMD_EHIP, "noise leaf launch failed: %s", hipGetErrorString(hipGetLastError()));
 		++c->stats.launches;
@@ -1650,7 +1639,7 @@ static int launch_leaves(a2amd_ctx *c, LeafPass &lp)
 	// its filter wavefront - for the whole batch: spread first (one workgroup per CU, 256), then fill.
 	const ListRange noisefilt = c->leaf[LEAF_NOISEFILTPAN];
 	if(noisefilt.count && !c->noise_st.empty() && c->n_noise_filt_quiet) {
-		const int vpg = getenv("A2AMD_NZFVPG") ? atoi(getenv("A2AMD_NZFVPG")) : (noisefilt.count + 255) / 256;
+		const int vpg = c->sw.nzfvpg_set ? c->sw.nzfvpg : (noisefilt.count + 255) / 256;
 		if(a2d_launch_leaf_noisefiltpan(c->d_params, c->hparams, list + noisefilt.first, noisefilt.count, vpg, c->stream))
 			return c->fail(A2AMD_EHIP, "noise filter leaf launch failed: %s", hipGetErrorString(hipGetLastError()));
 		++c->stats.launches;
@@ -1662,7 +1651,7 @@ static int launch_leaves(a2amd_ctx *c, LeafPass &lp)
 	else if(osc2pan.count) {
 		int vpw, ysplit;
 		// (its own chunk length; 16 time slices: 2.19 ms against 2.25 with 32 at configs[3], round 3)
-		pick_fast_shape(osc2pan.count, c->nfrags * A2D_FAST_FCH / A2D_OSC2_FCH, &vpw, &ysplit, 16);
+		pick_fast_shape(c->sw, osc2pan.count, c->nfrags * A2D_FAST_FCH / A2D_OSC2_FCH, &vpw, &ysplit, 16);
 		if(a2d_launch_leaf_osc2pan(c->d_params, c->hparams, list + osc2pan.first, osc2pan.count,
 				vpw, ysplit, c->d_ustage.d, c->d_staged.d + osc2pan.first, c->stream, &pend.c[pend.n]))
 			return c->fail(A2AMD_EHIP, "2-osc leaf launch failed: %s", hipGetErrorString(hipGetLastError()));
@@ -1679,8 +1668,7 @@ static int launch_leaves(a2amd_ctx *c, LeafPass &lp)
 		// per CU), else spread out (a workgroup takes as long as its filter chain,
 		// whatever its voice count)
 		const int nf = oscfilt.count;
-		int vpw = getenv("A2AMD_FVPW") ? atoi(getenv("A2AMD_FVPW")) :
-				std::min(std::max((nf + 255) / 256, 1), 64);
+		int vpw = c->sw.fvpw_set ? c->sw.fvpw : std::min(std::max((nf + 255) / 256, 1), 64);
 		if(a2d_launch_leaf_oscfiltpan(c->d_params, c->hparams, list + oscfilt.first, nf, vpw, c->stream))
 			return c->fail(A2AMD_EHIP, "filter leaf launch failed: %s", hipGetErrorString(hipGetLastError()));
 		++c->stats.launches;
@@ -1693,10 +1681,9 @@ static int launch_leaves(a2amd_ctx *c, LeafPass &lp)
 		// fewest whole rounds of 256 workgroups that allows (16 384 voices: 2 rounds of 32 - measured 1.09 ms per 256
 		// fragments against 3.83 with 48 and 1.50 with 64 voices per workgroup)
 		const int nf = o2f.count;
-		const int env_vpg = c->f2vpw;
 		const int maxv = a2d_osc2filtpan_max_vpg();
 		const int rounds = std::max(1, (nf + 256 * maxv - 1) / (256 * maxv));
-		const int vpg = env_vpg ? env_vpg : std::min(std::max((nf + 256 * rounds - 1) / (256 * rounds), 1), maxv);
+		const int vpg = c->sw.f2vpw ? c->sw.f2vpw : std::min(std::max((nf + 256 * rounds - 1) / (256 * rounds), 1), maxv);
 		if(a2d_launch_leaf_osc2filtpan(c->d_params, c->hparams, list + o2f.first, nf, vpg, c->stream))
 			return c->fail(A2AMD_EHIP, "2-osc filter leaf launch failed: %s", hipGetErrorString(hipGetLastError()));
 		++c->stats.launches;
@@ -1709,7 +1696,7 @@ static int launch_leaves(a2amd_ctx *c, LeafPass &lp)
 	int fm_kinds = 0;
 	for(int k = 0; k < 8; ++k)
 		fm_kinds += c->fm_kind_count[k] != 0;
-	if(fm_kinds > 1 && fm.count <= 16384 && !getenv("A2AMD_FMVPW")) {
+	if(fm_kinds > 1 && fm.count <= 16384 && !c->sw.fmvpw_set) {
 		// several kinds, few voices: one launch for all of them (the
 		// per-kind launches below would run back to back, each as long
 		// as a voice's serial chain)
@@ -1726,7 +1713,7 @@ static int launch_leaves(a2amd_ctx *c, LeafPass &lp)
 			// wavefront shadow its voices, see fmpan_body) until there is one
 			// wavefront per SIMD (1 024), then the lanes fill up
 			// (profiles/r01_fm_vpw_sweep.txt).
-			int vpw = getenv("A2AMD_FMVPW") ? atoi(getenv("A2AMD_FMVPW")) : (n + 1023) / 1024;
+			int vpw = c->sw.fmvpw_set ? c->sw.fmvpw : (n + 1023) / 1024;
 			vpw = std::min(std::max(vpw, 1), 64);
 			if(a2d_launch_leaf_fmpan(c->d_params, c->hparams, A2AMD_FM1 + k, list + at, n, vpw, c->stream))
 				return c->fail(A2AMD_EHIP, "fm leaf launch failed: %s", hipGetErrorString(hipGetLastError()));
@@ -1755,10 +1742,10 @@ static int launch_leaves(a2amd_ctx *c, LeafPass &lp)
 		c->last_batch.recs_voices = (uint32_t)total;
 		if(!c->vm.list.empty())
 			c->last_batch.recs_voices += (uint32_t)(c->vm.n_cls[0] + c->vm.n_cls[1] + c->vm.n_cls[2]);
-		if(kinds > 1 && total <= 4096 && !getenv("A2AMD_RVPW")) {
+		if(kinds > 1 && total <= 4096 && !c->sw.rvpw_set) {
 			// few voices of several kinds (a song): one launch - on one stream the per-kind
 			// launches would run back to back, each as long as one voice's walk through the batch
-			if(a2d_launch_leaf_recs_all(c->d_params, c->hparams, lists, counts, 1, c->stream, c->o2f_quiet ? 8 : 0))
+			if(a2d_launch_leaf_recs_all(c->sw, c->d_params, c->hparams, lists, counts, 1, c->stream, c->o2f_quiet ? 8 : 0))
 				return c->fail(A2AMD_EHIP, "leaf records launch failed: %s", hipGetErrorString(hipGetLastError()));
 			++c->stats.launches;
 		} else {
@@ -1811,17 +1798,15 @@ static int issue_leaf_phase(a2amd_ctx *c, bool consume, bool consume_sub, hipEve
 	// 0.5 - 1.8).  A2AMD_WIN=0 / 1 forces (the parity tests run both), A2AMD_WIN_MIN moves the threshold.
 	bool use_win;
 	{
-		const char *wenv = getenv("A2AMD_WIN");
-		const int win_min = c->win_min;
 		int nwinv = 0;
 		for(int k = DYN_OSC1; k <= DYN_FILT2; ++k)
 			nwinv += c->dyn[k].count;
 		for(int k = 0; k < 3; ++k)
 			nwinv += c->vm.list.empty() ? 0 : c->vm.n_cls[k];
-		use_win = wenv ? atoi(wenv) != 0 : nwinv >= win_min;
+		use_win = c->sw.win >= 0 ? c->sw.win != 0 : nwinv >= c->sw.win_min;
 	}
 	// (A2AMD_VMWIN=0: the device VM's voices through records - k_vm_count / k_vm_emit - whatever renders them)
-	static const bool vmwin_ok = !(getenv("A2AMD_VMWIN") && !atoi(getenv("A2AMD_VMWIN")));
+	const bool vmwin_ok = c->sw.vmwin;
 	if(int r = vm_issue(c, use_win && vmwin_ok && !c->vm.fused_off))
 		return r;
 	// a2amd_last_batch(): the lists as upload() made them; the launches below fill in the rest
@@ -1837,7 +1822,7 @@ static int issue_leaf_phase(a2amd_ctx *c, bool consume, bool consume_sub, hipEve
 	c->last_noise_filter = a2amd_noise_filter_batch_info{};
 	c->last_noise_filter.class_voices = (uint32_t)c->leaf[LEAF_NOISEFILTPAN].count;
 	c->last_noise_filter.quiet_voices = c->n_noise_filt_quiet;
-	c->last_noise_filter.min_voices = (uint32_t)c->nzf_min;
+	c->last_noise_filter.min_voices = (uint32_t)c->sw.nzf_min;
 	// The batch's other leaf kernels - the quiet kernels of the classes, the records kernels where the window kernels
 	// are not in use, the general kernel - as a block that runs once: normally behind the window kernels, and
 	// (round 6) from INSIDE issue_windows, between its control passes and its render passes, when a speculative VM
@@ -1846,9 +1831,8 @@ static int issue_leaf_phase(a2amd_ctx *c, bool consume, bool consume_sub, hipEve
 	// and then has the render pass - the long one - beside it, not in front of it.  All of these kernels only ever
 	// ADD to the buses, and runs[] is written by the control passes: their order among themselves is free.
 	LeafPass lp = { pend, e1, use_win, oscpan_alone(c), false };
-	static const bool spec_early = !(getenv("A2AMD_VMSPEC_EARLY") && !atoi(getenv("A2AMD_VMSPEC_EARLY")));
 	const std::function<int()> mid = [&]() -> int {
-		if(!spec_early || !vmwin_ok || !vm_spec_wanted(c))
+		if(!c->sw.vmspec_early || !vmwin_ok || !vm_spec_wanted(c))
 			return 0;	// (no pass to follow: the old order)
 		if(int r = launch_leaves(c, lp))
 			return r;

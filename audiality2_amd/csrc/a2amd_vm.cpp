@@ -115,8 +115,7 @@ static std::vector<int32_t> make_f1tab(const uint32_t *ptab, int samplerate)
 void start_f1tab(a2amd_ctx *c)
 {
 	VmHost &m = c->vm;
-	static const bool off = getenv("A2AMD_NO_VM") != nullptr;
-	if(off)
+	if(c->sw.no_vm)
 		return;
 	struct Args { uint32_t ptab[128]; int sr; };
 	Args a;
@@ -862,23 +861,21 @@ bool vm_spec_plan(a2amd_ctx *c, int *nfrags, uint8_t *ff, uint8_t *fb)
 static int vm_spec_why_not(a2amd_ctx *c, int *nfrags, uint8_t *ff, uint8_t *fb)
 {
 	VmHost &m = c->vm;
-	static const bool on = !(getenv("A2AMD_VMSPEC") && !atoi(getenv("A2AMD_VMSPEC")));
 	const int ncls = m.n_cls[0] + m.n_cls[1] + m.n_cls[2];
-	if(!on || m.list.empty() || !ncls || c->capturing || m.fused_off || c->nfrags < 1 || c->nfrags > A2D_MAXBATCH)
+	if(!c->sw.vmspec || m.list.empty() || !ncls || c->capturing || m.fused_off || c->nfrags < 1 || c->nfrags > A2D_MAXBATCH)
 		return 1;
 	// Short batches are left alone: k_vm_win over ONE fragment is a few tens of microseconds, and the commit plus a
 	// pass that shares the chip with the batch's own kernels cost more than that (measured, 16 384 scripted voices,
 	// a2_Run(64): 140 -> 164 us per call with the pass, 130 -> 137 with filter12; a2_Run(1024) = 16 fragments: 335 -> 295,
 	// 496 -> 421; a2_Run(4096): 1 108 -> 904, 1 713 -> 1 360 - profiles/r06_vm_speculation_ab.txt).  A2AMD_VMSPEC_MIN moves it.
-	static const int min_frags = getenv("A2AMD_VMSPEC_MIN") ? atoi(getenv("A2AMD_VMSPEC_MIN")) : 8;
-	if(c->nfrags < min_frags)
+	if(c->nfrags < c->sw.vmspec_min)
 		return 1;
 	if(m.vm_batches - m.rebuilt_at < 2)	// (the lists have only just changed: VmHost::rebuilt_at)
 		return 4;
 	if(!vm_spec_plan(c, nfrags, ff, fb))
 		return 2;
 	// (the slots of the three classes for the whole batch in one piece: within the window kernels' own budget)
-	static const size_t budget = (size_t)(getenv("A2AMD_WIN_MB") ? atoi(getenv("A2AMD_WIN_MB")) : 1024) * (1u << 20) / sizeof(int);
+	const size_t budget = (size_t)c->sw.win_mb * (1u << 20) / sizeof(int);
 	static const int nosc[3] = { 1, 2, 1 }, filt[3] = { 0, 0, 1 };
 	size_t words = 0;
 	for(int k = 0; k < 3; ++k)
@@ -910,8 +907,7 @@ int vm_speculate(a2amd_ctx *c)
 		const int ncls0 = m.n_cls[0] + m.n_cls[1] + m.n_cls[2];
 		if(!m.list.empty() && ncls0)
 			++m.spec_skip[why - 1];
-		static const int trace = getenv("A2AMD_HOSTTIMING") ? atoi(getenv("A2AMD_HOSTTIMING")) : 0;
-		if(trace >= 2 && why == 2 && !m.list.empty() && ncls0)
+		if(c->sw.hosttiming_level >= 2 && why == 2 && !m.list.empty() && ncls0)
 			fprintf(stderr, "a2amd device VM: no speculative pass behind a batch of %d fragments: its span is not whole engine "
 					"fragments, or two wake-ups of the root are expected inside one\n", c->nfrags);
 		return 0;
@@ -986,8 +982,7 @@ int vm_speculate(a2amd_ctx *c)
 	// "render pass, then pass".  Without filter voices the pass shares the CUs with k_win_render, and whether it got
 	// onto them first was a race that went one way in one process and the other way in the next: 575 or 745 us per
 	// buffer of OscPanScripted, bimodal over runs (profiles/r06_timeline_before.txt, r06_go_ab.txt).
-	static const bool go = !(getenv("A2AMD_VMSPEC_GO") && !atoi(getenv("A2AMD_VMSPEC_GO")));
-	if(go && !m.n_cls[2]) {
+	if(c->sw.vmspec_go && !m.n_cls[2]) {
 		if(!m.spec_go)
 			HIPCHK(c, hipEventCreateWithFlags(&m.spec_go, hipEventDisableTiming));
 		HIPCHK(c, hipEventRecord(m.spec_go, m.pred_stream));
@@ -1006,9 +1001,7 @@ int vm_speculate(a2amd_ctx *c)
 				m.d_swext[set].d, m.d_swscr.d + atv * A2D_VMW_ROW * A2D_WIN_WORDS, m.d_swidx[set].d + at, m.d_swtop,
 				(unsigned)m.spec_cap, m.pred_stream, &out))
 			return c->fail(A2AMD_EHIP, "speculative VM pass launch failed: %s", hipGetErrorString(hipGetLastError()));
-		// (A2AMD_WIN_SYNC=1, debugging: wait for the pass and say so - the last line names the kernel that faulted)
-		static const bool dbgsync = getenv("A2AMD_WIN_SYNC") != nullptr;
-		if(dbgsync) {
+		if(c->sw.win_sync) {
 			const hipError_t e = hipStreamSynchronize(m.pred_stream);
 			fprintf(stderr, "a2amd device VM: speculative pass <%d,%d> of %d voices over %d fragments into set %d (slots at %zu words, "
 					"index at %zu, rows at %zu; pool room %zu): %s\n", nosc[k], filt[k], m.n_cls[k], nfrags, set, atw, at, atv,
@@ -1097,10 +1090,9 @@ int vm_issue(a2amd_ctx *c, bool fused)
 				why = 4;
 		}
 		++m.pred_why[why];
-		static const int trace = getenv("A2AMD_HOSTTIMING") ? atoi(getenv("A2AMD_HOSTTIMING")) : 0;
 		if(why && m.spec_valid)
 			++m.spec_miss[0];
-		if(trace >= 2 && why >= 4)
+		if(c->sw.hosttiming_level >= 2 && why >= 4)
 			fprintf(stderr, "a2amd device VM: batch of %d fragments not fused: %s (predicted: %u frames)\n", c->nfrags,
 					why == 4 ? "another length" : "a fragment across a 64-frame boundary", m.pred_span);
 		if(!why) {
@@ -1181,8 +1173,7 @@ int vm_issue(a2amd_ctx *c, bool fused)
 	vp.rec_cap = m.rec_cap;
 	if(a2d_launch_vm(vp, 1, c->stream))
 		return c->fail(A2AMD_EHIP, "VM emit launch failed: %s", hipGetErrorString(hipGetLastError()));
-	static const bool dump = getenv("A2AMD_VM_DUMP") != nullptr;	// (... and device-made)
-	if(dump) {
+	if(c->sw.vm_dump) {	// (... and device-made)
 		std::vector<A2DRun> runs(m.list.size());
 		std::vector<A2DRec> recs(total);
 		HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1226,13 +1217,13 @@ void vm_end_batch(a2amd_ctx *c)
 void vm_close(a2amd_ctx *c)
 {
 	VmHost &m = c->vm;
-	if(c->hosttiming && m.vm_batches)
+	if(c->sw.hosttiming && m.vm_batches)
 		fprintf(stderr, "a2amd device VM: %llu batches with device VM voices, %llu of them through k_vm_win (the others: %llu not "
 				"predicted, %llu other voices, %llu another time, %llu / %llu / %llu other fragments)\n",
 				(unsigned long long)m.vm_batches, (unsigned long long)m.fused_batches, (unsigned long long)m.pred_why[1],
 				(unsigned long long)m.pred_why[2], (unsigned long long)m.pred_why[3], (unsigned long long)m.pred_why[4],
 				(unsigned long long)m.pred_why[5], (unsigned long long)m.pred_why[6]);
-	if(c->hosttiming && m.spec_launched)
+	if(c->sw.hosttiming && m.spec_launched)
 		fprintf(stderr, "a2amd device VM: %llu speculative passes (k_vm_win for the batch expected next, into shadows), %llu of them taken "
 				"(k_vm_commit + render pass in k_vm_win's place); pool room %zu entries, last demand %zu; not taken: %llu not the "
 				"batch predicted, %llu other fragments / classes, %llu pool overflow, %llu faults; batches without a pass: %llu off / "

@@ -40,6 +40,7 @@
 #include <stdlib.h>
 #include <algorithm>
 #include "a2amd_device.h"
+#include "a2amd_switches.h"
 #include "a2amd_dsp.h"
 #include "a2amd_taps.h"
 
@@ -1013,7 +1014,7 @@ int a2d_launch_win_ctl(const A2DParams *dparams, const A2DParams &hp, int nosc, 
 	return (int)hipGetLastError();
 }
 
-int a2d_launch_win_render(const A2DParams &hp, int nosc, int filt, const int *dlist, int nlist, int fa, int fb,
+int a2d_launch_win_render(const A2Switches &sw, const A2DParams &hp, int nosc, int filt, const int *dlist, int nlist, int fa, int fb,
 		const int *wslot, const int *wext, const unsigned *widx, void *stream)
 {
 	if(nlist <= 0 || fb <= fa)
@@ -1021,8 +1022,7 @@ int a2d_launch_win_render(const A2DParams &hp, int nosc, int filt, const int *dl
 	if(!filt) {
 		// voices per wavefront (one per lane at most): about 8 192 wavefronts in the launch
 		const int nchunks = (fb - fa + WIN_FCH - 1) / WIN_FCH;
-		static const int force = getenv("A2AMD_WVPW") ? atoi(getenv("A2AMD_WVPW")) : 0;
-		int vpw = force > 0 ? force : (int)std::min<long long>(std::max<long long>(((long long)nlist * nchunks + 8191) / 8192, 1), 64);
+		int vpw = sw.wvpw > 0 ? sw.wvpw : (int)std::min<long long>(std::max<long long>(((long long)nlist * nchunks + 8191) / 8192, 1), 64);
 		vpw = std::min(std::max(vpw, 1), 64);
 		const int ngroups = (nlist + vpw - 1) / vpw;
 		const int nblocks = nchunks * ((ngroups + WIN_WPB - 1) / WIN_WPB);
@@ -1035,15 +1035,13 @@ int a2d_launch_win_render(const A2DParams &hp, int nosc, int filt, const int *dl
 	} else {
 		// voices per workgroup = lanes of its filter wavefront: spread out until every CU has a couple of
 		// workgroups (a workgroup takes as long as its filter chain whatever its voice count), then fill up
-		static const int force = getenv("A2AMD_WFVPG") ? atoi(getenv("A2AMD_WFVPG")) : 0;
 		const int maxw = WINF_MAXW(nosc);
 		// (measured at 16 384 voices x 64 fragments: one oscillator 32 per workgroup 0.63 ms, 48 - a workgroup and a half
 		// per CU - 0.77; two oscillators 64 per workgroup 0.94, 32 1.03, 60 - 274 workgroups on 256 CUs - 1.49)
-		int vpg = force > 0 ? force : nosc == 1 ? std::min(std::max((nlist + 511) / 512, 1), 48) : std::min(std::max((nlist + 255) / 256, 1), 64);
+		int vpg = sw.wfvpg > 0 ? sw.wfvpg : nosc == 1 ? std::min(std::max((nlist + 511) / 512, 1), 48) : std::min(std::max((nlist + 255) / 256, 1), 64);
 		vpg = std::min(std::max(vpg, 1), 64);
 		// wavefronts: the filter's + one per ~4 voices
-		static const int forcew = getenv("A2AMD_WFWAVES") ? atoi(getenv("A2AMD_WFWAVES")) : 0;
-		int nw = forcew > 1 ? forcew : 1 + std::min(std::max((vpg + 3) / 4, 1), 7);
+		int nw = sw.wfwaves > 1 ? sw.wfwaves : 1 + std::min(std::max((vpg + 3) / 4, 1), 7);
 		nw = std::min(std::max(nw, 2), maxw);
 		// (three tiles of vpg rows + the wavefronts' bus sums: within 64 KB of LDS)
 		while(vpg > 1 && (size_t)(3 * vpg * WINF_PITCH + 2 * nw * 2 * 64 + 2 * nw * 2) * sizeof(int) > 65536)
