@@ -2843,17 +2843,20 @@ void k_bus_driver(const A2DParams *__restrict__ pp, const int *__restrict__ list
 		__syncthreads();
 	}
 	const bool sclamp = pan.value > 0xffffff || pan.value < -0xffffff;
+	// (a mono owner - inline 0 1; panmix 1 2: the second input is the first, panmix_process12 - has one channel to read
+	// and to zero: its "second channel" is the first one's address again)
+	const int ch1 = vc.own_nch == 1 ? 0 : A2D_FRAG;
 	for(int f = fbeg; f < p.nfrags; f += fstep) {
 		if(lane >= p.fragframes[f])
 			continue;
 		int *src = p.busmem + vc.own_off + (size_t)f * vc.own_nch * A2D_FRAG;
 		int *dst = p.busmem + vc.out_off + (size_t)f * vc.out_nch * A2D_FRAG;
-		int i0 = src[lane], i1 = src[A2D_FRAG + lane];
+		int i0 = src[lane], i1 = src[ch1 + lane];
 		if(consume & 1) {
 			// every bus of this batch is read here and nowhere else: leave it
 			// zeroed for the next batch (no memset between batches)
 			src[lane] = 0;
-			src[A2D_FRAG + lane] = 0;
+			src[ch1 + lane] = 0;
 		}
 		int vk = settled ? vol.value : wadd(fr[f][0], wmul(fr[f][1], lane));
 		int pk = settled ? pan.value : wadd(fr[f][2], wmul(fr[f][3], lane));

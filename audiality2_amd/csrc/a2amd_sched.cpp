@@ -273,14 +273,26 @@ bool is_fmpan_chain(const a2amd_ctx *c, const HVoice &v)
 			(pm.flags & A2AMD_PROCADD);
 }
 
-// inline 0 2; panmix 2 2; xinsert 2 >  (a2_rootdriver / a2_groupdriver)
+// wtosc alone, wired and adding into the output bus: `struct { wtosc }` (compiler.c:3085-3106 wires the last unit's
+// outputs to the voice's; the engine clamps them to the one a wtosc has, core.c:222-235 - channel 0 of the parent's bus)
+bool is_oscbare_chain(const a2amd_ctx *c, const HVoice &v)
+{
+	if(v.nunits != 1 || v.out_nch < 1 || v.out_nch > 2)
+		return false;
+	const HUnit &o = c->units[v.unit[0]];
+	return o.kind == A2AMD_WTOSC && (o.flags & A2AMD_PROCADD) && o.wired && o.nout == 1 && leaf_mode(o.mode);
+}
+
+// inline 0 2; panmix 2 2; xinsert 2 >  (a2_rootdriver / a2_groupdriver), or - a mono group: `struct { inline; panmix }`
+// compiles to it - inline 0 1; panmix 1 2 ..., which is the same chain with the one channel read twice (panmix_process12
+// against panmix_process22, panmix.c:78-115 / :191-229)
 bool is_driver_chain(const a2amd_ctx *c, const HVoice &v)
 {
-	if((v.nunits != 3 && v.nunits != 2) || v.own_nch != 2 || v.out_nch < 2 || v.own_off < 0)
+	if((v.nunits != 3 && v.nunits != 2) || (v.own_nch != 2 && v.own_nch != 1) || v.out_nch < 2 || v.own_off < 0)
 		return false;
 	const HUnit &il = c->units[v.unit[0]], &pm = c->units[v.unit[1]];
-	if(!(il.kind == A2AMD_INLINE && !(il.flags & A2AMD_PROCADD) && !il.wired && il.nout == 2 &&
-			pm.kind == A2AMD_PANMIX && pm.nin == 2 && pm.nout == 2))
+	if(!(il.kind == A2AMD_INLINE && !(il.flags & A2AMD_PROCADD) && !il.wired && il.nout == v.own_nch &&
+			pm.kind == A2AMD_PANMIX && pm.nin == v.own_nch && pm.nout == 2))
 		return false;
 	if(v.nunits == 2)
 		// inline 0 2; panmix 2 >  - what the drop-in's root voice looks like from here (the root's
@@ -765,7 +777,10 @@ int upload(a2amd_ctx *c)
 							// (no quiet kernel of its own: k_leaf_recs renders it, records or not - unless an
 							// oscillator leaves the mip-mapped waves somewhere in this batch)
 							!(c->sw.no_fast & 128) && !v.mode_mix && is_osc2filtpan_chain(c, v) ? CLS_OSC2FILTPAN :
-							!(c->sw.no_fast & 16) && is_fmpan_chain(c, v) ? CLS_FMPAN : CLS_GENERIC;
+							!(c->sw.no_fast & 16) && is_fmpan_chain(c, v) ? CLS_FMPAN :
+							// (a voice the device VM runs stays with the general kernel: the host cannot tell in which
+							// batches the VM writes it records - adoption and recall mark the class stale, a2amd_vm.cpp)
+							!(c->sw.no_fast & 256) && v.vm < 0 && is_oscbare_chain(c, v) ? CLS_OSCBARE : CLS_GENERIC;
 				if(v.out_off == 0)
 					owners_ok = false;	// adds straight into the master bus
 				leaf[cls_lists[v.cls].leaf].push_back((int)vi);
@@ -840,6 +855,10 @@ int upload(a2amd_ctx *c)
 				if(v.cls == CLS_OSC2FILTPAN)
 					v.dynf2_run = c->serial_base;
 				dyn[ok ? cls_lists[v.cls].dyn : DYN_REST].push_back(vi);
+			} else if(v.cls == CLS_OSCBARE) {
+				// (a bare wtosc with records - or the stand-in run of a noise oscillator in a device-seeded stretch: the general
+				// kernel's, which renders the voices on its exception list; k_leaf_oscbare skips a voice that has a run)
+				dyn[DYN_REST].push_back(vi);
 			} else if((v.cls == CLS_BUSDRIVER || v.cls == CLS_FBDCHAIN) && v.depth < (int)dyn_bus.size()) {
 				dyn_bus[v.depth].push_back(vi);
 				if(c->sw.hosttiming_level >= 3 && !v.recs.empty())
@@ -901,12 +920,14 @@ int upload(a2amd_ctx *c)
 		// alone write them, the device VM adopts no bus owner) are listed once more, for k_bus_driver's launch of one
 		// workgroup a voice: the launch over all drivers leaves an unsettled one alone.
 		std::vector<int> ramp;
+		c->n_mono_drivers = 0;
 		for(size_t d = 0; d < c->depth_ranges.size(); ++d) {
 			DepthRange &r = c->depth_ranges[d];
 			ramp.clear();
 			for(int k = 0; k < r.driver.count; ++k) {
 				const int vi = c->list_all[r.driver.first + k];
 				const HVoice &v = c->voices[vi];
+				c->n_mono_drivers += v.own_nch == 1;
 				if(!v.recs.empty())
 					continue;
 				++bi.driver_voices;
@@ -918,6 +939,21 @@ int upload(a2amd_ctx *c)
 			for(int k = 0; k < r.fbd.count; ++k)
 				bi.fbd_voices += c->voices[c->list_all[r.fbd.first + k]].recs.empty();
 			bi.generic_voices += (uint32_t)(r.generic.count + r.dyn.count);
+		}
+		// a2amd_last_batch_bare(): the bare wtosc voices by who renders them this batch.  One with a run - records of its
+		// own, or the stand-in run of a noise oscillator in a device-seeded stretch - stands on the general kernel's list
+		// above; the others are k_leaf_oscbare's, those still gliding by the host's bound (moving_until) included: the class
+		// is given no stand-in run for a glide, the kernel steps the rampers itself.
+		c->n_bare_quiet = c->n_bare_gliding = c->n_bare_records = 0;
+		const ListRange bare = c->leaf[LEAF_OSCBARE];
+		for(int k = 0; k < bare.count; ++k) {
+			const HVoice &v = c->voices[c->list_all[bare.first + k]];
+			if(!v.recs.empty() || v.moving_run == c->serial_base) {
+				++c->n_bare_records;
+				continue;
+			}
+			++c->n_bare_quiet;
+			c->n_bare_gliding += v.moving_until > c->vm.batch_time;
 		}
 	}
 
@@ -1645,6 +1681,18 @@ static int launch_leaves(a2amd_ctx *c, LeafPass &lp)
 		++c->stats.launches;
 		c->last_noise_filter.quiet_launched = 1;
 	}
+	// bare wtosc voices without a run this batch, settled or gliding (upload() counted them: none, and the segment's voices
+	// are all the general kernel's - no launch).  A wavefront keeps its voices for the whole batch, as k_leaf_noisepan's
+	// does: one wavefront per SIMD first (1 024), then the lanes fill up.  A2AMD_VPW forces the voices per wavefront.
+	const ListRange bare = c->leaf[LEAF_OSCBARE];
+	if(bare.count && c->n_bare_quiet) {
+		const int vpw = std::min(std::max(c->sw.vpw_set ? c->sw.vpw : (bare.count + 1023) / 1024, 1), 64);
+		if(a2d_launch_leaf_oscbare(c->d_params, c->hparams, list + bare.first, bare.count, vpw, c->stream))
+			return c->fail(A2AMD_EHIP, "bare oscillator leaf launch failed: %s", hipGetErrorString(hipGetLastError()));
+		++c->stats.launches;
+		c->last_bare.launched = 1;
+		c->last_bare.vpw = (uint32_t)vpw;
+	}
 	const ListRange osc2pan = c->leaf[LEAF_OSC2PAN];
 	if(osc2pan.count && none_quiet(1, osc2pan.count))
 		++c->vm.quiet_skipped;
@@ -1823,6 +1871,12 @@ static int issue_leaf_phase(a2amd_ctx *c, bool consume, bool consume_sub, hipEve
 	c->last_noise_filter.class_voices = (uint32_t)c->leaf[LEAF_NOISEFILTPAN].count;
 	c->last_noise_filter.quiet_voices = c->n_noise_filt_quiet;
 	c->last_noise_filter.min_voices = (uint32_t)c->sw.nzf_min;
+	c->last_bare = a2amd_bare_batch_info{};
+	c->last_bare.class_voices = (uint32_t)c->leaf[LEAF_OSCBARE].count;
+	c->last_bare.quiet_voices = c->n_bare_quiet;
+	c->last_bare.gliding_voices = c->n_bare_gliding;
+	c->last_bare.record_voices = c->n_bare_records;
+	c->last_bare.mono_drivers = c->n_mono_drivers;
 	// The batch's other leaf kernels - the quiet kernels of the classes, the records kernels where the window kernels
 	// are not in use, the general kernel - as a block that runs once: normally behind the window kernels, and
 	// (round 6) from INSIDE issue_windows, between its control passes and its render passes, when a speculative VM

@@ -29,7 +29,7 @@ static inline int within(const char *name, int lo, int hi) { const int v = num(n
 	X(bool, hosttiming, a2sw::set("A2AMD_HOSTTIMING")) X(int, hosttiming_level, a2sw::num("A2AMD_HOSTTIMING", 0))	/* unset: host timing counters and their dump at exit; the level (2, 3) adds per-batch traces */ \
 	X(bool, noise_quiet, a2sw::on("A2AMD_NOISE_QUIET"))	/* on. 0: no launch classes for wtosc (noise)-[filter12-]panmix voices - they are wtosc-[filter12-]panmix voices, and every noise voice of a device-seeded batch gets the stand-in record (A/B) */ \
 	X(bool, no_direct, a2sw::set("A2AMD_NO_DIRECT"))	/* unset. Set: the root never stores the master bus straight into the host's buffer */ \
-	X(int, no_fast, a2sw::num("A2AMD_NO_FAST", 0))		/* 0. Bit mask of classes sent to the general kernel: 1 wtosc-panmix, 2 wtosc-filter12-panmix, 4 driver chains, 8 2 x wtosc-panmix, 16 fm-panmix, 32 fbdelay chains, 64 no records kernel, 128 2 x wtosc-filter12-panmix (debugging / A-B tests) */ \
+	X(int, no_fast, a2sw::num("A2AMD_NO_FAST", 0))		/* 0. Bit mask of classes sent to the general kernel: 1 wtosc-panmix, 2 wtosc-filter12-panmix, 4 driver chains, 8 2 x wtosc-panmix, 16 fm-panmix, 32 fbdelay chains, 64 no records kernel, 128 2 x wtosc-filter12-panmix, 256 bare wtosc (debugging / A-B tests) */ \
 	X(bool, no_graph, a2sw::set("A2AMD_NO_GRAPH"))		/* unset. Set: no batch is captured into or replayed from a graph */ \
 	X(bool, no_moving, a2sw::set("A2AMD_NO_MOVING"))	/* unset. Set: gliding voices get no stand-in record (they stay the quiet kernels') */ \
 	X(bool, no_selfclean, a2sw::set("A2AMD_NO_SELFCLEAN"))	/* unset. Set: bus owners never count as clearing their own buses */ \
@@ -49,7 +49,7 @@ static inline int within(const char *name, int lo, int hi) { const int v = num(n
 	X(int, vmspec_min, a2sw::num("A2AMD_VMSPEC_MIN", 8))	/* 8: fragments of a batch from which the speculative pass runs */ \
 	X(bool, vmwin, a2sw::on("A2AMD_VMWIN"))			/* on. 0: the device VM's voices never go through the fused window pass */ \
 	X(bool, vm_dump, a2sw::set("A2AMD_VM_DUMP"))		/* unset. Set: print the records of every batch, host-made and device-made (debugging aid) */ \
-	X(bool, vpw_set, a2sw::set("A2AMD_VPW")) X(int, vpw, a2sw::num("A2AMD_VPW", 0))	/* unset = pick_fast_shape(): voices per wavefront of the time-sliced leaf kernels */ \
+	X(bool, vpw_set, a2sw::set("A2AMD_VPW")) X(int, vpw, a2sw::num("A2AMD_VPW", 0))	/* unset = pick_fast_shape(): voices per wavefront of the time-sliced leaf kernels; and, clamped to 1..64, of k_leaf_oscbare (unset: by count) */ \
 	X(int, wfvpg, a2sw::within("A2AMD_WFVPG", 1, 0x7fffffff))	/* 0 = by count; > 0 forces k_win_render_f's voices per workgroup */ \
 	X(int, wfwaves, a2sw::within("A2AMD_WFWAVES", 2, 0x7fffffff))	/* 0 = by voices per workgroup; > 1 forces k_win_render_f's wavefronts per workgroup */ \
 	X(int, win, a2sw::set("A2AMD_WIN") ? a2sw::num("A2AMD_WIN", 0) != 0 : -1)	/* -1 = from win_min voices on; 0 ("" too) / not 0: the window kernels never / always take the voices with records */ \

@@ -117,6 +117,15 @@ class a2amd_bus_info(C.Structure):
         return "bus_info(" + ", ".join(f"{n}={getattr(self, n)}" for n, _ in self._fields_) + ")"
 
 
+class a2amd_bare_batch_info(C.Structure):
+    """include/a2amd_oscbare.h: who rendered the bare wtosc voices of the most recent batch, and the mono group drivers"""
+    _fields_ = [(n, C.c_uint32) for n in ("launched", "class_voices", "quiet_voices", "gliding_voices", "record_voices",
+                                          "vpw", "mono_drivers", "reserved")]
+
+    def __repr__(self):
+        return "bare_batch_info(" + ", ".join(f"{n}={getattr(self, n)}" for n, _ in self._fields_) + ")"
+
+
 class Backend:
     """Thin ctypes veneer over one implementation of the call protocol."""
 
@@ -172,6 +181,9 @@ class Backend:
         self._last_batch_buses = None
         if hasattr(lib, prefix + "last_batch_buses"):
             self._last_batch_buses = fn("last_batch_buses", i32, vp, C.POINTER(a2amd_bus_info))
+        self._last_batch_bare = None
+        if hasattr(lib, prefix + "last_batch_bare"):
+            self._last_batch_bare = fn("last_batch_bare", i32, vp, C.POINTER(a2amd_bare_batch_info))
         # waves built on the device from what it rendered (the product library only)
         self.has_capture = hasattr(lib, prefix + "wave_upload_captured_post")
         if self.has_capture:
@@ -307,6 +319,16 @@ class Backend:
             raise RuntimeError(f"this library has no {self.prefix}last_batch_buses")
         bi = a2amd_bus_info()
         self._chk(self._last_batch_buses(self.ctx, C.byref(bi)), "last_batch_buses")
+        return bi
+
+    def last_batch_bare(self):
+        """a2amd_last_batch_bare: whether k_leaf_oscbare was launched for the most recent batch, the voices of its launch
+        class (bare wtosc: one unit, wired, adding) by who rendered them - the kernel (of which still gliding), the
+        general kernel (those with records) - its voices per wavefront, and the mono owners on k_bus_driver's lists"""
+        if self._last_batch_bare is None:
+            raise RuntimeError(f"this library has no {self.prefix}last_batch_bare")
+        bi = a2amd_bare_batch_info()
+        self._chk(self._last_batch_bare(self.ctx, C.byref(bi)), "last_batch_bare")
         return bi
 
     def unit_init(self, voice_key, kind, flags, nin, nout, wired, transpose=0, wakefrac=0):

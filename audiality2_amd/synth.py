@@ -245,6 +245,24 @@ class Scene:
         (self.groups if parent is None else parent.setdefault("subs", [])).append(g)
         return g
 
+    def add_mono_group(self, parent=None, pan=None, xinsert=False):
+        """A mono group as `struct { inline; panmix }` compiles: inline 0 1; panmix+ 1 > 2, one channel panned into its
+        parent's stereo bus - add_bus_group with a mono bus of its own.  pan: written to the panmix when given.
+        xinsert: the three-unit shape, inline 0 1; panmix 1 2; xinsert+ 2 >."""
+        be, k = self.be, self._key()
+        if xinsert:
+            u = [be.unit_init(k, K_INLINE, 0, 0, 1, 0),
+                 be.unit_init(k, K_PANMIX, 0, 1, 2, 0),
+                 be.unit_init(k, K_XINSERT, PROCADD, 2, 2, 1)]
+        else:
+            u = [be.unit_init(k, K_INLINE, 0, 0, 1, 0),
+                 be.unit_init(k, K_PANMIX, PROCADD, 1, 2, 1)]
+        if pan is not None:
+            be.unit_write(u[1], 1, fix(pan))
+        g = dict(units=u, leaves=[], subs=[])
+        (self.groups if parent is None else parent.setdefault("subs", [])).append(g)
+        return g
+
     def add_voices(self, n, chain="osc-pan", group=None, total=None, private=False):
         """n sustained voices with the per-voice parameters of SURVEY.md 8(d):
         wave 7k mod 24, pitch ((k mod 61)-30)/12 oct, pan ((k mod 17)-8)/8 ..."""
@@ -258,7 +276,11 @@ class Scene:
             key = self._key()
             p = fix(((k % 61) - 30) / 12.0)
             units = []
-            if chain == "osc-pan":
+            if chain == "osc":
+                # `struct { wtosc }`: the oscillator alone, wired and adding - channel 0 of the parent's bus, no pan
+                units = [be.unit_init(key, K_WTOSC, PROCADD, 0, 1, 1)]
+                oscs, pan = [units[0]], None
+            elif chain == "osc-pan":
                 units = [be.unit_init(key, K_WTOSC, 0, 0, 1, 0),
                          be.unit_init(key, K_PANMIX, PROCADD, 1, 2, 1)]
                 oscs, pan = [units[0]], units[1]
@@ -340,7 +362,8 @@ class Scene:
                 be.unit_write(o, 1, p + (fix(0.01) if j == 0 else -fix(0.01)) * (len(oscs) > 1))
                 be.unit_write(o, 2, amp)
                 be.unit_write(o, 3, (k * 2654435761) % 65536)
-            be.unit_write(pan, 1, fix(((k % 17) - 8) / 8.0))
+            if pan is not None:
+                be.unit_write(pan, 1, fix(((k % 17) - 8) / 8.0))
             dst.append(units)
 
     # -- the engine's per-fragment voice walk (core.c:1847-1896), all VMs asleep --

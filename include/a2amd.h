@@ -453,5 +453,7 @@ int  a2amd_last_batch(const a2amd_ctx *ctx, a2amd_batch_info *bi);
 #include "a2amd_bus.h"
 /* Rendered waves with "normalize" / "xfade", post-processed on the device: a2amd_wave_upload_captured_post(), a2amd_wavepost_host(). */
 #include "a2amd_wavepost.h"
+/* The quiet kernel of bare wtosc voices and the mono group drivers: a2amd_last_batch_bare(). */
+#include "a2amd_oscbare.h"
 
 #endif /* A2AMD_H */

@@ -2,7 +2,8 @@
  * recent batch - the voices with an inline unit, i.e. the root and the group voices.
  *
  * A bus owner goes to one of three kernels.  k_bus_driver takes the chain inline -> panmix 2->2 -> xinsert
- * (the engine's root and group drivers), k_bus_fbdchain the chain inline -> fbdelay [-> fbdelay ...] of at
+ * (the engine's root and group drivers) and its mono form, inline 0 1 -> panmix 1->2 [-> xinsert] under a stereo bus,
+ * whose one channel it reads twice (a mono root stays with the general kernel), k_bus_fbdchain the chain inline -> fbdelay [-> fbdelay ...] of at
  * most four delays whose taps are all between one fragment and the delay line less one fragment long, the
  * general kernel every other chain - and any bus owner in a batch in which it carries records.  The counts
  * are the host's: what upload() listed for each kernel and what the launches were given, not something read
