@@ -7,8 +7,13 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "a2amd_settled.h"	// (the settled-voice prologue every leaf kernel calls)
 
 #define DEV __device__ __forceinline__
+
+// a per-lane word as a wave-uniform one: the first active lane's, lane 'lane''s
+DEV int rfl(int x) { return __builtin_amdgcn_readfirstlane(x); }
+DEV int rdl(int v, int lane) { return __builtin_amdgcn_readlane(v, lane); }
 
 // ---------------------------------------------------------------------------
 // fixed point helpers
@@ -23,6 +28,8 @@ struct Ramp { int value, target, delta, timer; };
 
 DEV Ramp ramp_load(const int *w) { Ramp r = { w[0], w[1], w[2], w[3] }; return r; }
 DEV void ramp_store(int *w, const Ramp &r) { w[0] = r.value; w[1] = r.target; w[2] = r.delta; w[3] = r.timer; }
+// a2_PrepareRamper on the words of a ramper at rest (a2s_at_rest): value = target, delta = timer = 0
+DEV void ramp_settle(int *r) { r[0] = r[1]; r[2] = r[3] = 0; }
 
 // a2_InitRamper, a2_dsp.h:121-125
 DEV void ramp_init(Ramp &r, int v) { r.value = r.target = wshl(v, 8); r.delta = r.timer = 0; }

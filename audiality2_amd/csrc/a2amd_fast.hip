@@ -177,13 +177,10 @@ DEV OscPend osc_fragment_begin(const FastPtrs &g, OscS &o, int nframes, int lane
 				o.p_ramping = o.p.delta;
 				o.dphase = (unsigned)rfl((int)p2i(g.ptab, (int)((lastv + (unsigned)o.p.value) >> 9)));
 			}
-			unsigned dph = ((o.dphase + 255) >> 8) * period;
 			ramp_prepare_s(o.a, nframes);
-			unsigned mm = 0;
-			for(; (dph > (A2D_MAXPHINC << 8)) && (mm < A2D_MIPS - 1); ++mm)
-				dph >>= 1;
+			unsigned dph;
+			const unsigned mm = a2s_mip(o.dphase, period, &dph);
 			uint64_t ph = o.phase >> mm;
-			dph = (unsigned)(((uint64_t)o.dphase * period) >> mm);
 			const unsigned sizem = w->size[mm];
 			bool play = true;
 			if(flags & 0x100u) {
@@ -263,8 +260,7 @@ DEV int osc_fragment_s(const FastPtrs &g, OscS &o, int nframes, int lane)
 // (panmix_Process12Add / panmix_process12, panmix.c:78-125) for input x.
 DEV void pan_fragment_s(Ramp &vol, Ramp &pan, int x, int nframes, int lane, int &acc0, int &acc1)
 {
-	const bool clamp = pan.target > 0xffffff || pan.target < -0xffffff ||
-			pan.value > 0xffffff || pan.value < -0xffffff;
+	const bool clamp = a2s_pan_over(pan.target) || a2s_pan_over(pan.value);
 	ramp_prepare_s(vol, nframes);
 	ramp_prepare_s(pan, nframes);
 	if((unsigned)lane < (unsigned)nframes) {
@@ -308,6 +304,20 @@ enum { SV_MODE = 0, SV_WAVE, SV_DPHASE, SV_PHLO, SV_PHHI, SV_PRAMP, SV_P = 6, SV
 
 // Extra per-lane words derived once per launch from a voice's state
 enum { DV_SETTLED = 0, DV_MM, DV_DPH, DV_SIZEM, DV_DOFF, DV_V0, DV_V1, DV_NWORDS };
+
+// The four words DV_MM .. DV_DOFF (k_leaf_osc2pan's OD_MM .. OD_DOFF) of an oscillator at a constant pitch on wave w:
+// mip level, increment there, that level's size and place in the pool.  False: no wave for the settled paths - or
+// 'settled' was false already, and then the descriptor's test words are not read (k_leaf_osc2pan's second oscillator).
+DEV bool settled_wave(const A2DWave *w, unsigned dphase, int *d, bool settled = true)
+{
+	unsigned dph;
+	const unsigned mm = a2s_mip(dphase, w->period, &dph);
+	d[0] = (int)mm;
+	d[1] = (int)dph;
+	d[2] = (int)w->size[mm];
+	d[3] = (int)w->off[mm];
+	return settled && a2s_wave_ok(w->size[0], w->flags, dph);
+}
 
 // an oscillator's state from / to the unit's state words in memory (wave-uniform address)
 // (volatile: what this wavefront stored a chunk ago must come from memory, not from a scalar or
@@ -426,34 +436,11 @@ void k_leaf_oscpan(const A2DParams *__restrict__ pp, const int *__restrict__ lis
 		// change nothing) and the pitch is constant, so over the whole batch
 		// only the phase moves; mip level, increment and the two pan gains
 		// are fixed.  Anything else takes the per-fragment path.
-		bool settled = sv[SV_MODE] == A2D_OSC_MIPWAVE && sv[SV_DPHASE] && !sv[SV_PRAMP] &&
-				!(sv[SV_P + 3] | sv[SV_P + 2] | sv[SV_A + 3] | sv[SV_A + 2] |
-				  sv[SV_VOL + 3] | sv[SV_VOL + 2] | sv[SV_PAN + 3] | sv[SV_PAN + 2]) &&
-				sv[SV_P] == sv[SV_P + 1] && sv[SV_A] == sv[SV_A + 1] &&
-				sv[SV_VOL] == sv[SV_VOL + 1] && sv[SV_PAN] == sv[SV_PAN + 1];
+		bool settled = a2s_osc_settled(sv[SV_MODE], (unsigned)sv[SV_DPHASE], sv[SV_PRAMP], sv + SV_P, sv + SV_A) &&
+				a2s_arrived(sv + SV_VOL, sv + SV_PAN);
 		if(settled) {
-			const A2DWave *w = waves + sv[SV_WAVE];
-			const unsigned period = w->period, dphase = (unsigned)sv[SV_DPHASE];
-			unsigned dph = ((dphase + 255) >> 8) * period, mm = 0;	// wtosc.c:250-258
-			for(; (dph > (A2D_MAXPHINC << 8)) && (mm < A2D_MIPS - 1); ++mm)
-				dph >>= 1;
-			dph = (unsigned)(((uint64_t)dphase * period) >> mm);
-			settled = w->size[0] && (w->flags & 0x100u) && dph <= (A2D_MAXPHINC << 16);
-			dv[DV_MM] = (int)mm;
-			dv[DV_DPH] = (int)dph;
-			dv[DV_SIZEM] = (int)w->size[mm];
-			dv[DV_DOFF] = (int)w->off[mm];
-			// panmix_process12 gains (panmix.c:89-104)
-			const int vol = sv[SV_VOL], pan = sv[SV_PAN];
-			const int vp = mul64s(pan, vol, 24);
-			int v0 = wsub(vol, vp), v1 = wadd(vol, vp);
-			if(pan > 0xffffff || pan < -0xffffff) {
-				int lim = wshl(vol, 1);
-				if(v0 > lim) v0 = lim;
-				if(v1 > lim) v1 = lim;
-			}
-			dv[DV_V0] = v0;
-			dv[DV_V1] = v1;
+			settled = settled_wave(waves + sv[SV_WAVE], (unsigned)sv[SV_DPHASE], dv + DV_MM);
+			a2s_pan_gains(sv[SV_VOL], sv[SV_PAN], a2s_pan_over(sv[SV_PAN]), &dv[DV_V0], &dv[DV_V1]);
 		}
 		// (a wave the host marked as too big to stay in the caches as coefficient entries - 12 bytes per
 		// sample and tap against 2 - is read as samples: A2D_WF_RAWTAPS, a2amd_wave_upload)
@@ -810,9 +797,7 @@ void k_leaf_osc2pan(const A2DParams *__restrict__ pp, const int *__restrict__ li
 			amp_l[o] = w[OW_A];
 			phlo_l[o] = w[OW_PHASE_LO];
 			phhi_l[o] = w[OW_PHASE_HI];
-			settled = settled && w[OW_MODE] == A2D_OSC_MIPWAVE && dphase_l[o] && !w[OW_PRAMPING] &&
-					!(w[OW_P + 3] | w[OW_P + 2] | w[OW_A + 3] | w[OW_A + 2]) &&
-					w[OW_P] == w[OW_P + 1] && w[OW_A] == w[OW_A + 1];
+			settled = settled && a2s_osc_settled(w[OW_MODE], (unsigned)dphase_l[o], w[OW_PRAMPING], w + OW_P, w + OW_A);
 		}
 		uu[2] = vc.unit[2];
 		const int *wp = ustate + (size_t)uu[2] * A2D_USTATE;
@@ -820,31 +805,12 @@ void k_leaf_osc2pan(const A2DParams *__restrict__ pp, const int *__restrict__ li
 #pragma unroll
 		for(int k = 0; k < 8; ++k)
 			sp[k] = wp[k];		// vol ramper, pan ramper
-		settled = settled && !(sp[3] | sp[2] | sp[7] | sp[6]) && sp[0] == sp[1] && sp[4] == sp[5];
+		settled = settled && a2s_arrived(sp + PW_VOL, sp + PW_PAN);
 		if(settled) {
 #pragma unroll
-			for(int o = 0; o < 2; ++o) {
-				const A2DWave *w = waves + wave_l[o];
-				const unsigned period = w->period, dphase = (unsigned)dphase_l[o];
-				unsigned dph = ((dphase + 255) >> 8) * period, mm = 0;	// wtosc.c:250-258
-				for(; (dph > (A2D_MAXPHINC << 8)) && (mm < A2D_MIPS - 1); ++mm)
-					dph >>= 1;
-				dph = (unsigned)(((uint64_t)dphase * period) >> mm);
-				settled = settled && w->size[0] && (w->flags & 0x100u) && dph <= (A2D_MAXPHINC << 16);
-				od[o][OD_MM] = (int)mm;
-				od[o][OD_DPH] = (int)dph;
-				od[o][OD_SIZEM] = (int)w->size[mm];
-				od[o][OD_DOFF] = (int)w->off[mm];
-			}
-			const int vol = sp[0], pan = sp[4];	// panmix_process12 gains (panmix.c:89-104)
-			const int vp = mul64s(pan, vol, 24);
-			v0l = wsub(vol, vp);
-			v1l = wadd(vol, vp);
-			if(pan > 0xffffff || pan < -0xffffff) {
-				int lim = wshl(vol, 1);
-				if(v0l > lim) v0l = lim;
-				if(v1l > lim) v1l = lim;
-			}
+			for(int o = 0; o < 2; ++o)
+				settled = settled_wave(waves + wave_l[o], (unsigned)dphase_l[o], od[o], settled);
+			a2s_pan_gains(sp[PW_VOL], sp[PW_PAN], a2s_pan_over(sp[PW_PAN]), &v0l, &v1l);
 		}
 		settled_l = settled ? 1 : 0;
 	}
@@ -1510,8 +1476,7 @@ DEV void recs_body(const A2DParams *__restrict__ pp, const int *__restrict__ lis
 						}
 						const int wqv = fs.q.value, wqd = fs.q.delta;
 						ramp_run(fs.q, len);
-						const bool clamp = pan.target > 0xffffff || pan.target < -0xffffff ||
-								pan.value > 0xffffff || pan.value < -0xffffff;
+						const bool clamp = a2s_pan_over(pan.target) || a2s_pan_over(pan.value);
 						ramp_prepare_s(vol, len);
 						ramp_prepare_s(pan, len);
 						if((unsigned)fl < (unsigned)len)
@@ -2231,6 +2196,7 @@ DEV void oscfiltpan_body(const A2DParams *__restrict__ pp, const int *__restrict
 			sv[SV_VOL + k] = w2[PW_VOL + k];
 			sv[SV_PAN + k] = w2[PW_PAN + k];
 		}
+		// (restates a2s_osc_settled() && a2s_arrived(vol, pan), and a2s_osc_settled() below: profiles/settled_header_codeobj.txt)
 		bool settled = sv[SV_MODE] == A2D_OSC_MIPWAVE && sv[SV_DPHASE] && !sv[SV_PRAMP] &&
 				!(sv[SV_P + 3] | sv[SV_P + 2] | sv[SV_A + 3] | sv[SV_A + 2] |
 				  sv[SV_VOL + 3] | sv[SV_VOL + 2] | sv[SV_PAN + 3] | sv[SV_PAN + 2]) &&
@@ -2251,40 +2217,10 @@ DEV void oscfiltpan_body(const A2DParams *__restrict__ pp, const int *__restrict
 					sw[SV_P] == sw[SV_P + 1] && sw[SV_A] == sw[SV_A + 1];
 		}
 		if(settled) {
-			const A2DWave *w = waves + sv[SV_WAVE];
-			const unsigned period = w->period, dphase = (unsigned)sv[SV_DPHASE];
-			unsigned dph = ((dphase + 255) >> 8) * period, mm = 0;
-			for(; (dph > (A2D_MAXPHINC << 8)) && (mm < A2D_MIPS - 1); ++mm)
-				dph >>= 1;
-			dph = (unsigned)(((uint64_t)dphase * period) >> mm);
-			settled = w->size[0] && (w->flags & 0x100u) && dph <= (A2D_MAXPHINC << 16);
-			dv[DV_MM] = (int)mm;
-			dv[DV_DPH] = (int)dph;
-			dv[DV_SIZEM] = (int)w->size[mm];
-			dv[DV_DOFF] = (int)w->off[mm];
-			if constexpr(NOSC == 2) {
-				const A2DWave *w2 = waves + sw[SV_WAVE];
-				const unsigned period2 = w2->period, dphase2 = (unsigned)sw[SV_DPHASE];
-				unsigned dph2 = ((dphase2 + 255) >> 8) * period2, mm2 = 0;
-				for(; (dph2 > (A2D_MAXPHINC << 8)) && (mm2 < A2D_MIPS - 1); ++mm2)
-					dph2 >>= 1;
-				dph2 = (unsigned)(((uint64_t)dphase2 * period2) >> mm2);
-				settled = settled && w2->size[0] && (w2->flags & 0x100u) && dph2 <= (A2D_MAXPHINC << 16);
-				dw[DV_MM] = (int)mm2;
-				dw[DV_DPH] = (int)dph2;
-				dw[DV_SIZEM] = (int)w2->size[mm2];
-				dw[DV_DOFF] = (int)w2->off[mm2];
-			}
-			const int vol = sv[SV_VOL], pan = sv[SV_PAN];
-			const int vp = mul64s(pan, vol, 24);
-			int v0 = wsub(vol, vp), v1 = wadd(vol, vp);
-			if(pan > 0xffffff || pan < -0xffffff) {
-				int lim = wshl(vol, 1);
-				if(v0 > lim) v0 = lim;
-				if(v1 > lim) v1 = lim;
-			}
-			dv[DV_V0] = v0;
-			dv[DV_V1] = v1;
+			settled = settled_wave(waves + sv[SV_WAVE], (unsigned)sv[SV_DPHASE], dv + DV_MM);
+			if constexpr(NOSC == 2)
+				settled = settled_wave(waves + sw[SV_WAVE], (unsigned)sw[SV_DPHASE], dw + DV_MM, settled);
+			a2s_pan_gains(sv[SV_VOL], sv[SV_PAN], a2s_pan_over(sv[SV_PAN]), &dv[DV_V0], &dv[DV_V1]);
 		}
 		dv[DV_SETTLED] = settled ? 1 : 0;
 	}
@@ -2828,8 +2764,7 @@ void k_bus_driver(const A2DParams *__restrict__ pp, const int *__restrict__ list
 			// panmix_process22's rampers (panmix.c:192-249)
 			for(int f = 0; f < p.nfrags; ++f) {
 				const int n = p.fragframes[f];
-				fr[f][4] = pan.target > 0xffffff || pan.target < -0xffffff ||
-						pan.value > 0xffffff || pan.value < -0xffffff;
+				fr[f][4] = a2s_pan_over(pan.target) || a2s_pan_over(pan.value);
 				ramp_prepare(vol, n);
 				ramp_prepare(pan, n);
 				fr[f][0] = vol.value; fr[f][1] = vol.delta;
@@ -2842,7 +2777,7 @@ void k_bus_driver(const A2DParams *__restrict__ pp, const int *__restrict__ list
 		}
 		__syncthreads();
 	}
-	const bool sclamp = pan.value > 0xffffff || pan.value < -0xffffff;
+	const bool sclamp = a2s_pan_over(pan.value);
 	// (a mono owner - inline 0 1; panmix 1 2: the second input is the first, panmix_process12 - has one channel to read
 	// and to zero: its "second channel" is the first one's address again)
 	const int ch1 = vc.own_nch == 1 ? 0 : A2D_FRAG;
@@ -3121,8 +3056,7 @@ enum { PV_VOL = 0, PV_PAN = 4, PV_NWORDS = 8 };
 // (panmix_Process12Add, panmix.c:78-125) for input x, frame = lane
 DEV void pan_window_s(Ramp &vol, Ramp &pan, int x, int off, int len, int lane, int &acc0, int &acc1)
 {
-	const bool clamp = pan.target > 0xffffff || pan.target < -0xffffff ||
-			pan.value > 0xffffff || pan.value < -0xffffff;
+	const bool clamp = a2s_pan_over(pan.target) || a2s_pan_over(pan.value);
 	ramp_prepare_s(vol, len);
 	ramp_prepare_s(pan, len);
 	const int k = lane - off;
@@ -3219,19 +3153,9 @@ DEV void fmpan_body(const A2DParams &p, const int *__restrict__ list, int first,
 			pv[PV_VOL + k] = w1[PW_VOL + k];
 			pv[PV_PAN + k] = w1[PW_PAN + k];
 		}
-		settled = !run_count && !(pv[PV_VOL + 3] | pv[PV_VOL + 2] | pv[PV_PAN + 3] | pv[PV_PAN + 2]) &&
-				pv[PV_VOL] == pv[PV_VOL + 1] && pv[PV_PAN] == pv[PV_PAN + 1];
-		if(settled) {
-			const int vol = pv[PV_VOL], pan = pv[PV_PAN];
-			const int vp = mul64s(pan, vol, 24);
-			v0 = wsub(vol, vp);
-			v1 = wadd(vol, vp);
-			if(pan > 0xffffff || pan < -0xffffff) {
-				int lim = wshl(vol, 1);
-				if(v0 > lim) v0 = lim;
-				if(v1 > lim) v1 = lim;
-			}
-		}
+		settled = !run_count && a2s_arrived(pv + PV_VOL, pv + PV_PAN);
+		if(settled)
+			a2s_pan_gains(pv[PV_VOL], pv[PV_PAN], a2s_pan_over(pv[PV_PAN]), &v0, &v1);
 	}
 	int curB = 0, curC = 0, actC = actB;	// record cursors / liveness of the two stages
 	int *row = tile + lane * FILT_PITCH;

@@ -16,6 +16,7 @@
 #include "a2amd_host.h"
 #include "a2amd_noisemap.h"
 #include "a2amd_cutsweep.h"
+#include "a2amd_settled.h"
 
 namespace a2h { thread_local char g_err[256] = ""; }
 
@@ -1217,12 +1218,9 @@ static void shadow_wave(a2amd_ctx *c, HUnit &u, unsigned frames)
 	}
 	shadow_run_pitch(c, u, frames);
 	if(u.mode == A2D_OSC_MIPWAVE) {		// wtosc_wavetable, wtosc.c:239-286
-		unsigned dph = ((u.dphase + 255) >> 8) * w.period;
-		unsigned mm = 0;
-		for(; (dph > (A2D_MAXPHINC << 8)) && (mm < A2D_MIPS - 1); ++mm)
-			dph >>= 1;
+		unsigned dph;
+		const unsigned mm = a2s_mip(u.dphase, w.period, &dph);
 		uint64_t ph = u.phase >> mm;
-		dph = (unsigned)(((uint64_t)u.dphase * w.period) >> mm);
 		if(looped) {
 			const uint64_t m = (uint64_t)w.size[mm] << 24;
 			if(!(m & (m - 1)))

@@ -195,6 +195,7 @@ DEV void osc_mipwave(Ctx &c, uint32_t desc, Osc &o, int offset, int frames)
 		return;
 	}
 	osc_run_pitch(p, o, frames);
+	// (restates a2s_mip() around the ramper's branch: profiles/settled_header_codeobj.txt)
 	unsigned dph = ((o.dphase + 255) >> 8) * w.period;
 	ramp_prepare(o.a, frames);
 	unsigned mm = 0;
@@ -330,8 +331,7 @@ DEV void panmix_process(Ctx &c, uint32_t desc, int *w, int offset, int frames)
 	} else {
 		// clamp variant is chosen before the rampers are prepared,
 		// panmix.c:117-135 / :171-189 / :231-249
-		bool clamp = pan.target > 0xffffff || pan.target < -0xffffff ||
-				pan.value > 0xffffff || pan.value < -0xffffff;
+		bool clamp = a2s_pan_over(pan.target) || a2s_pan_over(pan.value);
 		ramp_prepare(vol, frames);
 		ramp_prepare(pan, frames);
 		if(in) {

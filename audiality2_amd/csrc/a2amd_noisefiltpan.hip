@@ -32,8 +32,7 @@
 // reads the same words and comes to the same answer.
 #include <hip/hip_runtime.h>
 #include "a2amd_device.h"
-#include "a2amd_dsp.h"
-#include "a2amd_noisemap.h"
+#include "a2amd_noisevoice.h"
 #include "a2amd_filt.h"
 
 #define NFP_MAXV  64	// voices per workgroup: the lanes of the filter wavefront
@@ -54,12 +53,6 @@
 #define NFP_WAVES 8
 #define NFP_WORKERS 6
 
-static __device__ __forceinline__ int nf_rdl(int v, int lane) { return __builtin_amdgcn_readlane(v, lane); }
-
-// a ramper a2_PrepareRamper (a2_dsp.h:128-149) leaves at its target with delta and timer 0 whatever the window's length
-// (k_leaf_noisepan's test)
-static __device__ __forceinline__ bool nf_at_rest(const int *r) { return !r[3] || ((unsigned)r[3] < 256u && r[0] == r[1]); }
-
 __global__ __launch_bounds__(64 * NFP_WAVES)
 void k_leaf_noisefiltpan(const A2DParams *__restrict__ pp, const int *__restrict__ list, int nlist, int vpg,
 		const A2DVoice *__restrict__ voices, const A2DRun *__restrict__ runs, int *ustate,
@@ -76,9 +69,9 @@ void k_leaf_noisefiltpan(const A2DParams *__restrict__ pp, const int *__restrict
 	const int tsize = vpg * NFP_PITCH;
 
 	// lane v: voice v of this workgroup, in every wavefront
-	int u0 = 0, u1 = 0, u2 = 0, my_off = -1, my_nch = 2, col = 0;
-	unsigned d_l = 0, phlo_l = 0, phhi_l = 0, seed_l = 0;
-	int h_l = 0, g_l = 0, v0_l = 0, v1_l = 0, v0r_l = 0, v1r_l = 0;
+	int u0 = 0, u1 = 0, u2 = 0, my_off = -1, my_nch = 2;
+	NoiseV nz = { 0, 0, 0, 0, 0, 0, 0 };
+	int v0_l = 0, v1_l = 0, v0r_l = 0, v1r_l = 0;
 	int qt_l = 0, ff_l = 0, lp_l = 0, bp_l = 0, hp_l = 0, d1_l = 0, d2_l = 0;
 	bool ok = false;
 	if(lane < nv) {
@@ -93,39 +86,26 @@ void k_leaf_noisefiltpan(const A2DParams *__restrict__ pp, const int *__restrict
 			const int *w0 = ustate + (size_t)u0 * A2D_USTATE;
 			const int *w1 = ustate + (size_t)u1 * A2D_USTATE;
 			const int *w2 = ustate + (size_t)u2 * A2D_USTATE;
-			d_l = (unsigned)w0[OW_DPHASE];
+			nz.d = (unsigned)w0[OW_DPHASE];
 			// at rest: wtosc_run_pitch returns early, a2_PrepareRamper finds every ramper arrived, no R_F1RAMP is pending
-			ok = vc.nunits == 3 && my_off >= 0 && w0[OW_MODE] == A2D_OSC_NOISE && d_l && !w0[OW_PRAMPING] &&
-					nf_at_rest(w0 + OW_P) && nf_at_rest(w0 + OW_A) && nf_at_rest(w1 + FW_Q) && !w1[FW_RAMP] &&
-					nf_at_rest(w2 + PW_VOL) && nf_at_rest(w2 + PW_PAN);
+			ok = vc.nunits == 3 && my_off >= 0 && w0[OW_MODE] == A2D_OSC_NOISE && nz.d && !w0[OW_PRAMPING] &&
+					a2s_at_rest(w0 + OW_P) && a2s_at_rest(w0 + OW_A) && a2s_at_rest(w1 + FW_Q) && !w1[FW_RAMP] &&
+					a2s_at_rest(w2 + PW_VOL) && a2s_at_rest(w2 + PW_PAN);
 			if(ok) {
-				phlo_l = (unsigned)w0[OW_PHASE_LO];
-				phhi_l = (unsigned)w0[OW_PHASE_HI];
-				h_l = w0[OW_NOISE];
-				seed_l = (unsigned)w0[OW_SEED];
-				g_l = w0[OW_A + 1];
-				// its column of the batch's seed table (a2d_noise_seed's bounds)
-				if(nseed) {
-					const int k = nslot[u0];
-					col = k > 0 && k <= nnoise ? k : 0;
-				}
+				noisev_load(nz, w0, u0, nseed, nslot, nnoise);
 				// f12_process's loop constants (filter12.c:99-100) with the q ramper at its target
 				qt_l = w1[FW_Q + 1];
 				ff_l = w1[FW_F1] >> 12;
 				lp_l = w1[FW_LP]; bp_l = w1[FW_BP]; hp_l = w1[FW_HP];
 				d1_l = w1[FW_D1A];
 				d2_l = w1[FW_D2A];
-				// panmix_process12's two gains (panmix.c:84-104) as k_leaf_noisepan derives them.  Whether they are clamped
-				// is decided in front of a2_PrepareRamper (panmix.c:120-124): the first window still sees the value a
-				// finished ramp stopped at, the others the target
-				const int vol = w2[PW_VOL + 1], pan = w2[PW_PAN + 1], pwas = w2[PW_PAN];
-				const int vp = mul64s(pan, vol, 24), lim = wshl(vol, 1);
-				const int v0 = wsub(vol, vp), v1 = wadd(vol, vp);
-				const bool cr = pan > 0xffffff || pan < -0xffffff, c0 = cr || pwas > 0xffffff || pwas < -0xffffff;
-				v0_l = c0 && v0 > lim ? lim : v0;
-				v1_l = c0 && v1 > lim ? lim : v1;
-				v0r_l = cr && v0 > lim ? lim : v0;
-				v1r_l = cr && v1 > lim ? lim : v1;
+				// panmix_process12's two gains as k_leaf_noisepan derives them.  Whether they are clamped is decided in front of
+				// a2_PrepareRamper (panmix.c:120-124): the first window still sees the value a finished ramp stopped at, the
+				// others the target
+				const int vol = w2[PW_VOL + 1], pan = w2[PW_PAN + 1];
+				const bool cr = a2s_pan_over(pan), c0 = cr || a2s_pan_over(w2[PW_PAN]);
+				a2s_pan_gains(vol, pan, c0, &v0_l, &v1_l);
+				a2s_pan_gains(vol, pan, cr, &v0r_l, &v1r_l);
 			}
 		}
 	}
@@ -137,7 +117,7 @@ void k_leaf_noisefiltpan(const A2DParams *__restrict__ pp, const int *__restrict
 	const bool lpraw = __all(!ok || (bp_l == 0 && hp_l == 0));
 	// the workgroup's share of its bus, fragment by fragment, where it has one bus (stage D)
 	__shared__ int nf_acc[3][2][A2D_FRAG];
-	const int wg_off = nf_rdl(my_off, (int)__builtin_ctzll(todo));
+	const int wg_off = rdl(my_off, (int)__builtin_ctzll(todo));
 	const bool wgbus = __all(!ok || (my_off == wg_off && my_nch == 2));
 	const int nsteps = nfrags + 3;
 
@@ -162,7 +142,7 @@ void k_leaf_noisefiltpan(const A2DParams *__restrict__ pp, const int *__restrict
 		// state out: the filter's words as ctl_store / k_win_render_f leave them
 		if(ok) {
 			int *w1 = ustate + (size_t)u1 * A2D_USTATE;
-			w1[FW_Q] = w1[FW_Q + 1]; w1[FW_Q + 2] = w1[FW_Q + 3] = 0;
+			ramp_settle(w1 + FW_Q);
 			w1[FW_D1A] = d1_l;
 			w1[FW_D2A] = d2_l;
 		}
@@ -228,35 +208,19 @@ void k_leaf_noisefiltpan(const A2DParams *__restrict__ pp, const int *__restrict
 			if(n > 0) {
 				// the generator word in front of each voice's window: the seed pass's, or - no column in this batch - the
 				// word its last window left
-				if(col && mylane)
-					seed_l = nseed[(size_t)f * (size_t)nnoise + (size_t)(col - 1)];
+				if(nz.col && mylane)
+					nz.seed = noisev_seed(nz, nseed, f, nnoise);
 				int *tile = nf_tiles + (f % 3) * tsize;
 				const unsigned fl = (unsigned)min(lane, n - 1);	// (lanes beyond the fragment's frames: the last frame's, stored as 0)
 				for(unsigned long long m = mine; m; m &= m - 1) {
 					const int v = (int)__builtin_ctzll(m);
-					const unsigned d = (unsigned)nf_rdl((int)d_l, v), ph = (unsigned)nf_rdl((int)phlo_l, v);
-					const unsigned s0 = (unsigned)nf_rdl((int)seed_l, v);
-					const int h = nf_rdl(h_l, v);
-					// draw j + 1 of the window, in lane j
-					const uint32_t w = a2nm_word(mapA, mapC, s0);
-					const int val = a2nm_value(w);
-					// the draw this lane's frame holds
-					const unsigned c = a2nm_upto(ph, d, fl);
-					const int got = __builtin_amdgcn_ds_bpermute((int)(((c - 1u) & 63u) << 2), val);
-					const int x = c ? got : h;
-					// what the window leaves: the last frame's sample, the word after its last draw
-					const unsigned total = (unsigned)nf_rdl((int)c, n - 1);
-					const int hn = nf_rdl(x, n - 1);
-					const unsigned sn = total ? (unsigned)nf_rdl((int)w, (int)total - 1) : s0;
-					const bool me = lane == v;
-					h_l = me ? hn : h_l;
-					seed_l = me ? sn : seed_l;
+					const int x = noisev_window(nz, v, lane, fl, n, mapA, mapC);
 					// wtosc.c:148 at the amplitude, filter12.c:105's shift
-					const int y = a2nm_out(x, nf_rdl(g_l, v));
+					const int y = a2nm_out(x, rdl(nz.g, v));
 					tile[v * NFP_PITCH + lane] = lane < n ? y >> 5 : 0;
 				}
 				// every voice moves on by n frames (all lanes at once)
-				phlo_l += (unsigned)n * d_l;
+				nz.phlo += (unsigned)n * nz.d;
 				total_frames += (unsigned)n;
 			}
 		}
@@ -270,20 +234,20 @@ void k_leaf_noisefiltpan(const A2DParams *__restrict__ pp, const int *__restrict
 				int cur_off = -1, cur_nch = 2;
 				for(unsigned long long m = mine; m; m &= m - 1) {
 					const int v = (int)__builtin_ctzll(m);
-					const int voff = nf_rdl(my_off, v);
+					const int voff = rdl(my_off, v);
 					if(voff != cur_off) {
 						if(cur_off >= 0)
 							bus_add(cur_off, cur_nch, f, acc0, acc1);
 						acc0 = acc1 = 0;
 						cur_off = voff;
-						cur_nch = nf_rdl(my_nch, v);
+						cur_nch = rdl(my_nch, v);
 					}
 					int y = tile[v * NFP_PITCH + lane];
 					if(lpraw)
-						y = wmul(y, nf_rdl(lp_l, v)) >> 3;	// (filt_step: the row holds l)
+						y = wmul(y, rdl(lp_l, v)) >> 3;	// (filt_step: the row holds l)
 					if(lane < n) {
-						acc0 = wadd(acc0, mul64s(y, nf_rdl(cfirst ? v0_l : v0r_l, v), 24));
-						acc1 = wadd(acc1, mul64s(y, nf_rdl(cfirst ? v1_l : v1r_l, v), 24));
+						acc0 = wadd(acc0, mul64s(y, rdl(cfirst ? v0_l : v0r_l, v), 24));
+						acc1 = wadd(acc1, mul64s(y, rdl(cfirst ? v1_l : v1r_l, v), 24));
 					}
 				}
 				if(cur_off >= 0)
@@ -295,20 +259,8 @@ void k_leaf_noisefiltpan(const A2DParams *__restrict__ pp, const int *__restrict
 	}
 
 	// state out: ctl_store's words for the same windows
-	if(mylane) {
-		int *w0 = ustate + (size_t)u0 * A2D_USTATE;
-		int *w2 = ustate + (size_t)u2 * A2D_USTATE;
-		const uint64_t ph = ((uint64_t)(unsigned)w0[OW_PHASE_LO] | ((uint64_t)phhi_l << 32)) + (uint64_t)total_frames * d_l;
-		w0[OW_PHASE_LO] = (int)(unsigned)ph;
-		w0[OW_PHASE_HI] = (int)(unsigned)(ph >> 32);
-		w0[OW_NOISE] = h_l;
-		w0[OW_SEED] = (int)seed_l;
-		// (a2_PrepareRamper on a ramper at rest: value = target, delta = timer = 0)
-		w0[OW_P] = w0[OW_P + 1]; w0[OW_P + 2] = w0[OW_P + 3] = 0;
-		w0[OW_A] = w0[OW_A + 1]; w0[OW_A + 2] = w0[OW_A + 3] = 0;
-		w2[PW_VOL] = w2[PW_VOL + 1]; w2[PW_VOL + 2] = w2[PW_VOL + 3] = 0;
-		w2[PW_PAN] = w2[PW_PAN + 1]; w2[PW_PAN + 2] = w2[PW_PAN + 3] = 0;
-	}
+	if(mylane)
+		noisev_store(nz, total_frames, ustate + (size_t)u0 * A2D_USTATE, ustate + (size_t)u2 * A2D_USTATE);
 }
 
 // voices per workgroup: at most NFP_MAXV (one per lane of the filter wavefront)

@@ -20,17 +20,9 @@
 // that is not at rest all the same is left alone here, as one with records is.
 #include <hip/hip_runtime.h>
 #include "a2amd_device.h"
-#include "a2amd_dsp.h"
-#include "a2amd_noisemap.h"
+#include "a2amd_noisevoice.h"
 
 #define NP_WPB 4	// wavefronts per workgroup
-
-static __device__ __forceinline__ int np_rdl(int v, int lane) { return __builtin_amdgcn_readlane(v, lane); }
-
-// a ramper a2_PrepareRamper (a2_dsp.h:128-149) leaves at its target with delta and timer 0 whatever the window's length:
-// the timer at 0, or - a write without a duration that has not met a window yet, a2_SetRamper :161-170 - below one frame
-// with the value already there
-static __device__ __forceinline__ bool np_at_rest(const int *r) { return !r[3] || ((unsigned)r[3] < 256u && r[0] == r[1]); }
 
 __global__ __launch_bounds__(64 * NP_WPB)
 void k_leaf_noisepan(const A2DParams *__restrict__ pp, const int *__restrict__ list, int nlist, int vpw,
@@ -50,9 +42,9 @@ void k_leaf_noisepan(const A2DParams *__restrict__ pp, const int *__restrict__ l
 	a2nm_map((unsigned)lane + 1u, &mapA, &mapC);
 
 	// lane v: voice v of this wavefront's run
-	int u0 = 0, u1 = 0, my_off = -1, my_nch = 2, col = 0;
-	unsigned d_l = 0, phlo_l = 0, phhi_l = 0, seed_l = 0;
-	int h_l = 0, g_l = 0, v0_l = 0, v1_l = 0, v0r_l = 0, v1r_l = 0;
+	int u0 = 0, u1 = 0, my_off = -1, my_nch = 2;
+	NoiseV nz = { 0, 0, 0, 0, 0, 0, 0 };
+	int v0_l = 0, v1_l = 0, v0r_l = 0, v1r_l = 0;
 	bool ok = false;
 	if(lane < nv) {
 		const int slot = list[first + lane];
@@ -64,32 +56,18 @@ void k_leaf_noisepan(const A2DParams *__restrict__ pp, const int *__restrict__ l
 			my_nch = vc.out_nch;
 			const int *w0 = ustate + (size_t)u0 * A2D_USTATE;
 			const int *w1 = ustate + (size_t)u1 * A2D_USTATE;
-			d_l = (unsigned)w0[OW_DPHASE];
+			nz.d = (unsigned)w0[OW_DPHASE];
 			// at rest: wtosc_run_pitch returns early, and a2_PrepareRamper finds every ramper arrived
-			ok = vc.nunits == 2 && my_off >= 0 && w0[OW_MODE] == A2D_OSC_NOISE && d_l && !w0[OW_PRAMPING] &&
-					np_at_rest(w0 + OW_P) && np_at_rest(w0 + OW_A) && np_at_rest(w1 + PW_VOL) && np_at_rest(w1 + PW_PAN);
+			ok = vc.nunits == 2 && my_off >= 0 && w0[OW_MODE] == A2D_OSC_NOISE && nz.d && !w0[OW_PRAMPING] &&
+					a2s_at_rest(w0 + OW_P) && a2s_at_rest(w0 + OW_A) && a2s_at_rest(w1 + PW_VOL) && a2s_at_rest(w1 + PW_PAN);
 			if(ok) {
-				phlo_l = (unsigned)w0[OW_PHASE_LO];
-				phhi_l = (unsigned)w0[OW_PHASE_HI];
-				h_l = w0[OW_NOISE];
-				seed_l = (unsigned)w0[OW_SEED];
-				g_l = w0[OW_A + 1];
-				// its column of the batch's seed table (a2d_noise_seed's bounds)
-				if(nseed) {
-					const int k = nslot[u0];
-					col = k > 0 && k <= nnoise ? k : 0;
-				}
-				// panmix_process12's two gains (panmix.c:84-104) as k_leaf_oscpan's settled path derives them.  Whether
-				// they are clamped is decided in front of a2_PrepareRamper (panmix.c:120-124): the first window still
-				// sees the value a finished ramp stopped at, the others the target
-				const int vol = w1[PW_VOL + 1], pan = w1[PW_PAN + 1], pwas = w1[PW_PAN];
-				const int vp = mul64s(pan, vol, 24), lim = wshl(vol, 1);
-				const int v0 = wsub(vol, vp), v1 = wadd(vol, vp);
-				const bool cr = pan > 0xffffff || pan < -0xffffff, c0 = cr || pwas > 0xffffff || pwas < -0xffffff;
-				v0_l = c0 && v0 > lim ? lim : v0;
-				v1_l = c0 && v1 > lim ? lim : v1;
-				v0r_l = cr && v0 > lim ? lim : v0;
-				v1r_l = cr && v1 > lim ? lim : v1;
+				noisev_load(nz, w0, u0, nseed, nslot, nnoise);
+				// panmix_process12's two gains.  Whether they are clamped is decided in front of a2_PrepareRamper
+				// (panmix.c:120-124): the first window still sees the value a finished ramp stopped at, the others the target
+				const int vol = w1[PW_VOL + 1], pan = w1[PW_PAN + 1];
+				const bool cr = a2s_pan_over(pan), c0 = cr || a2s_pan_over(w1[PW_PAN]);
+				a2s_pan_gains(vol, pan, c0, &v0_l, &v1_l);
+				a2s_pan_gains(vol, pan, cr, &v0r_l, &v1r_l);
 			}
 		}
 	}
@@ -104,14 +82,14 @@ void k_leaf_noisepan(const A2DParams *__restrict__ pp, const int *__restrict__ l
 			continue;
 		// the generator word in front of each voice's window: the seed pass's, or - no column in this batch - the word
 		// its last window left
-		if(col)
-			seed_l = nseed[(size_t)f * (size_t)nnoise + (size_t)(col - 1)];
+		if(nz.col)
+			nz.seed = noisev_seed(nz, nseed, f, nnoise);
 		int acc0 = 0, acc1 = 0;
 		int cur_off = -1, cur_nch = 2;
 		const unsigned fl = (unsigned)min(lane, n - 1);	// (lanes beyond the fragment's frames: the last frame's, dropped below)
 		for(unsigned long long m = todo; m; m &= m - 1) {
 			const int v = (int)__builtin_ctzll(m);
-			const int voff = np_rdl(my_off, v);
+			const int voff = rdl(my_off, v);
 			if(voff != cur_off) {
 				if(cur_off >= 0) {
 					int *dst = busmem + cur_off + (size_t)f * cur_nch * A2D_FRAG;
@@ -122,29 +100,13 @@ void k_leaf_noisepan(const A2DParams *__restrict__ pp, const int *__restrict__ l
 				}
 				acc0 = acc1 = 0;
 				cur_off = voff;
-				cur_nch = np_rdl(my_nch, v);
+				cur_nch = rdl(my_nch, v);
 			}
-			const unsigned d = (unsigned)np_rdl((int)d_l, v), ph = (unsigned)np_rdl((int)phlo_l, v);
-			const unsigned s0 = (unsigned)np_rdl((int)seed_l, v);
-			const int h = np_rdl(h_l, v);
-			// draw j + 1 of the window, in lane j
-			const uint32_t w = a2nm_word(mapA, mapC, s0);
-			const int val = a2nm_value(w);
-			// the draw this lane's frame holds
-			const unsigned c = a2nm_upto(ph, d, fl);
-			const int got = __builtin_amdgcn_ds_bpermute((int)(((c - 1u) & 63u) << 2), val);
-			const int x = c ? got : h;
-			// what the window leaves: the last frame's sample, the word after its last draw
-			const unsigned total = (unsigned)np_rdl((int)c, n - 1);
-			const int hn = np_rdl(x, n - 1);
-			const unsigned sn = total ? (unsigned)np_rdl((int)w, (int)total - 1) : s0;
-			const bool me = lane == v;
-			h_l = me ? hn : h_l;
-			seed_l = me ? sn : seed_l;
+			const int x = noisev_window(nz, v, lane, fl, n, mapA, mapC);
 			if(lane < n) {
-				const int y = a2nm_out(x, np_rdl(g_l, v));
-				acc0 = wadd(acc0, mul64s(y, np_rdl(v0_l, v), 24));
-				acc1 = wadd(acc1, mul64s(y, np_rdl(v1_l, v), 24));
+				const int y = a2nm_out(x, rdl(nz.g, v));
+				acc0 = wadd(acc0, mul64s(y, rdl(v0_l, v), 24));
+				acc1 = wadd(acc1, mul64s(y, rdl(v1_l, v), 24));
 			}
 		}
 		if(cur_off >= 0) {
@@ -155,27 +117,15 @@ void k_leaf_noisepan(const A2DParams *__restrict__ pp, const int *__restrict__ l
 				atomicAdd(&dst[A2D_FRAG + lane], acc1);
 		}
 		// every voice moves on by n frames (all lanes at once)
-		phlo_l += (unsigned)n * d_l;
+		nz.phlo += (unsigned)n * nz.d;
 		total_frames += (unsigned)n;
 		v0_l = v0r_l;
 		v1_l = v1r_l;
 	}
 
 	// state out: ctl_store's words for the same windows
-	if(ok) {
-		int *w0 = ustate + (size_t)u0 * A2D_USTATE;
-		int *w1 = ustate + (size_t)u1 * A2D_USTATE;
-		const uint64_t ph = ((uint64_t)(unsigned)w0[OW_PHASE_LO] | ((uint64_t)phhi_l << 32)) + (uint64_t)total_frames * d_l;
-		w0[OW_PHASE_LO] = (int)(unsigned)ph;
-		w0[OW_PHASE_HI] = (int)(unsigned)(ph >> 32);
-		w0[OW_NOISE] = h_l;
-		w0[OW_SEED] = (int)seed_l;
-		// (a2_PrepareRamper on a ramper at rest: value = target, delta = timer = 0)
-		w0[OW_P] = w0[OW_P + 1]; w0[OW_P + 2] = w0[OW_P + 3] = 0;
-		w0[OW_A] = w0[OW_A + 1]; w0[OW_A + 2] = w0[OW_A + 3] = 0;
-		w1[PW_VOL] = w1[PW_VOL + 1]; w1[PW_VOL + 2] = w1[PW_VOL + 3] = 0;
-		w1[PW_PAN] = w1[PW_PAN + 1]; w1[PW_PAN + 2] = w1[PW_PAN + 3] = 0;
-	}
+	if(ok)
+		noisev_store(nz, total_frames, ustate + (size_t)u0 * A2D_USTATE, ustate + (size_t)u1 * A2D_USTATE);
 }
 
 // voices per wavefront: at most 64 (one per lane)

@@ -68,12 +68,8 @@ void k_leaf_oscbare(const A2DParams *__restrict__ pp, const int *__restrict__ li
 
 	// lane v: voice v of this wavefront's run, loaded as ctl_load loads an oscillator
 	OscV o;
-	o.mode = A2D_OSC_OFF; o.wave = -1; o.dphase = 0; o.phase = 0; o.p_ramping = 0;
-	o.p.value = o.p.target = o.p.delta = o.p.timer = 0;
-	o.a = o.p;
-	o.noise = 0; o.seed = 0;
+	oscv_clear(o);
 	o.cmm = -2;
-	o.wperiod = o.wflags = o.wsize0 = o.csize = o.coff = 0;
 	int u0 = 0, my_off = -1, my_nch = 1;
 	bool ok = false;
 	if(lane < nv) {
@@ -83,14 +79,7 @@ void k_leaf_oscbare(const A2DParams *__restrict__ pp, const int *__restrict__ li
 			u0 = vc.unit[0];
 			my_off = vc.out_off;
 			my_nch = vc.out_nch;
-			const int *w0 = ustate + (size_t)u0 * A2D_USTATE;
-			o.mode = w0[OW_MODE]; o.wave = w0[OW_WAVE]; o.dphase = (unsigned)w0[OW_DPHASE];
-			o.phase = (uint64_t)(unsigned)w0[OW_PHASE_LO] | ((uint64_t)(unsigned)w0[OW_PHASE_HI] << 32);
-			o.p_ramping = w0[OW_PRAMPING];
-			o.p = ramp_load(w0 + OW_P);
-			o.a = ramp_load(w0 + OW_A);
-			o.noise = w0[OW_NOISE];
-			o.seed = (unsigned)w0[OW_SEED];
+			oscv_load(o, ustate + (size_t)u0 * A2D_USTATE);
 			ok = vc.nunits == 1 && my_off >= 0 && my_nch >= 1 && (o.mode == A2D_OSC_MIPWAVE || o.mode == A2D_OSC_OFF);
 		}
 	}
@@ -145,16 +134,8 @@ void k_leaf_oscbare(const A2DParams *__restrict__ pp, const int *__restrict__ li
 	}
 
 	// state out: ctl_store's words of an oscillator
-	if(ok) {
-		int *w0 = ustate + (size_t)u0 * A2D_USTATE;
-		w0[OW_MODE] = o.mode; w0[OW_WAVE] = o.wave; w0[OW_DPHASE] = (int)o.dphase;
-		w0[OW_PHASE_LO] = (int)(unsigned)o.phase; w0[OW_PHASE_HI] = (int)(unsigned)(o.phase >> 32);
-		w0[OW_PRAMPING] = o.p_ramping;
-		ramp_store(w0 + OW_P, o.p);
-		ramp_store(w0 + OW_A, o.a);
-		w0[OW_NOISE] = o.noise;
-		w0[OW_SEED] = (int)o.seed;
-	}
+	if(ok)
+		oscv_store(ustate + (size_t)u0 * A2D_USTATE, o);
 }
 
 // voices per wavefront: at most 64 (one per lane)

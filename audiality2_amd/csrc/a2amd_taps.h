@@ -12,8 +12,6 @@
 #define FAST_WPB   4		// wavefronts per workgroup
 #define FAST_FCH   A2D_FAST_FCH	// fragments whose bus sums stay in registers at a time
 
-DEV int rfl(int x) { return __builtin_amdgcn_readfirstlane(x); }
-DEV int rdl(int v, int lane) { return __builtin_amdgcn_readlane(v, lane); }
 // park a wave-uniform value back in lane 'sel' of a per-lane register
 #define WRL(reg, val) reg = me ? (val) : reg
 

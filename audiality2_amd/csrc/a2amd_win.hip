@@ -428,13 +428,8 @@ DEV void win_pan(unsigned head, int vol, int dvol, int pan, int dpan, int y, int
 	const bool clamp = (head & WH_CLAMP) != 0;
 	if(!(dvol | dpan)) {
 		// volume and pan at rest - most windows: the two gains are the window's, worked out on the scalar unit
-		const int vp = mul64s(pan, vol, 24);
-		int v0 = wsub(vol, vp), v1 = wadd(vol, vp);
-		if(clamp) {
-			const int lim = wshl(vol, 1);
-			if(v0 > lim) v0 = lim;
-			if(v1 > lim) v1 = lim;
-		}
+		int v0, v1;
+		a2s_pan_gains(vol, pan, clamp, &v0, &v1);
 		if(in) {
 			acc0 = wadd(acc0, mul64s(y, v0, 24));
 			acc1 = wadd(acc1, mul64s(y, v1, 24));

@@ -92,6 +92,43 @@ DEV void osc_wave_fields(const A2DWave *waves, OscV &o)
 	}
 }
 
+// ... as nothing (a lane without a voice), from a unit's state words, and back to them
+DEV void oscv_clear(OscV &o)
+{
+	o.mode = A2D_OSC_OFF; o.wave = -1; o.dphase = 0; o.phase = 0; o.p_ramping = 0;
+	o.p.value = o.p.target = o.p.delta = o.p.timer = 0;
+	o.a = o.p;
+	o.noise = 0; o.seed = 0;
+	o.cmm = -1;
+	o.wperiod = o.wflags = o.wsize0 = o.csize = o.coff = 0;
+}
+
+DEV void oscv_load(OscV &o, const int *w)
+{
+	o.mode = w[OW_MODE]; o.wave = w[OW_WAVE]; o.dphase = (unsigned)w[OW_DPHASE];
+	o.phase = (uint64_t)(unsigned)w[OW_PHASE_LO] | ((uint64_t)(unsigned)w[OW_PHASE_HI] << 32);
+	o.p_ramping = w[OW_PRAMPING];
+	o.p = ramp_load(w + OW_P);
+	o.a = ramp_load(w + OW_A);
+	o.noise = w[OW_NOISE];
+	o.seed = (unsigned)w[OW_SEED];
+	// (the wave's descriptor is read when a window or a phase write first needs it: the state words of
+	// a unit that has not been initialized yet - a recycled slot - may hold anything)
+	o.cmm = -2;
+	o.wperiod = o.wflags = o.wsize0 = o.csize = o.coff = 0;
+}
+
+DEV void oscv_store(int *w, const OscV &o)
+{
+	w[OW_MODE] = o.mode; w[OW_WAVE] = o.wave; w[OW_DPHASE] = (int)o.dphase;
+	w[OW_PHASE_LO] = (int)(unsigned)o.phase; w[OW_PHASE_HI] = (int)(unsigned)(o.phase >> 32);
+	w[OW_PRAMPING] = o.p_ramping;
+	ramp_store(w + OW_P, o.p);
+	ramp_store(w + OW_A, o.a);
+	w[OW_NOISE] = o.noise;
+	w[OW_SEED] = (int)o.seed;
+}
+
 // a2_PrepareRamper, a2_dsp.h:128-149 (the 64 bit division by an exact double division: the first
 // branch is only taken with timer >= 256 * frames > 0)
 DEV void ramp_prepare_v(Ramp &r, int frames)
@@ -163,6 +200,7 @@ DEV int osc_window_v(const A2DWave *waves, const PTab &ptab, OscV &o, int len, i
 		}
 		const unsigned period = o.wperiod;
 		run_pitch_v(ptab, o, len);
+		// (restates a2s_mip() around the ramper's branch: profiles/settled_header_codeobj.txt)
 		unsigned dph = ((o.dphase + 255) >> 8) * period;
 		ramp_prepare_v(o.a, len);
 		int mm = 0;
@@ -308,14 +346,8 @@ DEV void ctl_clear(CtlVoice<NOSC, FILT> &s)
 	for(int o = 0; o <= NOSC + FILT; ++o)
 		s.uu[o] = 0;
 #pragma unroll
-	for(int o = 0; o < NOSC; ++o) {
-		s.os[o].mode = 0; s.os[o].wave = -1; s.os[o].dphase = 0; s.os[o].phase = 0; s.os[o].p_ramping = 0;
-		s.os[o].p.value = s.os[o].p.target = s.os[o].p.delta = s.os[o].p.timer = 0;
-		s.os[o].a = s.os[o].p;
-		s.os[o].noise = 0; s.os[o].seed = 0;
-		s.os[o].cmm = -1;
-		s.os[o].wperiod = s.os[o].wflags = s.os[o].wsize0 = s.os[o].csize = s.os[o].coff = 0;
-	}
+	for(int o = 0; o < NOSC; ++o)
+		oscv_clear(s.os[o]);
 	s.vol.value = s.vol.target = s.vol.delta = s.vol.timer = 0;
 	s.pan = s.vol;
 	s.active = s.pending_fresh = 0;
@@ -326,20 +358,8 @@ template<int NOSC, int FILT>
 DEV void ctl_load(CtlVoice<NOSC, FILT> &s, const int *ustate, const int *vactive, int slot)
 {
 #pragma unroll
-	for(int o = 0; o < NOSC; ++o) {
-		const int *w = ustate + (size_t)s.uu[o] * A2D_USTATE;
-		s.os[o].mode = w[OW_MODE]; s.os[o].wave = w[OW_WAVE]; s.os[o].dphase = (unsigned)w[OW_DPHASE];
-		s.os[o].phase = (uint64_t)(unsigned)w[OW_PHASE_LO] | ((uint64_t)(unsigned)w[OW_PHASE_HI] << 32);
-		s.os[o].p_ramping = w[OW_PRAMPING];
-		s.os[o].p = ramp_load(w + OW_P);
-		s.os[o].a = ramp_load(w + OW_A);
-		s.os[o].noise = w[OW_NOISE];
-		s.os[o].seed = (unsigned)w[OW_SEED];
-		// (the wave's descriptor is read when a window or a phase write first needs it: the state words of
-		// a unit that has not been initialized yet - a recycled slot - may hold anything)
-		s.os[o].cmm = -2;
-		s.os[o].wperiod = s.os[o].wflags = s.os[o].wsize0 = s.os[o].csize = s.os[o].coff = 0;
-	}
+	for(int o = 0; o < NOSC; ++o)
+		oscv_load(s.os[o], ustate + (size_t)s.uu[o] * A2D_USTATE);
 	if(FILT) {
 		const int *wf = ustate + (size_t)s.uu[NOSC] * A2D_USTATE;
 		s.fs.q = ramp_load(wf + FW_Q);
@@ -356,16 +376,8 @@ template<int NOSC, int FILT>
 DEV void ctl_store(const CtlVoice<NOSC, FILT> &s, int *ustate, int *vactive, int slot)
 {
 #pragma unroll
-	for(int o = 0; o < NOSC; ++o) {
-		int *w = ustate + (size_t)s.uu[o] * A2D_USTATE;
-		w[OW_MODE] = s.os[o].mode; w[OW_WAVE] = s.os[o].wave; w[OW_DPHASE] = (int)s.os[o].dphase;
-		w[OW_PHASE_LO] = (int)(unsigned)s.os[o].phase; w[OW_PHASE_HI] = (int)(unsigned)(s.os[o].phase >> 32);
-		w[OW_PRAMPING] = s.os[o].p_ramping;
-		ramp_store(w + OW_P, s.os[o].p);
-		ramp_store(w + OW_A, s.os[o].a);
-		w[OW_NOISE] = s.os[o].noise;
-		w[OW_SEED] = (int)s.os[o].seed;
-	}
+	for(int o = 0; o < NOSC; ++o)
+		oscv_store(ustate + (size_t)s.uu[o] * A2D_USTATE, s.os[o]);
 	if(FILT) {
 		int *wf = ustate + (size_t)s.uu[NOSC] * A2D_USTATE;
 		ramp_store(wf + FW_Q, s.fs.q);
@@ -421,7 +433,7 @@ DEV unsigned ctl_window(CtlVoice<NOSC, FILT> &s, const A2DWave *waves, const PTa
 	}
 	// panmix_process12's head, panmix.c:84-95
 	Ramp &vol = s.vol, &pan = s.pan;
-	if(pan.target > 0xffffff || pan.target < -0xffffff || pan.value > 0xffffff || pan.value < -0xffffff)
+	if(a2s_pan_over(pan.target) || a2s_pan_over(pan.value))
 		head |= WH_CLAMP;
 	ramp_prepare_v(vol, len);
 	ramp_prepare_v(pan, len);
@@ -446,15 +458,9 @@ DEV unsigned ctl_window(CtlVoice<NOSC, FILT> &s, const A2DWave *waves, const PTa
 		for(int o = 0; o < NOSC; ++o)
 			plain = plain && WH_MODE(head, o) == WM_TAPS && W[WE_OSC + 6 * o + WO_DA] == 0;
 		if(plain) {
-			// (win_pan's branch for volume and pan at rest, a2amd_win.hip: the same integer expressions)
-			const int v = W[WE_VOL], p = W[WE_PAN];
-			const int vp = mul64s(p, v, 24);
-			int v0 = wsub(v, vp), v1 = wadd(v, vp);
-			if(head & WH_CLAMP) {
-				const int lim = wshl(v, 1);
-				if(v0 > lim) v0 = lim;
-				if(v1 > lim) v1 = lim;
-			}
+			// (win_pan's branch for volume and pan at rest, a2amd_win.hip: the same call)
+			int v0, v1;
+			a2s_pan_gains(W[WE_VOL], W[WE_PAN], (head & WH_CLAMP) != 0, &v0, &v1);
 			W[WE_VOL] = v0;
 			W[WE_PAN] = v1;
 			head |= WH_PLAIN;

@@ -1,8 +1,10 @@
 """Every kernel's fixed point against the oracle OUTSIDE the musical range.
 
 The signal path is 8.24 in int32 and every control register a 16.16 script value shifted left by 8; the reference clamps
-none of them, it wraps.  The pan / volume gains, the amplitude product, the filter's output mix, the delay gains and the
-FM operator products are restated in every kernel of the project, and several restatements rest on range arguments
+none of them, it wraps.  The settled pan / volume gains and their clamp are stated once, in csrc/a2amd_settled.h
+(tests/test_settled_header.py holds that statement to the reference's lines), and this file pins every kernel that calls
+it; the per-frame gains, the amplitude product, the filter's output mix, the delay gains and the FM operator products are
+still restated kernel by kernel.  Several of these rest on range arguments
 (24-bit multiplies of a split gain, precomputed v0 / v1 / lim) that the other test files never leave: their gains are
 positive and of musical size.  Here the gain registers - and only those: what becomes an address (pitch, phase, wave,
 delay time, cutoff) stays where the other tests keep it - are negative, beyond +-1, at the values whose `<< 1` and
@@ -16,6 +18,7 @@ import pytest
 
 from audiality2_amd import synth
 from conftest import make_gpu, make_oracle
+from gain_cases import GAINS, ONE
 from test_gpu_bus_paths import Ramper, batch_starts, first_diff
 from test_gpu_parity import last_batch
 from test_noise_filt_quiet import FiltScene
@@ -28,24 +31,9 @@ VOL, PAN = 0, 1                                  # panmix registers
 A = 2                                            # wtosc 'a'
 Q, LP, BP, HP = 1, 2, 3, 4                       # filter12 registers
 DRY, FBG, LG, RG = 3, 4, 5, 6                    # fbdelay gain registers
-ONE = 65536                                      # 1.0 as a register value; the register's 8.24 word is value << 8
 WT = ("osc-pan", "osc2-pan", "osc-filter-pan", "osc2-filter-pan")
 N = 131                                          # two full wavefronts of voices and a partial one
 
-# (a, vol, pan) as register values, by voice number mod 11
-GAINS = [
-    (fix(-0.7), fix(-1.0), fix(1.5)),            # negative amplitude and volume, pan beyond +1
-    (fix(1.3), fix(0.8), fix(-1.7)),             # pan beyond -1 with a positive volume
-    (fix(3.0), fix(64.0), fix(0.5)),             # vol << 8 = 1 << 30: vol << 1 wraps to INT32_MIN
-    (fix(-100.0), fix(-127.5), fix(-2.5)),
-    (fix(127.9), fix(130.0), ONE - 1),           # vol << 8 wraps; pan 0xffff00: the last value below the clamp ...
-    (fix(0.9), fix(-64.0), ONE),                 # ... pan 0x1000000 exactly: clamped ...
-    (fix(-2.0), fix(100.0), ONE + 1),            # ... and 0x1000100.  (0xffffff itself has no register value.)
-    (fix(0.5), fix(-0.3), -(ONE - 1)),
-    (fix(-90.0), fix(90.0), -ONE),
-    (fix(40.0), fix(-90.0), -(ONE + 1)),
-    (fix(300.0), fix(1.0), fix(110.0)),          # a << 8 wraps
-]
 # (q, lp, bp, hp) by voice number mod 7
 FILT = [
     (0, fix(127.0), fix(-127.0), fix(77.0)),
