@@ -412,6 +412,7 @@ struct VmHost {
 	bool envlut_up = false;
 	uint32_t *d_total = nullptr, *h_total = nullptr;	// {records, faults}; pinned
 	uint32_t last_total = 0;	// records the count pass of this batch found
+	a2amd_vm_batch_info last = {};	// a2amd_last_batch_vm(): what vm_issue / vm_note_batch decided for this batch
 	A2DVmVoice *h_stage = nullptr;	// pinned staging for recalls
 	size_t h_stage_cap = 0;
 };
@@ -789,6 +790,7 @@ void vm_class_params(a2amd_ctx *c, int k, A2DVmParams *vp);	// k_vm_win's parame
 int vm_fused_done(a2amd_ctx *c);		// ... and its fault count on its way back
 int vm_predict(a2amd_ctx *c);			// k_vm_pool for the batch after this one (issue_kernels, behind the window kernels)
 bool vm_spec_wanted(a2amd_ctx *c);		// round 6: may a speculative pass follow the batch being issued?
+void vm_note_batch(a2amd_ctx *c, bool asked);	// a2amd_last_batch_vm(): was one launched behind this batch, and if not, why
 // ... and over which fragments: the span of this batch again, cut where the root's VM is expected to wake (cut_hint)
 bool vm_spec_plan(a2amd_ctx *c, int *nfrags, uint8_t *ff, uint8_t *fb);
 int vm_speculate(a2amd_ctx *c);			// ... k_vm_win for the batch after this one, into shadows (behind the leaf kernels)

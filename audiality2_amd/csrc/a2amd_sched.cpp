@@ -1657,6 +1657,7 @@ static int launch_leaves(a2amd_ctx *c, LeafPass &lp)
 		if(pend.c[pend.n].nlist)
 			++pend.n;
 		++c->stats.launches;
+		c->vm.last.quiet_launched[0] = 1;	// (a2amd_last_batch_vm)
 	}
 	// wtosc (noise) -> panmix without records: only a batch with device-seeded windows has such voices (in any other every
 	// window of a noise oscillator carries its R_NOISESEED record).  A wavefront keeps its voices for the whole batch - no
@@ -1706,6 +1707,7 @@ static int launch_leaves(a2amd_ctx *c, LeafPass &lp)
 		if(pend.c[pend.n].nlist)
 			++pend.n;
 		++c->stats.launches;
+		c->vm.last.quiet_launched[1] = 1;	// (a2amd_last_batch_vm)
 	}
 	const ListRange oscfilt = c->leaf[LEAF_OSCFILTPAN];
 	if(oscfilt.count && none_quiet(2, oscfilt.count))
@@ -1720,6 +1722,7 @@ static int launch_leaves(a2amd_ctx *c, LeafPass &lp)
 		if(a2d_launch_leaf_oscfiltpan(c->d_params, c->hparams, list + oscfilt.first, nf, vpw, c->stream))
 			return c->fail(A2AMD_EHIP, "filter leaf launch failed: %s", hipGetErrorString(hipGetLastError()));
 		++c->stats.launches;
+		c->vm.last.quiet_launched[2] = 1;	// (a2amd_last_batch_vm)
 	}
 	const ListRange o2f = c->leaf[LEAF_OSC2FILTPAN];
 	if(o2f.count && c->o2f_quiet) {
@@ -1915,6 +1918,7 @@ static int issue_leaf_phase(a2amd_ctx *c, bool consume, bool consume_sub, hipEve
 		if(int r = vm_speculate(c))
 			return r;
 	}
+	vm_note_batch(c, use_win && vmwin_ok);
 	return 0;
 }
 

@@ -888,6 +888,23 @@ static int vm_spec_why_not(a2amd_ctx *c, int *nfrags, uint8_t *ff, uint8_t *fb)
 	return words <= budget ? 0 : 3;
 }
 
+// a2amd_last_batch_vm(): behind the batch's leaf phase - was a pass for the batch expected next launched, and if not,
+// why (asked: the window kernels and k_vm_win are in use; the callers of vm_speculate look before they call)
+void vm_note_batch(a2amd_ctx *c, bool asked)
+{
+	VmHost &m = c->vm;
+	if(m.list.empty())
+		return;
+	if(m.spec_launched_now && m.spec_valid) {
+		m.last.spec_next = 1;
+		return;
+	}
+	int n;
+	uint8_t ff[A2D_MAXBATCH], fb[A2D_MAXBATCH];
+	const int why = asked ? vm_spec_why_not(c, &n, ff, fb) : 1;
+	m.last.spec_why_not = (uint32_t)(why ? why : 1);
+}
+
 bool vm_spec_wanted(a2amd_ctx *c)
 {
 	int n;
@@ -1052,6 +1069,18 @@ int vm_issue(a2amd_ctx *c, bool fused)
 	m.spec_use = false;
 	m.spec_launched_now = false;
 	m.spec_go_pending = false;
+	// (a2amd_last_batch_vm: the lists as they stand, what was valid when the batch came, the decisions below)
+	m.last = a2amd_vm_batch_info{};
+	m.last.pending = (uint32_t)m.n_fresh;
+	m.last.listed = (uint32_t)m.list.size();
+	if(!m.list.empty()) {
+		for(int k = 0; k < 3; ++k)
+			m.last.class_voices[k] = (uint32_t)m.n_cls[k];
+		m.last.other_voices = (uint32_t)m.n_other;
+		m.last.spec_valid = m.spec_valid;
+		if(m.n_cls[0] + m.n_cls[1] + m.n_cls[2] > 0 && !fused)
+			m.last.not_fused = A2AMD_VM_NOT_ASKED;
+	}
 	// (the faults of the last fused batch are looked at whether or not a voice is left: all of them may have been
 	// recalled since)
 	if(m.total_pending) {
@@ -1095,8 +1124,11 @@ int vm_issue(a2amd_ctx *c, bool fused)
 				why = 4;
 		}
 		++m.pred_why[why];
-		if(why && m.spec_valid)
+		m.last.not_fused = (uint32_t)why;
+		if(why && m.spec_valid) {
 			++m.spec_miss[0];
+			m.last.spec_miss = 1;
+		}
 		if(c->sw.hosttiming_level >= 2 && why >= 4)
 			fprintf(stderr, "a2amd device VM: batch of %d fragments not fused: %s (predicted: %u frames)\n", c->nfrags,
 					why == 4 ? "another length" : "a fragment across a 64-frame boundary", m.pred_span);
@@ -1122,10 +1154,19 @@ int vm_issue(a2amd_ctx *c, bool fused)
 					for(int k = 0; k < 3; ++k)
 						m.spec_idle[k] = m.h_spec[4 + k];
 				}
-				else
+				else {
 					++m.spec_miss[!exact ? 1 : m.h_spec[1] ? 2 : 3];
+					m.last.spec_miss = !exact ? 2 : m.h_spec[1] ? 3 : 4;
+				}
 			}
 		}
+	}
+	m.last.fused = m.fused;
+	m.last.spec_taken = m.spec_use;
+	if(m.spec_use) {
+		m.last.idle_known = 1;
+		for(int k = 0; k < 3; ++k)
+			m.last.idle[k] = m.spec_idle[k];
 	}
 	m.pred_valid = m.spec_valid = false;
 	if(m.fused) {
@@ -1151,6 +1192,7 @@ int vm_issue(a2amd_ctx *c, bool fused)
 	HIPCHK(c, hipStreamSynchronize(c->stream));
 	const uint32_t total = m.h_total[0];
 	m.last_total = total;
+	m.last.records = total;
 	if(m.h_total[1])
 		return c->fail(A2AMD_ESTATE, "device VM: %u voice(s) faulted (the analysis let a program through that it should "
 				"not have)", m.h_total[1]);
@@ -1760,6 +1802,14 @@ static int trace_impl(const uint32_t *code, unsigned nwords, a2amd_vm_state *st,
 	const int n = std::min(e.n, (int)cap);
 	memcpy(recs, buf.data(), (size_t)n * sizeof(A2DRec));
 	return e.n;
+}
+
+int a2amd_last_batch_vm(const a2amd_ctx *c, a2amd_vm_batch_info *out)
+{
+	if(!c || !out)
+		return A2AMD_EINVAL;
+	*out = c->vm.last;
+	return A2AMD_OK;
 }
 
 int a2amd_vm_get_stats(a2amd_ctx *c, a2amd_vm_stats *out)

@@ -126,6 +126,25 @@ class a2amd_bare_batch_info(C.Structure):
         return "bare_batch_info(" + ", ".join(f"{n}={getattr(self, n)}" for n, _ in self._fields_) + ")"
 
 
+class a2amd_vm_batch_info(C.Structure):
+    """include/a2amd_vmbatch.h: who ran the device VM's voices of the most recent batch"""
+    _fields_ = [("listed", C.c_uint32), ("class_voices", C.c_uint32 * 3), ("other_voices", C.c_uint32),
+                ("pending", C.c_uint32), ("fused", C.c_uint32), ("not_fused", C.c_uint32),
+                ("spec_valid", C.c_uint32), ("spec_taken", C.c_uint32), ("spec_miss", C.c_uint32),
+                ("spec_next", C.c_uint32), ("spec_why_not", C.c_uint32), ("records", C.c_uint32),
+                ("idle_known", C.c_uint32), ("idle", C.c_uint32 * 3), ("quiet_launched", C.c_uint32 * 3)]
+
+    def __repr__(self):
+        return ("vm_batch_info(" + ", ".join(f"{n}={list(getattr(self, n)) if n in ('class_voices', 'idle', 'quiet_launched') else getattr(self, n)}"
+                                             for n, _ in self._fields_) + ")")
+
+
+class a2amd_vm_state(C.Structure):
+    """include/a2amd_vm.h: A2_vmstate, field for field"""
+    _fields_ = [("waketime", C.c_uint32), ("state", C.c_uint8), ("func", C.c_uint8), ("pc", C.c_uint16),
+                ("r", C.c_int32 * 64)]
+
+
 class Backend:
     """Thin ctypes veneer over one implementation of the call protocol."""
 
@@ -184,6 +203,18 @@ class Backend:
         self._last_batch_bare = None
         if hasattr(lib, prefix + "last_batch_bare"):
             self._last_batch_bare = fn("last_batch_bare", i32, vp, C.POINTER(a2amd_bare_batch_info))
+        # the device VM (the product library only; include/a2amd_vm.h)
+        self.has_vm = hasattr(lib, prefix + "vm_adopt")
+        if self.has_vm:
+            self._fragment_offset = fn("fragment_offset", i32, vp, u32)
+            self._vm_program = fn("vm_program", i32, vp, u64, C.POINTER(C.c_uint32), u32)
+            self._vm_adopt = fn("vm_adopt", i32, vp, i32, i32, C.POINTER(a2amd_vm_state), C.POINTER(C.c_int32),
+                                C.POINTER(C.c_uint8), C.c_uint32, C.c_uint32, vp, i32)
+            self._vm_expect_cuts = fn("vm_expect_cuts", i32, vp, C.POINTER(C.c_uint32), i32)
+            self._vm_recall = fn("vm_recall", i32, vp, C.POINTER(C.c_int32), u32, C.POINTER(a2amd_vm_state), vp)
+        self._last_batch_vm = None
+        if hasattr(lib, prefix + "last_batch_vm"):
+            self._last_batch_vm = fn("last_batch_vm", i32, vp, C.POINTER(a2amd_vm_batch_info))
         # waves built on the device from what it rendered (the product library only)
         self.has_capture = hasattr(lib, prefix + "wave_upload_captured_post")
         if self.has_capture:
@@ -330,6 +361,51 @@ class Backend:
         bi = a2amd_bare_batch_info()
         self._chk(self._last_batch_bare(self.ctx, C.byref(bi)), "last_batch_bare")
         return bi
+
+    def last_batch_vm(self):
+        """a2amd_last_batch_vm: the device VM's voices of the most recent batch by class, whether their VMs ran fused
+        (k_vm_win, or a speculative pass taken: k_vm_commit) or through records (k_vm_count / k_vm_emit) and why, and
+        whether a pass for the next batch was launched behind it"""
+        if self._last_batch_vm is None:
+            raise RuntimeError(f"this library has no {self.prefix}last_batch_vm")
+        bi = a2amd_vm_batch_info()
+        self._chk(self._last_batch_vm(self.ctx, C.byref(bi)), "last_batch_vm")
+        return bi
+
+    def fragment_offset(self, offset):
+        """the open fragment begins `offset` frames inside the engine's own 64-frame fragment (a2amd_fragment_offset)"""
+        return self._chk(self._fragment_offset(self.ctx, offset), "fragment_offset")
+
+    def vm_program(self, key, words):
+        """a2amd_vm_program: the text of one function (32 bit words); the program id"""
+        code = (C.c_uint32 * len(words))(*[w & 0xffffffff for w in words])
+        return self._chk(self._vm_program(self.ctx, key, code, len(words)), "vm_program")
+
+    def vm_adopt(self, head_unit, prog, state, wires, now, msdur, check=True):
+        """a2amd_vm_adopt without env units.  state: a2amd_vm_state; wires: {VM register: (backend unit, its register)}.
+        check=False: the return code as it is (a refusal is an answer)."""
+        wu = (C.c_int32 * 64)(*([-1] * 64))
+        wr = (C.c_uint8 * 64)()
+        for r, (u, ureg) in wires.items():
+            wu[r], wr[r] = u, ureg
+        rc = self._vm_adopt(self.ctx, head_unit, prog, C.byref(state), wu, wr, now & 0xffffffff, msdur, None, 0)
+        return self._chk(rc, "vm_adopt") if check else rc
+
+    def vm_expect_cuts(self, when):
+        """a2amd_vm_expect_cuts: engine times (24:8) at which the root's VM wakes next; [] forgets them"""
+        arr = (C.c_uint32 * max(len(when), 1))(*[w & 0xffffffff for w in when])
+        return self._chk(self._vm_expect_cuts(self.ctx, arr, len(when)), "vm_expect_cuts")
+
+    def vm_recall(self, head_units):
+        """a2amd_vm_recall: the voices go back to the host; their a2amd_vm_state as of the start of the open fragment"""
+        n = len(head_units)
+        out = (a2amd_vm_state * n)()
+        self._chk(self._vm_recall(self.ctx, (C.c_int32 * n)(*head_units), n, out, None), "vm_recall")
+        return list(out)
+
+    def last_error(self):
+        msg = self._err(self.ctx)
+        return msg.decode(errors="replace") if msg else ""
 
     def unit_init(self, voice_key, kind, flags, nin, nout, wired, transpose=0, wakefrac=0):
         return self._chk(self._unit_init(self.ctx, voice_key, kind, flags, nin, nout, wired,

@@ -35,6 +35,9 @@ def test_library_exports_every_declared_symbol(gpu_lib):
     # who rendered the bus owners (tests/test_gpu_bus_paths.py)
     assert declared_symbols("a2amd_bus.h") == ["a2amd_last_batch_buses"]
     assert hasattr(gpu_lib, "a2amd_last_batch_buses")
+    # who ran the device VM's voices (tests/test_gpu_vm_direct.py)
+    assert declared_symbols("a2amd_vmbatch.h") == ["a2amd_last_batch_vm"]
+    assert hasattr(gpu_lib, "a2amd_last_batch_vm")
 
 
 def test_walk_and_units_libraries_export_their_interface():

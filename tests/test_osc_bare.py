@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 from audiality2_amd import synth
-from audiality2_amd.replay import Trace, replay
+from audiality2_amd.replay import Trace, a2amd_vm_state, replay
 from conftest import GOLDEN, ROOT, fnv1a_fragments, make_gpu, make_oracle
 from test_gpu_parity import first_diff, is_gpu, last_batch
 
@@ -510,25 +510,15 @@ def test_a_voice_the_device_vm_runs_is_not_of_the_class(oracle_lib, monkeypatch)
 
     # the GPU
     be = make_gpu(max_batch=4)
-    L = be.lib
-    L.a2amd_vm_program.restype = ctypes.c_int
-    L.a2amd_vm_program.argtypes = [ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint32), ctypes.c_uint]
-    L.a2amd_vm_adopt.restype = ctypes.c_int
-    L.a2amd_vm_adopt.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(VmState), ctypes.POINTER(ctypes.c_int32),
-                                 ctypes.POINTER(ctypes.c_uint8), ctypes.c_uint32, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_int]
     sc, m, x = scene(be)
     got, infos = [], []
     walk1(be, sc, m, lambda: be.unit_process(x, 0, 64))
     got.append(be.render(64))
     infos.append(be.last_batch_bare())
     walk1(be, sc, m, lambda: be.unit_process(x, 0, 64))
-    prog = L.a2amd_vm_program(be.ctx, 0x5150, code, n)
+    prog = be.vm_program(0x5150, list(code))
     assert prog >= 0
-    wu = (ctypes.c_int32 * 64)(*([-1] * 64))
-    wr = (ctypes.c_uint8 * 64)()
-    wu[5], wr[5] = x, 1
-    st = state()
-    adopted = L.a2amd_vm_adopt(be.ctx, x, prog, ctypes.byref(st), wu, wr, 64 << 8, MSDUR, None, 0)
+    adopted = be.vm_adopt(x, prog, a2amd_vm_state.from_buffer_copy(state()), {5: (x, 1)}, 64 << 8, MSDUR, check=False)
     print("a2amd_vm_adopt:", adopted)
     if adopted != 0:
         assert adopted == -4, adopted                   # A2AMD_EUNSUPPORTED: the chain stays the engine's
