@@ -369,6 +369,8 @@ int a2d_launch_bus_driver(const A2DParams *dparams, const int *dlist, int nlist,
 int a2d_launch_commit(const A2DParams &hp, const A2DCommit &cm, void *stream);
 // quiet "inline; fbdelay 2->2 ... ; fbdelay 2->2 >" voices (one workgroup each)
 int a2d_launch_bus_fbdchain(const A2DParams *dparams, const int *dlist, int nlist, int consume, void *stream);
+// k_bus_fbdpan: the same rounds with a panmix 2->2, wired and adding, behind the last delay (none of them wired)
+int a2d_launch_bus_fbdpan(const A2DParams *dparams, const int *dlist, int nlist, int consume, void *stream);
 int a2d_launch_park(int32_t *stage, int32_t *bus, unsigned words, void *stream);
 int a2d_launch_add_bus(int32_t *dst, int32_t *src, unsigned words, void *stream);
 // bus[f][ch][64] (nch channels per fragment) += inj[f][ch][64] (8 channels per fragment), ch < n

@@ -2935,6 +2935,173 @@ int a2d_launch_bus_fbdchain(const A2DParams *dparams, const int *dlist, int nlis
 	return (int)hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------
+// inline -> fbdelay 2->2 [-> fbdelay 2->2 ...] -> panmix 2->2 (wired, adding): the master section of most
+// songs, `struct { inline 0 *; fbdelay * *; panmix * > }` (k2intro.a2s, fmtest3.a2s)
+// ---------------------------------------------------------------------------
+// k_bus_fbdchain's rounds with no delay wired and panmix_process22 behind the last one: pointwise per frame, its two
+// rampers linear in time.  Volume and pan at rest: two gains, computed once.  Otherwise - the voice begins the batch
+// with a timer, a delta or value != target - thread 0 steps both rampers through the batch's fragments first, as
+// k_bus_driver's one-workgroup launch does, and stores their end state; this workgroup owns the voice for the whole
+// batch, so nobody else decides by the words it stores.
+// (A body shared with k_bus_fbdchain as a template on the tail was tried first: it moved that kernel's code - 676
+// instructions became 768, profiles/fbdpan.md - so the two stand side by side.)
+__global__ __launch_bounds__(FBC_THREADS)
+void k_bus_fbdpan(const A2DParams *__restrict__ pp, const int *__restrict__ list, int nlist, int consume)
+{
+	__shared__ int fr[A2D_MAXBATCH][5];	// per fragment: vol, dvol, pan, dpan, clamp (at rest: row 0 alone)
+	__shared__ int at_rest;
+	const A2DParams &p = *pp;
+	const int slot = list[blockIdx.x];
+	if(p.runs[slot].count)
+		return;		// carries records this batch: the general kernel renders it
+	if(!p.vactive[slot])
+		return;
+	const A2DVoice &vc = p.voices[slot];
+	const int nd = vc.nunits - 2;
+	const int M = A2D_FBD_BUFSIZE - 1;
+	const int nfrags = p.nfrags;
+	// (one thread reads the rampers and decides for all: the words it may store are the ones the decision is made by)
+	if(threadIdx.x == 0) {
+		int *w = p.ustate + (size_t)vc.unit[nd + 1] * A2D_USTATE;
+		Ramp vol = ramp_load(w + PW_VOL), pan = ramp_load(w + PW_PAN);
+		const bool settled = !(vol.timer | vol.delta | pan.timer | pan.delta) &&
+				vol.value == vol.target && pan.value == pan.target;
+		at_rest = settled;
+		if(settled) {
+			fr[0][0] = vol.value; fr[0][1] = 0;
+			fr[0][2] = pan.value; fr[0][3] = 0;
+			fr[0][4] = a2s_pan_over(pan.value);
+		} else {
+			// panmix_process22's rampers (panmix.c:192-249)
+			for(int f = 0; f < nfrags; ++f) {
+				const int n = p.fragframes[f];
+				fr[f][4] = a2s_pan_over(pan.target) || a2s_pan_over(pan.value);
+				ramp_prepare(vol, n);
+				ramp_prepare(pan, n);
+				fr[f][0] = vol.value; fr[f][1] = vol.delta;
+				fr[f][2] = pan.value; fr[f][3] = pan.delta;
+				ramp_run(vol, n);
+				ramp_run(pan, n);
+			}
+			ramp_store(w + PW_VOL, vol);
+			ramp_store(w + PW_PAN, pan);
+		}
+	}
+	FbdU d[FBC_MAXD];
+	int dmin = A2D_FBD_BUFSIZE, dmax = 0;
+#pragma unroll
+	for(int k = 0; k < FBC_MAXD; ++k)
+		if(k < nd) {
+			// (the same words for every thread: kept as wave-uniform ones, and d[] indexed by constants only - the
+			// chain's parameters stay in registers, where k_bus_fbdchain keeps its array in 240 bytes of scratch)
+			const int *w = p.ustate + (size_t)vc.unit[k + 1] * A2D_USTATE;
+			d[k].fb = rfl(w[DW_FBDELAY]); d[k].l = rfl(w[DW_LDELAY]); d[k].r = rfl(w[DW_RDELAY]);
+			d[k].dry = rfl(w[DW_DRYGAIN]); d[k].fbg = rfl(w[DW_FBGAIN]); d[k].lg = rfl(w[DW_LGAIN]); d[k].rg = rfl(w[DW_RGAIN]);
+			d[k].pos = rfl(w[DW_BUFPOS]);
+			d[k].b0 = p.fbdmem + (size_t)rfl(w[DW_BUFIDX]) * 2 * A2D_FBD_BUFSIZE;
+			d[k].b1 = d[k].b0 + A2D_FBD_BUFSIZE;
+			d[k].add = rfl((int)A2D_ADD(p.udesc[vc.unit[k + 1]]));
+			dmin = min(dmin, min(d[k].fb, min(d[k].l, d[k].r)));
+			dmax = max(dmax, max(d[k].fb, max(d[k].l, d[k].r)));
+		}
+	__syncthreads();
+	const bool rest = at_rest != 0;
+	int rv0 = 0, rv1 = 0;
+	if(rest) {
+		const int vk = fr[0][0], vp = mul64s(fr[0][2], vk, 24);
+		rv0 = wsub(vk, vp); rv1 = wadd(vk, vp);
+		if(fr[0][4]) {
+			const int lim = wshl(vk, 1);
+			if(rv0 > lim) rv0 = lim;
+			if(rv1 > lim) rv1 = lim;
+		}
+	}
+	// fragments per round (the host only lists voices whose taps allow >= 1)
+	const int rf = max(1, min(dmin, A2D_FBD_BUFSIZE - dmax) / A2D_FRAG);
+	int *own = p.busmem + vc.own_off;
+	int *out = p.busmem + vc.out_off;
+	const int out_nch = vc.out_nch;
+	for(int f0 = 0; f0 < nfrags; f0 += rf) {
+		const int fend = min(nfrags, f0 + rf);
+		for(int idx = f0 * A2D_FRAG + (int)threadIdx.x; idx < fend * A2D_FRAG; idx += FBC_THREADS) {
+			const int f = idx >> 6, lane = idx & 63;
+			if(lane >= p.fragframes[f])
+				continue;
+			const int t = (int)p.fragstart[f] + lane;
+			int *src = own + (size_t)f * 2 * A2D_FRAG;
+			int x0 = src[lane], x1 = src[A2D_FRAG + lane];
+			if(consume) {
+				// every bus of this batch is read by its owner's fast kernel and
+				// nowhere else: leave it zeroed for the next batch
+				src[lane] = 0;
+				src[A2D_FRAG + lane] = 0;
+			}
+#pragma unroll
+			for(int k = 0; k < FBC_MAXD; ++k)
+				if(k < nd) {
+					const FbdU &u = d[k];
+					const int pos = wadd(u.pos, t);
+					int o0 = mul64s(u.b1[(pos - u.fb) & M], u.fbg, 16);
+					int o1 = mul64s(u.b0[(pos - u.fb) & M], u.fbg, 16);
+					const int t0 = u.b0[(pos - u.l) & M], t1 = u.b1[(pos - u.r) & M];
+					u.b0[pos & M] = wadd(x0, o0);
+					u.b1[pos & M] = wadd(x1, o1);
+					o0 = wadd(o0, mul64s(t0, u.lg, 16));
+					o1 = wadd(o1, mul64s(t1, u.rg, 16));
+					o0 = wadd(o0, mul64s(x0, u.dry, 16));
+					o1 = wadd(o1, mul64s(x1, u.dry, 16));
+					if(u.add) {
+						x0 = wadd(x0, o0);
+						x1 = wadd(x1, o1);
+					} else {
+						x0 = o0;
+						x1 = o1;
+					}
+				}
+			// panmix_process22 on what the last delay left (panmix.c:191-229), adding into the output bus
+			int v0 = rv0, v1 = rv1;
+			if(!rest) {
+				const int vk = wadd(fr[f][0], wmul(fr[f][1], lane));
+				const int pk = wadd(fr[f][2], wmul(fr[f][3], lane));
+				const int vp = mul64s(pk, vk, 24);
+				v0 = wsub(vk, vp); v1 = wadd(vk, vp);
+				if(fr[f][4]) {
+					const int lim = wshl(vk, 1);
+					if(v0 > lim) v0 = lim;
+					if(v1 > lim) v1 = lim;
+				}
+			}
+			const int o0 = mul64s(x0, v0, 24), o1 = mul64s(x1, v1, 24);
+			int *dst = out + (size_t)f * out_nch * A2D_FRAG;
+			if(o0)
+				atomicAdd(&dst[lane], o0);
+			if(o1)
+				atomicAdd(&dst[A2D_FRAG + lane], o1);
+		}
+		if(fend < nfrags)
+			__syncthreads();	// (delay-line stores of this round visible to the next)
+	}
+	if(threadIdx.x == 0) {
+		int total = 0;
+		for(int f = 0; f < nfrags; ++f)
+			total += p.fragframes[f];
+#pragma unroll
+		for(int k = 0; k < FBC_MAXD; ++k)
+			if(k < nd)
+				p.ustate[(size_t)vc.unit[k + 1] * A2D_USTATE + DW_BUFPOS] = wadd(d[k].pos, total);
+	}
+}
+
+int a2d_launch_bus_fbdpan(const A2DParams *dparams, const int *dlist, int nlist, int consume, void *stream)
+{
+	if(nlist <= 0)
+		return 0;
+	hipLaunchKernelGGL(k_bus_fbdpan, dim3(nlist), dim3(FBC_THREADS), 0, (hipStream_t)stream,
+			dparams, dlist, nlist, consume);
+	return (int)hipGetLastError();
+}
+
 int a2d_launch_leaf_oscpan(const A2DParams *dparams, const A2DParams &hp, const int *dlist, int nlist,
 		int vpw, int ysplit, int *ustage, unsigned char *staged, void *stream, void *event_after_main, A2DCommit *defer)
 {

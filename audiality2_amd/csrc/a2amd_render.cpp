@@ -494,6 +494,14 @@ int a2amd_last_batch_bare(const a2amd_ctx *c, a2amd_bare_batch_info *out)
 	return A2AMD_OK;
 }
 
+int a2amd_last_batch_fbdpan(const a2amd_ctx *c, a2amd_fbdpan_batch_info *out)
+{
+	if(!c || !out)
+		return A2AMD_EINVAL;
+	*out = c->last_fbdpan;
+	return A2AMD_OK;
+}
+
 int a2amd_set_profiling(a2amd_ctx *c, int on)
 {
 	if(int r = drain_events(c))

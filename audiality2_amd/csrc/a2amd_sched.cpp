@@ -307,26 +307,55 @@ bool is_driver_chain(const a2amd_ctx *c, const HVoice &v)
 // a tap the frame-parallel delay kernel can take: at least one fragment long, and
 // short enough not to wrap onto the frames being written
 
-// inline 0 2; fbdelay 2 2 [; fbdelay 2 2 ...]; the last one wired and adding
-// (the group voices of benchmark/fmtest4.a2s:83-95), every tap >= one fragment
-bool is_fbdchain(const a2amd_ctx *c, const HVoice &v)
+// what the two delay-chain classes share: a stereo inline in front, then nd = 1 .. 4 two-channel fbdelay units at chain
+// positions 1 .. nd, every tap of each at least one fragment long and at most the delay line less one.  Wiring and
+// adding mode are the callers' to test.
+static bool fbd_units_ok(const a2amd_ctx *c, const HVoice &v, int nd)
 {
-	if(v.nunits < 2 || v.nunits > 5 || v.own_nch != 2 || v.out_nch < 2 || v.own_off < 0 || v.inline_pos != 0)
+	if(nd < 1 || nd > 4 || v.own_nch != 2 || v.out_nch < 2 || v.own_off < 0 || v.inline_pos != 0)
 		return false;
 	const HUnit &il = c->units[v.unit[0]];
 	if(il.kind != A2AMD_INLINE || (il.flags & A2AMD_PROCADD) || il.wired || il.nout != 2)
 		return false;
-	for(int k = 1; k < v.nunits; ++k) {
+	for(int k = 1; k <= nd; ++k) {
 		const HUnit &d = c->units[v.unit[k]];
-		const bool last = k == v.nunits - 1;
-		if(d.kind != A2AMD_FBDELAY || d.nin != 2 || d.nout != 2 || (d.wired != 0) != last ||
-				(last && !(d.flags & A2AMD_PROCADD)))
+		if(d.kind != A2AMD_FBDELAY || d.nin != 2 || d.nout != 2)
 			return false;
 		for(int t = 0; t < 3; ++t)
 			if(!fbd_tap_ok(d.fbd_taps[t]))
 				return false;
 	}
 	return true;
+}
+
+// inline 0 2; fbdelay 2 2 [; fbdelay 2 2 ...]; the last one wired and adding
+// (the group voices of benchmark/fmtest4.a2s:83-95), every tap >= one fragment
+bool is_fbdchain(const a2amd_ctx *c, const HVoice &v)
+{
+	const int nd = v.nunits - 1;
+	if(!fbd_units_ok(c, v, nd))
+		return false;
+	for(int k = 1; k <= nd; ++k) {
+		const HUnit &d = c->units[v.unit[k]];
+		const bool last = k == nd;
+		if((d.wired != 0) != last || (last && !(d.flags & A2AMD_PROCADD)))
+			return false;
+	}
+	return true;
+}
+
+// inline 0 2; fbdelay 2 2 [; fbdelay 2 2 ...]; panmix 2 2 wired and adding - no delay wired, any of them adding or not:
+// the master section of most songs (k2intro.a2s, fmtest3.a2s: `struct { inline 0 *; fbdelay * *; panmix * > }`)
+bool is_fbdpan_chain(const a2amd_ctx *c, const HVoice &v)
+{
+	const int nd = v.nunits - 2;
+	if(!fbd_units_ok(c, v, nd))
+		return false;
+	for(int k = 1; k <= nd; ++k)
+		if(c->units[v.unit[k]].wired)
+			return false;
+	const HUnit &pm = c->units[v.unit[nd + 1]];
+	return pm.kind == A2AMD_PANMIX && pm.nin == 2 && pm.nout == 2 && pm.wired && (pm.flags & A2AMD_PROCADD);
 }
 
 // append a launch list to list_all / to the batch's exceptions; the range it takes there
@@ -354,6 +383,7 @@ int upload(a2amd_ctx *c)
 	// (a2amd_last_batch_buses(): the lists of a quiet batch are the last upload's - nobody ramps, nothing is dropped)
 	c->n_bus_windows_dropped = 0;
 	c->last_bus.driver_ramping = c->last_bus.driver_windows_dropped = 0;
+	c->last_fbdpan.gliding_voices = 0;
 	if(c->sw.hosttiming) {
 		// (A2AMD_HOSTTIMING: why a batch did not take the quiet path - first reason that applies)
 		const int why = !c->blob_quiet ? 0 : !c->with_recs.empty() ? 1 : !c->prev_with_recs.empty() ? 2 :
@@ -737,7 +767,7 @@ int upload(a2amd_ctx *c)
 		bool owners_ok = !c->sw.no_selfclean, root_driver = false;
 		std::vector<int> leaf[LEAF_N];
 		std::map<int, std::pair<std::vector<int>, std::vector<int>>> bydepth;
-		std::map<int, std::vector<int>> fbd_bydepth;
+		std::map<int, std::vector<int>> fbd_bydepth, fbdpan_bydepth;
 		int maxdepth = -1;
 		for(size_t vi = 0; vi < nv; ++vi) {
 			HVoice &v = c->voices[vi];
@@ -757,13 +787,16 @@ int upload(a2amd_ctx *c)
 				auto &d = bydepth[v.depth];
 				if(classify)
 					v.cls = !(c->sw.no_fast & 4) && is_driver_chain(c, v) ? CLS_BUSDRIVER :
-							!(c->sw.no_fast & 32) && v.depth > 0 && is_fbdchain(c, v) ? CLS_FBDCHAIN : CLS_BUSGENERIC;
+							!(c->sw.no_fast & 32) && v.depth > 0 && is_fbdchain(c, v) ? CLS_FBDCHAIN :
+							// (a root of this shape stays general: the master bus is the root driver's to store)
+							!(c->sw.no_fast & 512) && v.depth > 0 && is_fbdpan_chain(c, v) ? CLS_FBDPAN : CLS_BUSGENERIC;
 				// (the master bus at offset 0 is the root's alone)
 				if(v.cls == CLS_BUSGENERIC || (v.out_off == 0) != (v.depth == 0))
 					owners_ok = false;
 				else if(v.depth == 0)
 					root_driver = true;
-				(v.cls == CLS_BUSDRIVER ? d.first : v.cls == CLS_FBDCHAIN ? fbd_bydepth[v.depth] : d.second).push_back((int)vi);
+				(v.cls == CLS_BUSDRIVER ? d.first : v.cls == CLS_FBDCHAIN ? fbd_bydepth[v.depth] :
+						v.cls == CLS_FBDPAN ? fbdpan_bydepth[v.depth] : d.second).push_back((int)vi);
 				maxdepth = std::max(maxdepth, v.depth);
 			} else {
 				if(classify)
@@ -814,6 +847,7 @@ int upload(a2amd_ctx *c)
 			DepthRange &r = c->depth_ranges[d];
 			r.driver = append_range(c->list_all, bydepth[d].first);
 			r.fbd = append_range(c->list_all, fbd_bydepth[d]);
+			r.fbdpan = append_range(c->list_all, fbdpan_bydepth[d]);
 			r.generic = append_range(c->list_all, bydepth[d].second);
 		}
 		if(int r = grow(c, c->d_list, c->list_all.size() + 64, 1, false)) return r;
@@ -859,7 +893,7 @@ int upload(a2amd_ctx *c)
 				// (a bare wtosc with records - or the stand-in run of a noise oscillator in a device-seeded stretch: the general
 				// kernel's, which renders the voices on its exception list; k_leaf_oscbare skips a voice that has a run)
 				dyn[DYN_REST].push_back(vi);
-			} else if((v.cls == CLS_BUSDRIVER || v.cls == CLS_FBDCHAIN) && v.depth < (int)dyn_bus.size()) {
+			} else if((v.cls == CLS_BUSDRIVER || v.cls == CLS_FBDCHAIN || v.cls == CLS_FBDPAN) && v.depth < (int)dyn_bus.size()) {
 				dyn_bus[v.depth].push_back(vi);
 				if(c->sw.hosttiming_level >= 3 && !v.recs.empty())
 					fprintf(stderr, "a2amd: bus voice %d (depth %d, class %d) carries %zu records, first: frag %u op %u unit %u reg %u value %d\n",
@@ -910,8 +944,9 @@ int upload(a2amd_ctx *c)
 			if(!dyn_bus[d].empty())
 				c->consume_ok = false;	// a bus owner carries records: the general kernel renders it
 		}
-		// a2amd_last_batch_buses(): the bus owners by the kernel that renders them this batch.  k_bus_driver and
-		// k_bus_fbdchain leave a listed voice whose run is not empty to the general kernel (the depth's exception list).
+		// a2amd_last_batch_buses(): the bus owners by the kernel that renders them this batch.  k_bus_driver,
+		// k_bus_fbdchain and k_bus_fbdpan leave a listed voice whose run is not empty to the general kernel (the depth's
+		// exception list).
 		a2amd_bus_info &bi = c->last_bus;
 		bi = a2amd_bus_info{};
 		bi.driver_windows_dropped = c->n_bus_windows_dropped;
@@ -940,6 +975,24 @@ int upload(a2amd_ctx *c)
 				bi.fbd_voices += c->voices[c->list_all[r.fbd.first + k]].recs.empty();
 			bi.generic_voices += (uint32_t)(r.generic.count + r.dyn.count);
 		}
+		// a2amd_last_batch_fbdpan(): the pan-tailed delay chains by who renders them this batch.  One with records stands on
+		// its depth's exception list above; the others are k_bus_fbdpan's, those whose volume or pan may not be at rest by
+		// the host's bound (moving_until, as for the drivers) included: the class has no list of its own for them, the
+		// voice's one workgroup steps the rampers itself.
+		a2amd_fbdpan_batch_info &fp = c->last_fbdpan;
+		fp = a2amd_fbdpan_batch_info{};
+		for(const DepthRange &r : c->depth_ranges)
+			for(int k = 0; k < r.fbdpan.count; ++k) {
+				const HVoice &v = c->voices[c->list_all[r.fbdpan.first + k]];
+				++fp.class_voices;
+				fp.max_delays = std::max(fp.max_delays, (uint32_t)(v.nunits - 2));
+				if(!v.recs.empty()) {
+					++fp.record_voices;
+					continue;
+				}
+				++fp.quiet_voices;
+				fp.gliding_voices += v.moving_until > c->vm.batch_time;
+			}
 		// a2amd_last_batch_bare(): the bare wtosc voices by who renders them this batch.  One with a run - records of its
 		// own, or the stand-in run of a noise oscillator in a device-seeded stretch - stands on the general kernel's list
 		// above; the others are k_leaf_oscbare's, those still gliding by the host's bound (moving_until) included: the class
@@ -1109,7 +1162,7 @@ int launch_depth(a2amd_ctx *c, int d, int consume, A2DCommitSet *pend)	// consum
 		// (the root, a plain driver chain that stores the master bus: into the host's buffer where asked)
 		// (... and only if nothing else adds into the master bus at depth 0: no voice with records there this
 		// batch, no leaf voice mixing straight into it - owners_all_driver says so for the static lists)
-		const bool direct = d == 0 && (consume & 2) && c->master_dst && r.driver.count == 1 && !r.generic.count && !r.fbd.count &&
+		const bool direct = d == 0 && (consume & 2) && c->master_dst && r.driver.count == 1 && !r.generic.count && !r.fbd.count && !r.fbdpan.count &&
 				!r.dyn.count && c->owners_all_driver && !c->capture.on;	// (a capture reads the bus memory)
 		if(direct)
 			c->master_direct = true;
@@ -1129,6 +1182,12 @@ int launch_depth(a2amd_ctx *c, int d, int consume, A2DCommitSet *pend)	// consum
 	if(r.fbd.count) {
 		if(a2d_launch_bus_fbdchain(c->d_params, c->d_list.d + r.fbd.first, r.fbd.count, consume & 1, c->stream))
 			return c->fail(A2AMD_EHIP, "delay chain launch failed: %s", hipGetErrorString(hipGetLastError()));
+		++c->stats.launches;
+	}
+	if(r.fbdpan.count) {
+		if(a2d_launch_bus_fbdpan(c->d_params, c->d_list.d + r.fbdpan.first, r.fbdpan.count, consume & 1, c->stream))
+			return c->fail(A2AMD_EHIP, "pan-tailed delay chain launch failed: %s", hipGetErrorString(hipGetLastError()));
+		c->last_fbdpan.launched = 1;
 		++c->stats.launches;
 	}
 	if(r.generic.count) {

@@ -29,7 +29,7 @@ static inline int within(const char *name, int lo, int hi) { const int v = num(n
 	X(bool, hosttiming, a2sw::set("A2AMD_HOSTTIMING")) X(int, hosttiming_level, a2sw::num("A2AMD_HOSTTIMING", 0))	/* unset: host timing counters and their dump at exit; the level (2, 3) adds per-batch traces */ \
 	X(bool, noise_quiet, a2sw::on("A2AMD_NOISE_QUIET"))	/* on. 0: no launch classes for wtosc (noise)-[filter12-]panmix voices - they are wtosc-[filter12-]panmix voices, and every noise voice of a device-seeded batch gets the stand-in record (A/B) */ \
 	X(bool, no_direct, a2sw::set("A2AMD_NO_DIRECT"))	/* unset. Set: the root never stores the master bus straight into the host's buffer */ \
-	X(int, no_fast, a2sw::num("A2AMD_NO_FAST", 0))		/* 0. Bit mask of classes sent to the general kernel: 1 wtosc-panmix, 2 wtosc-filter12-panmix, 4 driver chains, 8 2 x wtosc-panmix, 16 fm-panmix, 32 fbdelay chains, 64 no records kernel, 128 2 x wtosc-filter12-panmix, 256 bare wtosc (debugging / A-B tests) */ \
+	X(int, no_fast, a2sw::num("A2AMD_NO_FAST", 0))		/* 0. Bit mask of classes sent to the general kernel: 1 wtosc-panmix, 2 wtosc-filter12-panmix, 4 driver chains, 8 2 x wtosc-panmix, 16 fm-panmix, 32 fbdelay chains, 64 no records kernel, 128 2 x wtosc-filter12-panmix, 256 bare wtosc, 512 pan-tailed fbdelay chains (debugging / A-B tests) */ \
 	X(bool, no_graph, a2sw::set("A2AMD_NO_GRAPH"))		/* unset. Set: no batch is captured into or replayed from a graph */ \
 	X(bool, no_moving, a2sw::set("A2AMD_NO_MOVING"))	/* unset. Set: gliding voices get no stand-in record (they stay the quiet kernels') */ \
 	X(bool, no_selfclean, a2sw::set("A2AMD_NO_SELFCLEAN"))	/* unset. Set: bus owners never count as clearing their own buses */ \

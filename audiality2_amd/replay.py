@@ -126,6 +126,15 @@ class a2amd_bare_batch_info(C.Structure):
         return "bare_batch_info(" + ", ".join(f"{n}={getattr(self, n)}" for n, _ in self._fields_) + ")"
 
 
+class a2amd_fbdpan_batch_info(C.Structure):
+    """include/a2amd_fbdpan.h: who rendered the pan-tailed delay chains (inline; fbdelay x 1..4; panmix >) of the most recent batch"""
+    _fields_ = [(n, C.c_uint32) for n in ("launched", "class_voices", "quiet_voices", "gliding_voices", "record_voices",
+                                          "max_delays")] + [("reserved", C.c_uint32 * 2)]
+
+    def __repr__(self):
+        return "fbdpan_batch_info(" + ", ".join(f"{n}={getattr(self, n)}" for n, _ in self._fields_[:-1]) + ")"
+
+
 class a2amd_vm_batch_info(C.Structure):
     """include/a2amd_vmbatch.h: who ran the device VM's voices of the most recent batch"""
     _fields_ = [("listed", C.c_uint32), ("class_voices", C.c_uint32 * 3), ("other_voices", C.c_uint32),
@@ -203,6 +212,9 @@ class Backend:
         self._last_batch_bare = None
         if hasattr(lib, prefix + "last_batch_bare"):
             self._last_batch_bare = fn("last_batch_bare", i32, vp, C.POINTER(a2amd_bare_batch_info))
+        self._last_batch_fbdpan = None
+        if hasattr(lib, prefix + "last_batch_fbdpan"):
+            self._last_batch_fbdpan = fn("last_batch_fbdpan", i32, vp, C.POINTER(a2amd_fbdpan_batch_info))
         # the device VM (the product library only; include/a2amd_vm.h)
         self.has_vm = hasattr(lib, prefix + "vm_adopt")
         if self.has_vm:
@@ -360,6 +372,16 @@ class Backend:
             raise RuntimeError(f"this library has no {self.prefix}last_batch_bare")
         bi = a2amd_bare_batch_info()
         self._chk(self._last_batch_bare(self.ctx, C.byref(bi)), "last_batch_bare")
+        return bi
+
+    def last_batch_fbdpan(self):
+        """a2amd_last_batch_fbdpan: whether k_bus_fbdpan was launched for the most recent batch, the bus owners of its
+        class (inline; fbdelay x 1..4; panmix wired and adding) by who rendered them - the kernel (of which within the
+        host's bound for a moving volume or pan), the general kernel (those with records) - and the longest chain"""
+        if self._last_batch_fbdpan is None:
+            raise RuntimeError(f"this library has no {self.prefix}last_batch_fbdpan")
+        bi = a2amd_fbdpan_batch_info()
+        self._chk(self._last_batch_fbdpan(self.ctx, C.byref(bi)), "last_batch_fbdpan")
         return bi
 
     def last_batch_vm(self):

@@ -194,14 +194,18 @@ class Scene:
                ((868.75, 1126.25, 1378.75), (0.03, 0.05, 0.05)))
 
     def add_group(self, fb=(63.1, 75.6, 100.4), gains=(0.3, 0.25, 0.25), preset=None, delays=2, mid_add=False,
-                  parent=None):
+                  parent=None, tail=None):
         """inline 0 *; fbdelay * *; fbdelay * >   (benchmark/fmtest4.a2s shape);
         preset="fmtest4": that song's own delay times and gains (BASELINE configs[3]).
         delays: fbdelay units in the chain, positions 0 .. delays - 1 - the last one wired and adding, the others in
         place.  mid_add: which of the others add to what they read instead of replacing it - True: the ones between the
         first and the last, positions 1 .. delays - 2; or the positions themselves, of 0 .. delays - 2.
         fb / gains: one triple for every delay, or a list with a triple per delay (the preset has two).
-        parent: the bus or delay group that holds this one, instead of the root."""
+        parent: the bus or delay group that holds this one, instead of the root.
+        tail="panmix": the master section of the reference's songs, inline 0 2; fbdelay 2 2 x delays; panmix+ 2 > 2 -
+        no delay wired (mid_add: any of positions 0 .. delays - 1), the panmix wired and adding; `units` ends in it."""
+        if tail not in (None, "panmix"):
+            raise ValueError(f"tail {tail!r}")
         if delays < 1:
             raise ValueError("a delay group has at least one delay")
         if preset == "fmtest4" and delays != len(self.FMTEST4):
@@ -209,16 +213,17 @@ class Scene:
         for what in (fb, gains):
             if isinstance(what, list) and len(what) != delays:
                 raise ValueError(f"{len(what)} triples for {delays} delays")
-        if mid_add not in (True, False, None) and not set(mid_add) <= set(range(delays - 1)):
-            raise ValueError(f"mid_add positions are 0 .. {delays - 2}")
+        inplace = delays if tail else delays - 1        # the delays that are not wired
+        if mid_add not in (True, False, None) and not set(mid_add) <= set(range(inplace)):
+            raise ValueError(f"mid_add positions are 0 .. {inplace - 1}")
         be, k = self.be, self._key()
         if mid_add is True:
             mid_add = range(1, delays - 1)
         adding = set(mid_add or ())
         u = [be.unit_init(k, K_INLINE, 0, 0, 2, 0)]
-        u += [be.unit_init(k, K_FBDELAY, PROCADD if i in adding else 0, 2, 2, 0) for i in range(delays - 1)]
-        u.append(be.unit_init(k, K_FBDELAY, PROCADD, 2, 2, 1))
-        for i, d in enumerate(u[1:]):
+        u += [be.unit_init(k, K_FBDELAY, PROCADD if i in adding else 0, 2, 2, 0) for i in range(inplace)]
+        u.append(be.unit_init(k, K_PANMIX if tail else K_FBDELAY, PROCADD, 2, 2, 1))
+        for i, d in enumerate(u[1:1 + delays]):
             if preset == "fmtest4":
                 dfb, dg = self.FMTEST4[i]
             else:

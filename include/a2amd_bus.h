@@ -1,10 +1,12 @@
 /* a2amd_bus.h - part of include/a2amd.h (which includes it): who rendered the bus owners of the most
  * recent batch - the voices with an inline unit, i.e. the root and the group voices.
  *
- * A bus owner goes to one of three kernels.  k_bus_driver takes the chain inline -> panmix 2->2 -> xinsert
+ * A bus owner goes to one of four kernels.  k_bus_driver takes the chain inline -> panmix 2->2 -> xinsert
  * (the engine's root and group drivers) and its mono form, inline 0 1 -> panmix 1->2 [-> xinsert] under a stereo bus,
  * whose one channel it reads twice (a mono root stays with the general kernel), k_bus_fbdchain the chain inline -> fbdelay [-> fbdelay ...] of at
- * most four delays whose taps are all between one fragment and the delay line less one fragment long, the
+ * most four delays whose taps are all between one fragment and the delay line less one fragment long, k_bus_fbdpan
+ * the same chain with no delay wired and a wired, adding panmix 2->2 behind the last one (a2amd_fbdpan.h, which has
+ * its counts: fbd_voices below stays the wired-delay chains), the
  * general kernel every other chain - and any bus owner in a batch in which it carries records.  The counts
  * are the host's: what upload() listed for each kernel and what the launches were given, not something read
  * back from the device.  A test that names one of the bus kernels asserts them to prove it got there. */
@@ -32,7 +34,7 @@ typedef struct a2amd_bus_info {
 	                                  * batch: they stayed with k_bus_driver and are counted in driver_voices */
 	uint32_t fbd_voices;             /* bus owners on k_bus_fbdchain's lists that carry no record this batch */
 	uint32_t generic_voices;         /* bus owners the general kernel rendered: by their class, or because they carry
-	                                  * records this batch */
+	                                  * records this batch (a pan-tailed delay chain only in such a batch) */
 	uint32_t consume;                /* as given to the last bus launch: 0 the buses are cleared by a memset and the
 	                                  * root adds into the master bus, 1 the bus kernels zero what they read, 3 ... and
 	                                  * the root stores the master bus */
