@@ -14,6 +14,7 @@
 			      // (A2DVoiceExt).  (First cut: unit[16] in the record itself, 96 bytes - k_leaf_oscfiltpan 0.5539 against
 			      // 0.5505 ms, k_leaf_osc2pan 2.198 against 2.186 ms, same box, interleaved x 3: profiles/r06_maxchain_ab.txt)
 #define A2D_MAXBATCH 256
+#define FBW_MAXWIN (2 * A2D_MAXBATCH)	// k_bus_fbdpan's windows launch: table rows (windows) per voice and batch, in LDS
 #define A2D_USTATE    24      // int32 words of device state per unit
 #define A2D_MAXCH      8
 #define A2D_FRAG      64
@@ -370,7 +371,9 @@ int a2d_launch_commit(const A2DParams &hp, const A2DCommit &cm, void *stream);
 // quiet "inline; fbdelay 2->2 ... ; fbdelay 2->2 >" voices (one workgroup each)
 int a2d_launch_bus_fbdchain(const A2DParams *dparams, const int *dlist, int nlist, int consume, void *stream);
 // k_bus_fbdpan: the same rounds with a panmix 2->2, wired and adding, behind the last delay (none of them wired)
-int a2d_launch_bus_fbdpan(const A2DParams *dparams, const int *dlist, int nlist, int consume, void *stream);
+// (windows: the launch over the voices whose run is windows only - R_SEG records that tile their fragments, at most
+// FBW_MAXWIN table rows a voice, the host has checked both - and is read; without it a voice with a run is skipped)
+int a2d_launch_bus_fbdpan(const A2DParams *dparams, const int *dlist, int nlist, int consume, void *stream, int windows = 0);
 int a2d_launch_park(int32_t *stage, int32_t *bus, unsigned words, void *stream);
 int a2d_launch_add_bus(int32_t *dst, int32_t *src, unsigned words, void *stream);
 // bus[f][ch][64] (nch channels per fragment) += inj[f][ch][64] (8 channels per fragment), ch < n

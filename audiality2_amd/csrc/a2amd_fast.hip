@@ -2946,15 +2946,24 @@ int a2d_launch_bus_fbdchain(const A2DParams *dparams, const int *dlist, int nlis
 // batch, so nobody else decides by the words it stores.
 // (A body shared with k_bus_fbdchain as a template on the tail was tried first: it moved that kernel's code - 676
 // instructions became 768, profiles/fbdpan.md - so the two stand side by side.)
-__global__ __launch_bounds__(FBC_THREADS)
-void k_bus_fbdpan(const A2DParams *__restrict__ pp, const int *__restrict__ list, int nlist, int consume)
+// WIN: the windows launch (k_bus_fbdpan_win).  The voice's run is windows only - R_SEG records that tile their fragments, a
+// fragment without one being the default window (0, fragframes[f]); the host has checked that, and that the batch needs at
+// most FBW_MAXWIN rows (a2amd_sched.cpp: seg_rows).  fbdelay never sees a window (fbdelay.c:69-126 is a loop over frames)
+// and neither does inline; panmix sees one through a2_PrepareRamper alone (a2_dsp.h:128-149), once per window and ramper.
+// At rest that sets the same gains for every window: the run is ignored.  Otherwise thread 0 steps the rampers window by
+// window instead of fragment by fragment - a row per window, the clamp flag packed with the window's first frame and its
+// end: clamp | off << 8 | (off + n) << 16 - and wfirst[f] names fragment f's first row; a frame finds its row from there.
+// Everything behind the gains is the one body for both launches.
+template<bool WIN>
+DEV void bus_fbdpan(const A2DParams *__restrict__ pp, const int *__restrict__ list, const int consume)
 {
-	__shared__ int fr[A2D_MAXBATCH][5];	// per fragment: vol, dvol, pan, dpan, clamp (at rest: row 0 alone)
-	__shared__ int at_rest;
 	const A2DParams &p = *pp;
+	__shared__ int fr[WIN ? FBW_MAXWIN : A2D_MAXBATCH][5];	// per fragment (WIN: per window): vol, dvol, pan, dpan, clamp (at rest: row 0 alone)
+	__shared__ unsigned short wfirst[WIN ? A2D_MAXBATCH + 1 : 1];
+	__shared__ int at_rest;
 	const int slot = list[blockIdx.x];
-	if(p.runs[slot].count)
-		return;		// carries records this batch: the general kernel renders it
+	if(!WIN && p.runs[slot].count)
+		return;		// carries records this batch: the general kernel renders it, or - windows only - the windows launch
 	if(!p.vactive[slot])
 		return;
 	const A2DVoice &vc = p.voices[slot];
@@ -2972,6 +2981,34 @@ void k_bus_fbdpan(const A2DParams *__restrict__ pp, const int *__restrict__ list
 			fr[0][0] = vol.value; fr[0][1] = 0;
 			fr[0][2] = pan.value; fr[0][3] = 0;
 			fr[0][4] = a2s_pan_over(pan.value);
+		} else if constexpr(WIN) {
+			// ... window by window: the fragment's R_SEG records in run order, or its default window
+			const A2DRun run = p.runs[slot];
+			int ri = run.first, row = 0;
+			const int rend = run.first + run.count;
+			for(int f = 0; f < nfrags; ++f) {
+				wfirst[f] = (unsigned short)row;
+				const bool cut = ri < rend && (int)A2D_RFRAG(p.recs[ri].head) == f;
+				do {
+					const unsigned dur = cut ? p.recs[ri].dur : (unsigned)p.fragframes[f] << 16;
+					const int off = (int)(dur & 0xffff), n = (int)(dur >> 16);
+					ri += cut;
+					if(row >= FBW_MAXWIN)
+						break;	// (the host lists no such run: FBW_MAXWIN is its cap)
+					const int clamp = a2s_pan_over(pan.target) || a2s_pan_over(pan.value);
+					ramp_prepare(vol, n);
+					ramp_prepare(pan, n);
+					fr[row][0] = vol.value; fr[row][1] = vol.delta;
+					fr[row][2] = pan.value; fr[row][3] = pan.delta;
+					fr[row][4] = clamp | (off & 0xff) << 8 | ((off + n) & 0xff) << 16;
+					++row;
+					ramp_run(vol, n);
+					ramp_run(pan, n);
+				} while(cut && ri < rend && (int)A2D_RFRAG(p.recs[ri].head) == f);
+			}
+			wfirst[nfrags] = (unsigned short)row;
+			ramp_store(w + PW_VOL, vol);
+			ramp_store(w + PW_PAN, pan);
 		} else {
 			// panmix_process22's rampers (panmix.c:192-249)
 			for(int f = 0; f < nfrags; ++f) {
@@ -3062,11 +3099,21 @@ void k_bus_fbdpan(const A2DParams *__restrict__ pp, const int *__restrict__ list
 			// panmix_process22 on what the last delay left (panmix.c:191-229), adding into the output bus
 			int v0 = rv0, v1 = rv1;
 			if(!rest) {
-				const int vk = wadd(fr[f][0], wmul(fr[f][1], lane));
-				const int pk = wadd(fr[f][2], wmul(fr[f][3], lane));
+				// (an uncut fragment: one row for all 64 lanes, a broadcast; a cut one: the row whose window holds the frame)
+				int r = f, wk = lane;
+				if constexpr(WIN) {
+					// (both bounds hold by the host's checks; they keep a run that broke them inside the table)
+					r = min((int)wfirst[f], FBW_MAXWIN - 1);
+					const int rl = min((int)wfirst[f + 1], FBW_MAXWIN) - 1;
+					while(r < rl && lane >= (fr[r][4] >> 16))
+						++r;
+					wk = lane - ((fr[r][4] >> 8) & 0xff);
+				}
+				const int vk = wadd(fr[r][0], wmul(fr[r][1], wk));
+				const int pk = wadd(fr[r][2], wmul(fr[r][3], wk));
 				const int vp = mul64s(pk, vk, 24);
 				v0 = wsub(vk, vp); v1 = wadd(vk, vp);
-				if(fr[f][4]) {
+				if(WIN ? fr[r][4] & 1 : fr[r][4]) {
 					const int lim = wshl(vk, 1);
 					if(v0 > lim) v0 = lim;
 					if(v1 > lim) v1 = lim;
@@ -3093,11 +3140,23 @@ void k_bus_fbdpan(const A2DParams *__restrict__ pp, const int *__restrict__ list
 	}
 }
 
-int a2d_launch_bus_fbdpan(const A2DParams *dparams, const int *dlist, int nlist, int consume, void *stream)
+__global__ __launch_bounds__(FBC_THREADS)
+void k_bus_fbdpan(const A2DParams *__restrict__ pp, const int *__restrict__ list, int nlist, int consume)
+{
+	bus_fbdpan<false>(pp, list, consume);
+}
+
+__global__ __launch_bounds__(FBC_THREADS)
+void k_bus_fbdpan_win(const A2DParams *__restrict__ pp, const int *__restrict__ list, int nlist, int consume)
+{
+	bus_fbdpan<true>(pp, list, consume);
+}
+
+int a2d_launch_bus_fbdpan(const A2DParams *dparams, const int *dlist, int nlist, int consume, void *stream, int windows)
 {
 	if(nlist <= 0)
 		return 0;
-	hipLaunchKernelGGL(k_bus_fbdpan, dim3(nlist), dim3(FBC_THREADS), 0, (hipStream_t)stream,
+	hipLaunchKernelGGL(windows ? k_bus_fbdpan_win : k_bus_fbdpan, dim3(nlist), dim3(FBC_THREADS), 0, (hipStream_t)stream,
 			dparams, dlist, nlist, consume);
 	return (int)hipGetLastError();
 }

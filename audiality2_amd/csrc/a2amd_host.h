@@ -241,7 +241,9 @@ enum { DYN_OSC1 = 0, DYN_OSC2, DYN_FILT, DYN_FILT2, DYN_REST, DYN_N };
 // (ramp: in d_dyn, this batch's driver chains without records whose volume or pan may still glide - k_bus_driver's
 // second launch of the depth, one workgroup a voice)
 // (fbdpan: the delay chains that end in a wired panmix, k_bus_fbdpan's - filled in upload(), read in launch_depth())
-struct DepthRange { ListRange driver, fbd, fbdpan, generic, dyn, ramp; };
+// (fbdpan_win: in d_dyn, this batch's voices of that class whose run is windows only and tiles its fragments - they keep
+// the run, stand on no other exception list, and are k_bus_fbdpan's windows launch of the depth; include/a2amd_buswin.h)
+struct DepthRange { ListRange driver, fbd, fbdpan, generic, dyn, ramp, fbdpan_win; };
 // a launch class's leaf segment and, where k_leaf_recs knows the class, its exception list (-1: a bus owner), in CLS_* order
 static const struct { int8_t leaf, dyn; } cls_lists[CLS_N] = {
 	{ LEAF_GENERIC, DYN_REST }, { LEAF_OSCPAN, DYN_OSC1 }, { LEAF_OSCFILTPAN, DYN_FILT }, { -1, -1 }, { -1, -1 },
@@ -536,6 +538,7 @@ struct a2amd_ctx {
 	uint32_t n_bare_quiet = 0, n_bare_gliding = 0, n_bare_records = 0, n_mono_drivers = 0;
 	a2amd_bare_batch_info last_bare = {};	// a2amd_last_batch_bare()
 	a2amd_fbdpan_batch_info last_fbdpan = {};	// a2amd_last_batch_fbdpan(): upload() counts, launch_depth() sets launched
+	a2amd_bus_windows_info last_buswin = {};	// a2amd_last_batch_bus_windows(): likewise, reset by every upload()
 	// a2amd_last_batch_buses(): upload() fills in who renders the bus owners, launch_depth() what it was told to
 	// consume (a graph: gconsume, as at its capture); master_direct is the context's own flag
 	a2amd_bus_info last_bus = {};

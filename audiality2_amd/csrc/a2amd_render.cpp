@@ -112,7 +112,11 @@ int a2amd_render(a2amd_ctx *c, unsigned phases, int32_t *const *out, unsigned ca
 			if(x.unit >= 0 && x.tapped)
 				taps = true;
 		if(!c->sw.no_direct && (phases & A2AMD_RENDER_READBACK) && (phases & both) == both && !(phases & A2AMD_RENDER_KEEP) &&
-				!(phases & A2AMD_RENDER_TAPS) && !c->comm && !c->dist_local && c->uploaded && c->with_recs.empty() &&
+				!(phases & A2AMD_RENDER_TAPS) && !c->comm && !c->dist_local && c->uploaded &&
+				// (no record at all, or records and at least one delay chain that kept its fast kernel through cut windows -
+				// a2amd_buswin.h: the batch a song's master section makes of nearly every buffer.  consume_ok says that no bus
+				// owner is the general kernel's, launch_depth() that nothing but the root driver is at depth 0)
+				(c->with_recs.empty() || c->last_buswin.fbd_dropped + c->last_buswin.fbdpan_voices) &&
 				c->consume_ok && c->sub_resume < 0 && !c->paused_at && !taps) {
 			const size_t n = (size_t)c->nfrags * c->cfg.channels * A2D_FRAG;
 			if(phases & A2AMD_RENDER_ASYNC) {
@@ -499,6 +503,15 @@ int a2amd_last_batch_fbdpan(const a2amd_ctx *c, a2amd_fbdpan_batch_info *out)
 	if(!c || !out)
 		return A2AMD_EINVAL;
 	*out = c->last_fbdpan;
+	return A2AMD_OK;
+}
+
+int a2amd_last_batch_bus_windows(const a2amd_ctx *c, a2amd_bus_windows_info *out)
+{
+	if(!c || !out)
+		return A2AMD_EINVAL;
+	*out = c->last_buswin;
+	out->window_cap = FBW_MAXWIN;	// (also in front of the first batch)
 	return A2AMD_OK;
 }
 

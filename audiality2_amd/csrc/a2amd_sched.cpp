@@ -344,6 +344,41 @@ bool is_fbdchain(const a2amd_ctx *c, const HVoice &v)
 	return true;
 }
 
+// "Windows only, and they tile": every record of the run an R_SEG, the run sorted by fragment, and the windows of a
+// fragment starting at frame 0, following each other without gap or overlap, none of them empty, and ending at
+// fragframes[f] - the fragment is covered exactly once, in order, which is what lets a delay chain ignore the cuts
+// (fbdelay.c:69-126 is a loop over frames) and k_bus_fbdpan's windows launch find every frame's window.  Records reach
+// the library through the C ABI from outside: this is checked, not assumed.
+// Returns the table rows the batch needs - over its fragments, max(1, windows in the fragment): one without a record is
+// the default window (0, fragframes[f]) - or 0: not windows only (or no record at all), -1: windows only, but not a tiling.
+int seg_rows(const A2DRec *recs, size_t nrecs, const unsigned *fragframes, int nfrags)
+{
+	if(!nrecs)
+		return 0;
+	for(size_t i = 0; i < nrecs; ++i)
+		if(A2D_ROP(recs[i].head) != R_SEG)
+			return 0;
+	int rows = nfrags, prev = -1;
+	unsigned at = 0;	// the frame the open fragment's next window must start at
+	for(size_t i = 0; i < nrecs; ++i) {
+		const int f = (int)A2D_RFRAG(recs[i].head);
+		const unsigned off = recs[i].dur & 0xffff, n = recs[i].dur >> 16;
+		if(f >= nfrags || f < prev)
+			return -1;
+		if(f != prev) {
+			if(prev >= 0 && at != fragframes[prev])
+				return -1;
+			prev = f;
+			at = 0;
+		} else
+			++rows;		// (a fragment's first window is the row it has anyway)
+		if(off != at || !n || n > fragframes[f] - at)
+			return -1;
+		at += n;
+	}
+	return at == fragframes[prev] ? rows : -1;
+}
+
 // inline 0 2; fbdelay 2 2 [; fbdelay 2 2 ...]; panmix 2 2 wired and adding - no delay wired, any of them adding or not:
 // the master section of most songs (k2intro.a2s, fmtest3.a2s: `struct { inline 0 *; fbdelay * *; panmix * > }`)
 bool is_fbdpan_chain(const a2amd_ctx *c, const HVoice &v)
@@ -384,6 +419,9 @@ int upload(a2amd_ctx *c)
 	c->n_bus_windows_dropped = 0;
 	c->last_bus.driver_ramping = c->last_bus.driver_windows_dropped = 0;
 	c->last_fbdpan.gliding_voices = 0;
+	// (a2amd_last_batch_bus_windows(): a quiet batch has no record, so no windows)
+	c->last_buswin = a2amd_bus_windows_info{};
+	c->last_buswin.window_cap = FBW_MAXWIN;
 	if(c->sw.hosttiming) {
 		// (A2AMD_HOSTTIMING: why a batch did not take the quiet path - first reason that applies)
 		const int why = !c->blob_quiet ? 0 : !c->with_recs.empty() ? 1 : !c->prev_with_recs.empty() ? 2 :
@@ -611,6 +649,24 @@ int upload(a2amd_ctx *c)
 				v.listed_recs = false;
 				continue;
 			}
+		}
+		// ... and a group voice `inline; fbdelay [; fbdelay ...]` with the last delay wired (k_bus_fbdchain's), whatever its
+		// delays hold: fbdelay has no ramper and never sees a window - fbdelay_process (fbdelay.c:69-126) is a loop over
+		// frames that reads its parameters as plain integers and advances bufpos once per frame - so windows that cover
+		// each fragment exactly once, in order, leave the same delay lines, outputs and bufpos as the whole fragment, and
+		// inline picks its children's sum out of a bus they have filled independently.  seg_rows() checks the covering;
+		// a run that fails it stays: the general kernel's.  (is_fbdchain() itself, not v.cls: the class may be stale in
+		// front of the list rebuild below.  The pan-tailed chains keep their runs: the exception lists below.)
+		else if(!c->sw.bus_windows && v.inline_pos >= 0 && v.vm < 0 && v.resolved && v.depth > 0 && !(c->sw.no_fast & 32) &&
+				is_fbdchain(c, v)) {
+			const int rows = seg_rows(v.recs.data(), v.recs.size(), c->fragframes, c->nfrags);
+			if(rows > 0) {
+				++c->last_buswin.fbd_dropped;
+				v.recs.clear();
+				v.listed_recs = false;
+				continue;
+			}
+			c->last_buswin.refused_tiling += rows < 0;
 		}
 		A2DRun r = { (int)recs.size(), (int)v.recs.size() };
 		recs.insert(recs.end(), v.recs.begin(), v.recs.end());
@@ -871,7 +927,7 @@ int upload(a2amd_ctx *c)
 		// filter voices, a wave of another kind somewhere in the batch - to the
 		// general kernel.
 		std::vector<int> dyn[DYN_N];
-		std::vector<std::vector<int>> dyn_bus(c->depth_ranges.size());
+		std::vector<std::vector<int>> dyn_bus(c->depth_ranges.size()), fbdpan_win(c->depth_ranges.size());
 		const bool no_recs_kernel = (c->sw.no_fast & 64) != 0;
 		for(int vi : c->with_recs) {
 			HVoice &v = c->voices[vi];
@@ -894,6 +950,25 @@ int upload(a2amd_ctx *c)
 				// kernel's, which renders the voices on its exception list; k_leaf_oscbare skips a voice that has a run)
 				dyn[DYN_REST].push_back(vi);
 			} else if((v.cls == CLS_BUSDRIVER || v.cls == CLS_FBDCHAIN || v.cls == CLS_FBDPAN) && v.depth < (int)dyn_bus.size()) {
+				// A pan-tailed delay chain whose run is windows only and tiles its fragments (seg_rows(); the classes are fresh
+				// here) keeps the run and its kernel: k_bus_fbdpan's windows launch of the depth, which steps volume and pan
+				// window by window as panmix_process22 would (a2_PrepareRamper once per window, a2_dsp.h:128-149) and ignores
+				// the run where they are at rest - its thread 0 decides that from the ramper words, not the host; the delays
+				// and inline never see a window.  It is on no other exception list - the general kernel never sees it, the
+				// launch over r.fbdpan skips it for its run - and is no reason to give up the self-cleaning buses.
+				if(v.cls == CLS_FBDPAN && !c->sw.bus_windows && !(c->sw.no_fast & 512) && v.depth > 0 && v.vm < 0 && v.resolved) {
+					const int rows = seg_rows(v.recs.data(), v.recs.size(), c->fragframes, c->nfrags);
+					a2amd_bus_windows_info &bw = c->last_buswin;
+					if(rows > 0 && rows <= FBW_MAXWIN) {
+						fbdpan_win[v.depth].push_back(vi);
+						++bw.fbdpan_voices;
+						bw.fbdpan_gliding += v.moving_until > c->vm.batch_time;
+						bw.fbdpan_windows += (uint32_t)rows;
+						continue;
+					}
+					bw.refused_tiling += rows < 0;
+					bw.refused_cap += rows > FBW_MAXWIN;
+				}
 				dyn_bus[v.depth].push_back(vi);
 				if(c->sw.hosttiming_level >= 3 && !v.recs.empty())
 					fprintf(stderr, "a2amd: bus voice %d (depth %d, class %d) carries %zu records, first: frag %u op %u unit %u reg %u value %d\n",
@@ -943,10 +1018,13 @@ int upload(a2amd_ctx *c)
 			c->depth_ranges[d].dyn = append_range(dyn_all, dyn_bus[d]);
 			if(!dyn_bus[d].empty())
 				c->consume_ok = false;	// a bus owner carries records: the general kernel renders it
+			// (... but for those whose run k_bus_fbdpan's windows launch takes: a fast owner still)
+			c->depth_ranges[d].fbdpan_win = append_range(dyn_all, fbdpan_win[d]);
 		}
 		// a2amd_last_batch_buses(): the bus owners by the kernel that renders them this batch.  k_bus_driver,
 		// k_bus_fbdchain and k_bus_fbdpan leave a listed voice whose run is not empty to the general kernel (the depth's
-		// exception list).
+		// exception list) - or, a pan-tailed chain with a windows-only run, to k_bus_fbdpan's windows launch (fbdpan_win above:
+		// not in generic_voices; a2amd_last_batch_bus_windows() counts it).
 		a2amd_bus_info &bi = c->last_bus;
 		bi = a2amd_bus_info{};
 		bi.driver_windows_dropped = c->n_bus_windows_dropped;
@@ -976,7 +1054,8 @@ int upload(a2amd_ctx *c)
 			bi.generic_voices += (uint32_t)(r.generic.count + r.dyn.count);
 		}
 		// a2amd_last_batch_fbdpan(): the pan-tailed delay chains by who renders them this batch.  One with records stands on
-		// its depth's exception list above; the others are k_bus_fbdpan's, those whose volume or pan may not be at rest by
+		// its depth's exception list above (record_voices: the general kernel's, less those of the windows launch,
+		// a2amd_bus_windows_info.fbdpan_voices); the others are k_bus_fbdpan's, those whose volume or pan may not be at rest by
 		// the host's bound (moving_until, as for the drivers) included: the class has no list of its own for them, the
 		// voice's one workgroup steps the rampers itself.
 		a2amd_fbdpan_batch_info &fp = c->last_fbdpan;
@@ -1188,6 +1267,14 @@ int launch_depth(a2amd_ctx *c, int d, int consume, A2DCommitSet *pend)	// consum
 		if(a2d_launch_bus_fbdpan(c->d_params, c->d_list.d + r.fbdpan.first, r.fbdpan.count, consume & 1, c->stream))
 			return c->fail(A2AMD_EHIP, "pan-tailed delay chain launch failed: %s", hipGetErrorString(hipGetLastError()));
 		c->last_fbdpan.launched = 1;
+		++c->stats.launches;
+	}
+	// ... and those of the class whose run is windows only (upload(): DepthRange::fbdpan_win): the same kernel in its
+	// windows mode, which reads the run the launch above skipped the voice for
+	if(r.fbdpan_win.count) {
+		if(a2d_launch_bus_fbdpan(c->d_params, c->d_dyn + r.fbdpan_win.first, r.fbdpan_win.count, consume & 1, c->stream, 1))
+			return c->fail(A2AMD_EHIP, "pan-tailed delay chain windows launch failed: %s", hipGetErrorString(hipGetLastError()));
+		c->last_fbdpan.launched = c->last_buswin.launched = 1;
 		++c->stats.launches;
 	}
 	if(r.generic.count) {

@@ -17,7 +17,7 @@ static inline int within(const char *name, int lo, int hi) { const int v = num(n
 
 // X(type, member, read)	// name, default: meaning.  "x_set": whether the switch was there at all, where the code asks.
 #define A2AMD_SWITCHES(X) \
-	X(bool, bus_windows, a2sw::set("A2AMD_BUS_WINDOWS"))	/* unset: driver chains at rest drop windows-only records. Set: they go to the general kernel (A/B: round 4's routing) */ \
+	X(bool, bus_windows, a2sw::set("A2AMD_BUS_WINDOWS"))	/* unset: driver chains at rest and wired delay chains drop windows-only records, pan-tailed delay chains take theirs to k_bus_fbdpan's windows launch (include/a2amd_buswin.h). Set: they go to the general kernel (A/B: round 4's routing) */ \
 	X(bool, cls_check, a2sw::set("A2AMD_CLS_CHECK"))	/* unset. Set: every rebuild of the launch lists classifies every voice anew and fails on a remembered class that no longer holds */ \
 	X(int, coef_cache_mb, a2sw::full("A2AMD_COEF_CACHE_MB", 192))	/* 192 ("" too): MB of Hermite entries beyond which waves of 4 096 samples or more play from their samples */ \
 	X(int, dbg_walk, a2sw::num("A2AMD_DBG_WALK", 0))	/* 0. Bits: 1 a2amd_voice_process() never takes its short path, 2 ... never reports the default window (debugging the walk) */ \

@@ -135,6 +135,15 @@ class a2amd_fbdpan_batch_info(C.Structure):
         return "fbdpan_batch_info(" + ", ".join(f"{n}={getattr(self, n)}" for n, _ in self._fields_[:-1]) + ")"
 
 
+class a2amd_bus_windows_info(C.Structure):
+    """include/a2amd_buswin.h: the delay-chain bus owners of the most recent batch whose only records were cut windows"""
+    _fields_ = [(n, C.c_uint32) for n in ("fbd_dropped", "fbdpan_voices", "fbdpan_gliding", "fbdpan_windows", "refused_tiling",
+                                          "refused_cap", "window_cap", "launched")]
+
+    def __repr__(self):
+        return "bus_windows_info(" + ", ".join(f"{n}={getattr(self, n)}" for n, _ in self._fields_) + ")"
+
+
 class a2amd_vm_batch_info(C.Structure):
     """include/a2amd_vmbatch.h: who ran the device VM's voices of the most recent batch"""
     _fields_ = [("listed", C.c_uint32), ("class_voices", C.c_uint32 * 3), ("other_voices", C.c_uint32),
@@ -215,6 +224,9 @@ class Backend:
         self._last_batch_fbdpan = None
         if hasattr(lib, prefix + "last_batch_fbdpan"):
             self._last_batch_fbdpan = fn("last_batch_fbdpan", i32, vp, C.POINTER(a2amd_fbdpan_batch_info))
+        self._last_batch_bus_windows = None
+        if hasattr(lib, prefix + "last_batch_bus_windows"):
+            self._last_batch_bus_windows = fn("last_batch_bus_windows", i32, vp, C.POINTER(a2amd_bus_windows_info))
         # the device VM (the product library only; include/a2amd_vm.h)
         self.has_vm = hasattr(lib, prefix + "vm_adopt")
         if self.has_vm:
@@ -382,6 +394,18 @@ class Backend:
             raise RuntimeError(f"this library has no {self.prefix}last_batch_fbdpan")
         bi = a2amd_fbdpan_batch_info()
         self._chk(self._last_batch_fbdpan(self.ctx, C.byref(bi)), "last_batch_fbdpan")
+        return bi
+
+    def last_batch_bus_windows(self):
+        """a2amd_last_batch_bus_windows: the delay-chain bus owners whose only records this batch were cut windows - wired
+        chains whose records were dropped (k_bus_fbdchain's), pan-tailed chains on k_bus_fbdpan's windows launch (of which
+        within the host's bound for a moving volume or pan, and the table rows their runs need), the runs left to the
+        general kernel because they do not tile their fragments or need more rows than window_cap, and whether the
+        windows launch ran"""
+        if self._last_batch_bus_windows is None:
+            raise RuntimeError(f"this library has no {self.prefix}last_batch_bus_windows")
+        bi = a2amd_bus_windows_info()
+        self._chk(self._last_batch_bus_windows(self.ctx, C.byref(bi)), "last_batch_bus_windows")
         return bi
 
     def last_batch_vm(self):

@@ -457,6 +457,8 @@ int  a2amd_last_batch(const a2amd_ctx *ctx, a2amd_batch_info *bi);
 #include "a2amd_oscbare.h"
 /* The quiet kernel of delay chains that end in a panmix (song masters): a2amd_last_batch_fbdpan(). */
 #include "a2amd_fbdpan.h"
+/* Delay-chain bus owners whose only records are cut windows, and what became of them: a2amd_last_batch_bus_windows(). */
+#include "a2amd_buswin.h"
 /* Who ran the device VM's voices (a2amd_vm.h) of the most recent batch: a2amd_last_batch_vm(). */
 #include "a2amd_vmbatch.h"
 

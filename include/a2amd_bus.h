@@ -7,7 +7,8 @@
  * most four delays whose taps are all between one fragment and the delay line less one fragment long, k_bus_fbdpan
  * the same chain with no delay wired and a wired, adding panmix 2->2 behind the last one (a2amd_fbdpan.h, which has
  * its counts: fbd_voices below stays the wired-delay chains), the
- * general kernel every other chain - and any bus owner in a batch in which it carries records.  The counts
+ * general kernel every other chain - and any bus owner in a batch in which it carries records, unless the records of
+ * a delay chain of either kind are cut windows only (a2amd_buswin.h).  The counts
  * are the host's: what upload() listed for each kernel and what the launches were given, not something read
  * back from the device.  A test that names one of the bus kernels asserts them to prove it got there. */
 #ifndef A2AMD_BUS_H
@@ -32,9 +33,11 @@ typedef struct a2amd_bus_info {
 	                                  * generous, and the ones already at rest render on the split path like the others */
 	uint32_t driver_windows_dropped; /* driver chains at rest whose records - cut windows only - were dropped this
 	                                  * batch: they stayed with k_bus_driver and are counted in driver_voices */
-	uint32_t fbd_voices;             /* bus owners on k_bus_fbdchain's lists that carry no record this batch */
+	uint32_t fbd_voices;             /* bus owners on k_bus_fbdchain's lists that carry no record this batch, those whose
+	                                  * windows-only records were dropped included (a2amd_bus_windows_info.fbd_dropped) */
 	uint32_t generic_voices;         /* bus owners the general kernel rendered: by their class, or because they carry
-	                                  * records this batch (a pan-tailed delay chain only in such a batch) */
+	                                  * records this batch (a pan-tailed delay chain only in such a batch, and not where its
+	                                  * run went to k_bus_fbdpan's windows launch) */
 	uint32_t consume;                /* as given to the last bus launch: 0 the buses are cleared by a memset and the
 	                                  * root adds into the master bus, 1 the bus kernels zero what they read, 3 ... and
 	                                  * the root stores the master bus */
