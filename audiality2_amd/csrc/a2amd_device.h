@@ -193,6 +193,7 @@ enum { XW_SLOT = 0, XW_MODE = 1 };
 
 #define A2D_FAST_FCH 8	// k_leaf_oscpan: fragments per chunk (the host sizes the time slices by it)
 #define A2D_OSC2_FCH 4	// k_leaf_osc2pan: fragments per chunk
+#define A2D_OSC2_SCH 16	// ... and per super-chunk (a multiple of the chunk): what a wavefront keeps bus sums for in LDS
 #define A2D_MAXVPW   32       // voices one wavefront may walk per fragment
 
 struct A2DParams {
@@ -226,6 +227,32 @@ struct A2DParams {
 	uint8_t         fragframes[A2D_MAXBATCH];
 	uint16_t        fragstart[A2D_MAXBATCH];	// frames before each fragment
 };
+
+// How k_leaf_osc2pan walks a batch, for the kernel and for the host's report of it (include/a2amd_osc2.h) alike.
+// Time slice 'slice' of 'ysplit' takes the chunks [*c_lo, *c_hi) of A2D_OSC2_FCH fragments, *nslices of the ysplit
+// have any; false: this one is empty.
+#ifdef __HIPCC__
+#define A2D_HD static inline __host__ __device__
+#else
+#define A2D_HD static inline
+#endif
+A2D_HD bool a2d_osc2_slice(int nfrags, int ysplit, int slice, int *c_lo, int *c_hi, int *nslices)
+{
+	const int nchunks = (nfrags + A2D_OSC2_FCH - 1) / A2D_OSC2_FCH;
+	const int per = (nchunks + ysplit - 1) / ysplit;
+	*c_lo = slice * per;
+	*c_hi = *c_lo + per < nchunks ? *c_lo + per : nchunks;
+	*nslices = (nchunks + per - 1) / per;
+	return *c_lo < nchunks;
+}
+// A slice is walked in super-chunks of at most A2D_OSC2_SCH fragments, counted from its first chunk.  One whose n
+// fragments are all whole - A2D_FRAG frames each, so together n * A2D_FRAG: no fragment is longer - is walked voice by
+// voice; one that holds a shorter fragment (a cut window) chunk by chunk.  From the frames before its first and its
+// last fragment and that last one's length.
+A2D_HD bool a2d_osc2_whole(unsigned start_first, unsigned start_last, unsigned frames_last, int n)
+{
+	return start_last + frames_last - start_first == (unsigned)n * A2D_FRAG;
+}
 
 // A noise oscillator's default window - a fragment without records for its voice - takes the engine's RNG word from
 // the batch's seed table (a window the engine called for carries an R_NOISESEED record instead).
@@ -399,7 +426,7 @@ int a2d_launch_leaf_oscfiltpan(const A2DParams *dparams, const A2DParams &hp, co
 // runs[idx[i]] = val[i] for the few voices whose record run changed this batch
 int a2d_launch_scatter_runs(const int *didx, const A2DRun *dval, int n, A2DRun *druns, void *stream);
 int a2d_launch_leaf_osc2pan(const A2DParams *dparams, const A2DParams &hp, const int *dlist, int nlist,
-		int vpw, int ysplit, int *ustage, unsigned char *staged, void *stream, A2DCommit *defer);
+		int vpw, int ysplit, int *ustage, unsigned char *staged, void *stream, A2DCommit *defer, int voice_major, int *ysplit_used);
 // wtosc[+wtosc] [-> filter12] -> panmix voices that carry records this batch (nosc = 1 | 2, filt = 0 | 1)
 // skip_empty: the list's voices get their records from the device VM (a2amd_vm.hip); those it left
 // without any this batch are rendered by their class's quiet kernel

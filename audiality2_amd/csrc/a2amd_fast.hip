@@ -695,6 +695,8 @@ void k_commit_oscpan(A2DCommit cm, const A2DVoice *__restrict__ voices, int *__r
 // Same plan as k_leaf_oscpan with the oscillator state doubled; 4 fragments per
 // register chunk keep the 16 window loads of a chunk within the register budget.
 #define OSC2_FCH A2D_OSC2_FCH
+#define OSC2_SCH A2D_OSC2_SCH
+static_assert(OSC2_SCH % OSC2_FCH == 0, "a super-chunk is whole chunks");
 enum { OV_MODE = 0, OV_WAVE, OV_DPHASE, OV_PHLO, OV_PHHI, OV_PRAMP, OV_P = 6, OV_A = 10, OV_NWORDS = 14 };
 enum { OD_MM = 0, OD_DPH, OD_SIZEM, OD_DOFF, OD_NWORDS };
 
@@ -727,6 +729,94 @@ DEV void osc_to_lanes(int (&so)[OV_NWORDS], const OscS &o, bool me)
 	WRL(so[OV_A + 2], o.a.delta); WRL(so[OV_A + 3], o.a.timer);
 }
 
+// A settled voice's two oscillators over one chunk of OSC2_FCH fragments, lane = frame: the one body of the kernel's
+// two walks of its settled voices.  Everything in Osc2Voice is wave-uniform; ldph = lane_dph() of each oscillator.
+// WHOLE: every fragment of the chunk has A2D_FRAG frames (pre and nfr are not read); otherwise fragment j has nfr[j]
+// frames (0 past the batch's end) and pre[j] before it in the chunk, and the caller drops the frames past nfr[j].
+// In: ph = the phase, at the level, at the chunk's first frame, wrapped or not.  Out: xs = the samples in the scratch
+// buffer, ph = the phase behind the chunk's fourth fragment, and for park (wave-uniform) end = the unwrapped end phase
+// of the last of the chunk's nf real fragments, wtosc.c:284: its wrapped start plus its frames x the increment.
+struct Osc2Voice {
+	unsigned dph[2], sizem[2];
+	int cb[2], amp[2];
+	uint64_t ph[2], end[2];
+};
+
+template<bool WHOLE>
+DEV void osc2_chunk(const CoefRsrc &crs, Osc2Voice &s, const unsigned (&ldph)[2], const int (&nfr)[OSC2_FCH],
+		const unsigned (&pre)[OSC2_FCH], int nf, bool park, int (&xs)[OSC2_FCH])
+{
+	// the coefficient entries of BOTH oscillators (4 fragments x 2 taps x 2: 48 registers) are in
+	// flight before either is used (one oscillator after the other, 24 registers in flight at a
+	// time, was 4 % slower)
+	Coef4 ka[2][OSC2_FCH], kb[2][OSC2_FCH];
+	unsigned pa[2][OSC2_FCH], pb[2][OSC2_FCH];
+#pragma unroll
+	for(int o = 0; o < 2; ++o) {
+		const unsigned dph = s.dph[o], sizem = s.sizem[o];
+		uint64_t ph = s.ph[o];
+		uint64_t phs[OSC2_FCH];
+		if(!(sizem & (sizem - 1)) && !(ph >> 48)) {
+			// power-of-two size: the modulus is a mask (as in k_leaf_oscpan)
+			const uint64_t mask = ((uint64_t)sizem << 24) - 1;
+#pragma unroll
+			for(int j = 0; j < OSC2_FCH; ++j)
+				phs[j] = (ph + (uint64_t)dph * (WHOLE ? (unsigned)(j * A2D_FRAG) : pre[j])) & mask;
+			ph = phs[OSC2_FCH - 1] + (uint64_t)dph * (WHOLE ? (unsigned)A2D_FRAG : (unsigned)nfr[OSC2_FCH - 1]);
+		} else {
+#pragma unroll
+			for(int j = 0; j < OSC2_FCH; ++j) {
+				ph = wrap_phase(ph, sizem);
+				phs[j] = ph;
+				ph += (uint64_t)dph * (WHOLE ? (unsigned)A2D_FRAG : (unsigned)nfr[j]);
+			}
+		}
+#pragma unroll
+		for(int j = 0; j < OSC2_FCH; ++j) {
+			pa[o][j] = tap_phase(phs[j], ldph[o]);
+			asm("" : "+v"(pa[o][j]));	// (32 bit offsets: scalar-base loads, as in k_leaf_oscpan)
+			pb[o][j] = pa[o][j] + (dph >> 17);
+			ka[o][j] = coef_at(crs, s.cb[o], pa[o][j]);
+			kb[o][j] = coef_at(crs, s.cb[o], pb[o][j]);
+		}
+		if(park) {
+			uint64_t e = ph;	// (a full chunk: behind its fourth fragment)
+#pragma unroll
+			for(int j = OSC2_FCH - 2; j >= 0; --j)
+				if(nf == j + 1)
+					e = phs[j] + (uint64_t)dph * (WHOLE ? (unsigned)A2D_FRAG : (unsigned)nfr[j]);
+			s.end[o] = e;
+		}
+		s.ph[o] = ph;
+	}
+#pragma unroll
+	for(int o = 0; o < 2; ++o)
+#pragma unroll
+		for(int j = 0; j < OSC2_FCH; ++j) {
+			const int y = mul64s(inter_coefs(ka[o][j], pa[o][j], kb[o][j], pb[o][j]), s.amp[o], 17);
+			// the second oscillator adds into the scratch buffer (wrap-around)
+			xs[j] = o ? wadd(xs[j], y) : y;
+		}
+}
+
+// a voice's constants for osc2_chunk() out of the lanes that keep them, its phases at the frame 'before' of the batch
+// (mm: the level of each, for the way back to the state's phase)
+DEV void osc2_voice_from_lanes(Osc2Voice &s, unsigned (&ldph)[2], unsigned (&mm)[2], const int (&od)[2][OD_NWORDS],
+		const int (&amp_l)[2], const int (&phlo_l)[2], const int (&phhi_l)[2], int v, unsigned before, int lane)
+{
+#pragma unroll
+	for(int o = 0; o < 2; ++o) {
+		mm[o] = (unsigned)rdl(od[o][OD_MM], v);
+		s.dph[o] = (unsigned)rdl(od[o][OD_DPH], v);
+		s.sizem[o] = (unsigned)rdl(od[o][OD_SIZEM], v);
+		s.cb[o] = coef_base((unsigned)rdl(od[o][OD_DOFF], v));
+		s.amp[o] = rdl(amp_l[o], v);
+		const uint64_t phase = (uint64_t)(unsigned)rdl(phlo_l[o], v) | ((uint64_t)(unsigned)rdl(phhi_l[o], v) << 32);
+		s.ph[o] = (phase >> mm[o]) + (uint64_t)before * s.dph[o];
+		ldph[o] = lane_dph(lane, s.dph[o]);
+	}
+}
+
 #define OSC2_WPE 4	// (round 2: 3 wavefronts per SIMD with 143 registers and no spills beat 4 with 128 and 39 spills by a
 			// fifth.  Round 3: with only the settled loop's values parked in registers the kernel needs 118 -
 			// 4 wavefronts without spills: 2.30 -> 2.24 ms at configs[3]; 3 wavefronts of the same code: 2.40)
@@ -735,7 +825,7 @@ void k_leaf_osc2pan(const A2DParams *__restrict__ pp, const int *__restrict__ li
 		int ysplit, const A2DVoice *__restrict__ voices, const int *ustate, int *ustage,
 		const int16_t *__restrict__ wavepool, const A2DWave *__restrict__ waves,
 		const uint32_t *__restrict__ ptab, int *__restrict__ busmem, const int *__restrict__ wavecoef,
-		unsigned char *__restrict__ staged)
+		unsigned char *__restrict__ staged, int vmajor)
 {
 	const A2DParams &p = *pp;
 	const int wv = rfl((int)(threadIdx.x >> 6));	// (wave-uniform, and known to the compiler as such)
@@ -749,16 +839,13 @@ void k_leaf_osc2pan(const A2DParams *__restrict__ pp, const int *__restrict__ li
 	FastPtrs g = { wavepool, waves, ptab, dbg };
 	const CoefRsrc crs = coef_rsrc(wavecoef);
 
-	const int nchunks = (nfrags + OSC2_FCH - 1) / OSC2_FCH;
-	const int per = (nchunks + ysplit - 1) / ysplit;
+	// this wavefront's time slice, and the slices that exist: voices that still have something moving are
+	// dealt over them - slice s walks the whole batch for every nslices-th of them
 	const int slice = blockIdx.y;
-	const int c_lo = slice * per, c_hi = min(nchunks, c_lo + per);
-	const bool last_slice = c_hi >= nchunks;
-	if(c_lo >= nchunks)
+	int c_lo, c_hi, nslices;
+	if(!a2d_osc2_slice(nfrags, ysplit, slice, &c_lo, &c_hi, &nslices))
 		return;
-	// (the slices that exist; voices that still have something moving are dealt over
-	// them - slice s walks the whole batch for every nslices-th of them)
-	const int nslices = (nchunks + per - 1) / per;
+	const bool last_slice = c_hi * OSC2_FCH >= nfrags;
 
 	int ffr[A2D_MAXBATCH / 64], fst[A2D_MAXBATCH / 64];
 #pragma unroll
@@ -816,101 +903,116 @@ void k_leaf_osc2pan(const A2DParams *__restrict__ pp, const int *__restrict__ li
 	}
 	const unsigned long long unsettled_mask = __ballot(mine && !settled_l);
 
-	// ---- settled voices: this slice's chunks ----
-	for(int c = c_lo; c < c_hi; ++c) {
-		const int f0 = c * OSC2_FCH;
-		const int nf = min((int)OSC2_FCH, nfrags - f0);
-		int acc0[OSC2_FCH], acc1[OSC2_FCH], nfr[OSC2_FCH];
+	// ---- settled voices: this slice, in super-chunks of up to OSC2_SCH fragments ----
+	// One of whole fragments only (a2d_osc2_whole) is walked voice by voice: a voice's constants leave their lanes
+	// once for all its chunks, its phases travel from chunk to chunk in scalar registers, every frame is live, and the
+	// bus sums of the super-chunk's fragments - more than registers hold - are this wavefront's tile in LDS.  One
+	// with a short fragment (a cut window), and every one with vmajor off (A2AMD_DEBUG bit 16), is walked chunk by
+	// chunk with the sums in registers.
+	__shared__ int tiles[FAST_WPB][OSC2_SCH][2][A2D_FRAG];
+	int (*const tile)[2][A2D_FRAG] = tiles[wv];
+	if(vmajor)
 #pragma unroll
-		for(int j = 0; j < OSC2_FCH; ++j) {
-			acc0[j] = acc1[j] = 0;
-			nfr[j] = (j < nf) ? frames_of(ffr, f0 + j) : 0;
-		}
-		const unsigned before = (unsigned)frames_of(fst, f0);
-		unsigned pre[OSC2_FCH];		// frames from the start of the chunk to each fragment
-		pre[0] = 0;
-#pragma unroll
-		for(int j = 1; j < OSC2_FCH; ++j)
-			pre[j] = pre[j - 1] + (unsigned)nfr[j - 1];
-		int cur_off = rdl(my_off, 0), cur_nch = rdl(my_nch, 0);
-		for(int v = 0; v < nv; ++v) {
-			if(!rdl(settled_l, v))
-				continue;
-			const int voff = rdl(my_off, v);
-			if(voff != cur_off) {
-				flush_acc(busmem, cur_off, cur_nch, f0, nf, lane, dbg, acc0, acc1);
-				cur_off = voff;
-				cur_nch = rdl(my_nch, v);
-			}
-			const int v0 = rdl(v0l, v), v1 = rdl(v1l, v);
-			// the coefficient entries of BOTH oscillators (4 fragments x 2 taps x 2: 48 registers) are in
-			// flight before either is used (one oscillator after the other, 24 registers in flight at a
-			// time, was 4 % slower)
-			int xs[OSC2_FCH];
-			uint64_t endph[2];
-			Coef4 ka[2][OSC2_FCH], kb[2][OSC2_FCH];
-			unsigned pa[2][OSC2_FCH], pb[2][OSC2_FCH];
-			int amps[2];
-#pragma unroll
-			for(int o = 0; o < 2; ++o) {
-				const unsigned mm = (unsigned)rdl(od[o][OD_MM], v), dph = (unsigned)rdl(od[o][OD_DPH], v);
-				const unsigned sizem = (unsigned)rdl(od[o][OD_SIZEM], v), doff = (unsigned)rdl(od[o][OD_DOFF], v);
-				amps[o] = rdl(amp_l[o], v);
-				const uint64_t phase = (uint64_t)(unsigned)rdl(phlo_l[o], v) |
-						((uint64_t)(unsigned)rdl(phhi_l[o], v) << 32);
-				uint64_t ph = (phase >> mm) + (uint64_t)before * dph;
-				const unsigned ldph = lane_dph(lane, dph);
-				const int cb = coef_base(doff);
-				uint64_t phs[OSC2_FCH];
-				if(!(sizem & (sizem - 1)) && !(ph >> 48)) {
-					// power-of-two size: the modulus is a mask (as in k_leaf_oscpan)
-					const uint64_t mask = ((uint64_t)sizem << 24) - 1;
-#pragma unroll
-					for(int j = 0; j < OSC2_FCH; ++j)
-						phs[j] = (ph + (uint64_t)dph * pre[j]) & mask;
-					ph = phs[OSC2_FCH - 1] + (uint64_t)dph * (unsigned)nfr[OSC2_FCH - 1];
-				} else {
+		for(int r = 0; r < OSC2_SCH; ++r)
+			tile[r][0][lane] = tile[r][1][lane] = 0;
+	for(int s_lo = c_lo; s_lo < c_hi; s_lo += OSC2_SCH / OSC2_FCH) {
+		const int s_hi = min(c_hi, s_lo + OSC2_SCH / OSC2_FCH);
+		const int fa = s_lo * OSC2_FCH, nfs = min(nfrags, s_hi * OSC2_FCH) - fa;
+		const bool last = last_slice && s_hi == c_hi;
+		const unsigned before = (unsigned)frames_of(fst, fa);	// (frames of the batch before the super-chunk)
+		if(vmajor && a2d_osc2_whole(before, (unsigned)frames_of(fst, fa + nfs - 1), (unsigned)frames_of(ffr, fa + nfs - 1), nfs)) {
+			const int nsc = s_hi - s_lo;
+			const int nopre_i[OSC2_FCH] = { 0, 0, 0, 0 };
+			const unsigned nopre_u[OSC2_FCH] = { 0, 0, 0, 0 };
+			int cur_off = rdl(my_off, 0), cur_nch = rdl(my_nch, 0);
+			for(int v = 0; v < nv; ++v) {
+				if(!rdl(settled_l, v))
+					continue;
+				const int voff = rdl(my_off, v);
+				if(voff != cur_off) {
+					flush_tile(busmem, cur_off, cur_nch, fa, nfs, nsc * OSC2_FCH, lane, dbg, tile);
+					cur_off = voff;
+					cur_nch = rdl(my_nch, v);
+				}
+				const int v0 = rdl(v0l, v), v1 = rdl(v1l, v);
+				Osc2Voice s;
+				unsigned ldph[2], mm[2];
+				osc2_voice_from_lanes(s, ldph, mm, od, amp_l, phlo_l, phhi_l, v, before, lane);
+				for(int k = 0; k < nsc; ++k) {
+					// (a last chunk of fewer than 4 fragments: the rows past the batch's end are computed - from
+					// phases inside the wave - and never flushed)
+					const bool park = last && k == nsc - 1;
+					int xs[OSC2_FCH];
+					osc2_chunk<true>(crs, s, ldph, nopre_i, nopre_u, nfs - k * OSC2_FCH, park, xs);
 #pragma unroll
 					for(int j = 0; j < OSC2_FCH; ++j) {
-						ph = wrap_phase(ph, sizem);
-						phs[j] = ph;
-						ph += (uint64_t)dph * (unsigned)nfr[j];
+						tile_add(&tile[k * OSC2_FCH + j][0][lane], mul64s(xs[j], v0, 24));
+						tile_add(&tile[k * OSC2_FCH + j][1][lane], mul64s(xs[j], v1, 24));
+					}
+					if(park) {
+						const bool me = lane == v;
+#pragma unroll
+						for(int o = 0; o < 2; ++o) {
+							const uint64_t endph = s.end[o] << mm[o];
+							WRL(phlo_l[o], (int)(unsigned)endph);
+							WRL(phhi_l[o], (int)(unsigned)(endph >> 32));
+						}
 					}
 				}
-#pragma unroll
-				for(int j = 0; j < OSC2_FCH; ++j) {
-					pa[o][j] = tap_phase(phs[j], ldph);
-					asm("" : "+v"(pa[o][j]));	// (32 bit offsets: scalar-base loads, as in k_leaf_oscpan)
-					pb[o][j] = pa[o][j] + (dph >> 17);
-					ka[o][j] = coef_at(crs, cb, pa[o][j]);
-					kb[o][j] = coef_at(crs, cb, pb[o][j]);
-				}
-				endph[o] = ph << mm;
 			}
-#pragma unroll
-			for(int o = 0; o < 2; ++o)
-#pragma unroll
-				for(int j = 0; j < OSC2_FCH; ++j) {
-					const int y = mul64s(inter_coefs(ka[o][j], pa[o][j], kb[o][j], pb[o][j]), amps[o], 17);
-					// the second oscillator adds into the scratch buffer (wrap-around)
-					xs[j] = o ? wadd(xs[j], y) : y;
-				}
+			flush_tile(busmem, cur_off, cur_nch, fa, nfs, nsc * OSC2_FCH, lane, dbg, tile);
+			continue;
+		}
+		for(int c = s_lo; c < s_hi; ++c) {
+			const int f0 = c * OSC2_FCH;
+			const int nf = min((int)OSC2_FCH, nfrags - f0);
+			int acc0[OSC2_FCH], acc1[OSC2_FCH], nfr[OSC2_FCH];
 #pragma unroll
 			for(int j = 0; j < OSC2_FCH; ++j) {
-				const int x = (lane < nfr[j]) ? xs[j] : 0;
-				acc0[j] = wadd(acc0[j], mul64s(x, v0, 24));
-				acc1[j] = wadd(acc1[j], mul64s(x, v1, 24));
+				acc0[j] = acc1[j] = 0;
+				nfr[j] = (j < nf) ? frames_of(ffr, f0 + j) : 0;
 			}
-			if(last_slice && c == c_hi - 1) {
-				const bool me = lane == v;
+			const unsigned before = (unsigned)frames_of(fst, f0);
+			unsigned pre[OSC2_FCH];		// frames from the start of the chunk to each fragment
+			pre[0] = 0;
 #pragma unroll
-				for(int o = 0; o < 2; ++o) {
-					WRL(phlo_l[o], (int)(unsigned)endph[o]);
-					WRL(phhi_l[o], (int)(unsigned)(endph[o] >> 32));
+			for(int j = 1; j < OSC2_FCH; ++j)
+				pre[j] = pre[j - 1] + (unsigned)nfr[j - 1];
+			const bool park = last && c == s_hi - 1;
+			int cur_off = rdl(my_off, 0), cur_nch = rdl(my_nch, 0);
+			for(int v = 0; v < nv; ++v) {
+				if(!rdl(settled_l, v))
+					continue;
+				const int voff = rdl(my_off, v);
+				if(voff != cur_off) {
+					flush_acc(busmem, cur_off, cur_nch, f0, nf, lane, dbg, acc0, acc1);
+					cur_off = voff;
+					cur_nch = rdl(my_nch, v);
+				}
+				const int v0 = rdl(v0l, v), v1 = rdl(v1l, v);
+				Osc2Voice s;
+				unsigned ldph[2], mm[2];
+				int xs[OSC2_FCH];
+				osc2_voice_from_lanes(s, ldph, mm, od, amp_l, phlo_l, phhi_l, v, before, lane);
+				osc2_chunk<false>(crs, s, ldph, nfr, pre, nf, park, xs);
+#pragma unroll
+				for(int j = 0; j < OSC2_FCH; ++j) {
+					const int x = (lane < nfr[j]) ? xs[j] : 0;
+					acc0[j] = wadd(acc0[j], mul64s(x, v0, 24));
+					acc1[j] = wadd(acc1[j], mul64s(x, v1, 24));
+				}
+				if(park) {
+					const bool me = lane == v;
+#pragma unroll
+					for(int o = 0; o < 2; ++o) {
+						const uint64_t endph = s.end[o] << mm[o];
+						WRL(phlo_l[o], (int)(unsigned)endph);
+						WRL(phhi_l[o], (int)(unsigned)(endph >> 32));
+					}
 				}
 			}
+			flush_acc(busmem, cur_off, cur_nch, f0, nf, lane, dbg, acc0, acc1);
 		}
-		flush_acc(busmem, cur_off, cur_nch, f0, nf, lane, dbg, acc0, acc1);
 	}
 
 	// ---- voices with something still moving: one slice each walks the whole batch ----
@@ -3188,18 +3290,20 @@ int a2d_launch_leaf_oscpan(const A2DParams *dparams, const A2DParams &hp, const 
 }
 
 int a2d_launch_leaf_osc2pan(const A2DParams *dparams, const A2DParams &hp, const int *dlist, int nlist,
-		int vpw, int ysplit, int *ustage, unsigned char *staged, void *stream, A2DCommit *defer)
+		int vpw, int ysplit, int *ustage, unsigned char *staged, void *stream, A2DCommit *defer, int voice_major, int *ysplit_used)
 {
 	if(nlist <= 0)
 		return 0;
 	vpw = vpw < 1 ? 1 : (vpw > 64 ? 64 : vpw);
 	if(ysplit < 1 || !ustage || !staged)
 		ysplit = 1;
+	if(ysplit_used)
+		*ysplit_used = ysplit;
 	int nwaves = (nlist + vpw - 1) / vpw;
 	int nblocks = (nwaves + FAST_WPB - 1) / FAST_WPB;
 	hipLaunchKernelGGL(k_leaf_osc2pan, dim3(nblocks, ysplit), dim3(64 * FAST_WPB), 0, (hipStream_t)stream,
 			dparams, dlist, nlist, vpw, ysplit, hp.voices, (const int *)hp.ustate,
-			ysplit > 1 ? ustage : hp.ustate, hp.wavepool, hp.waves, hp.ptab, hp.busmem, hp.wavecoef, staged);
+			ysplit > 1 ? ustage : hp.ustate, hp.wavepool, hp.waves, hp.ptab, hp.busmem, hp.wavecoef, staged, voice_major);
 	if(ysplit > 1) {
 		A2DCommit cm = { dlist, nlist, 2, ustage, staged };
 		if(defer)

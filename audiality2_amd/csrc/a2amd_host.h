@@ -537,6 +537,7 @@ struct a2amd_ctx {
 	// batches that take upload()'s quiet path, which are the last full one again - and the mono owners on k_bus_driver's lists
 	uint32_t n_bare_quiet = 0, n_bare_gliding = 0, n_bare_records = 0, n_mono_drivers = 0;
 	a2amd_bare_batch_info last_bare = {};	// a2amd_last_batch_bare()
+	a2amd_osc2_batch_info last_osc2 = {};	// a2amd_last_batch_osc2(): the launch; the walks are counted when asked for
 	a2amd_fbdpan_batch_info last_fbdpan = {};	// a2amd_last_batch_fbdpan(): upload() counts, launch_depth() sets launched
 	a2amd_bus_windows_info last_buswin = {};	// a2amd_last_batch_bus_windows(): likewise, reset by every upload()
 	// a2amd_last_batch_buses(): upload() fills in who renders the bus owners, launch_depth() what it was told to

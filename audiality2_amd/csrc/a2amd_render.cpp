@@ -498,6 +498,39 @@ int a2amd_last_batch_bare(const a2amd_ctx *c, a2amd_bare_batch_info *out)
 	return A2AMD_OK;
 }
 
+int a2amd_last_batch_osc2(const a2amd_ctx *c, a2amd_osc2_batch_info *out)
+{
+	if(!c || !out)
+		return A2AMD_EINVAL;
+	*out = c->last_osc2;
+	if(!out->launched || c->blob_nfrags < 1 || c->blob_nfrags > A2D_MAXBATCH)
+		return A2AMD_OK;
+	// the kernel's walk over the fragment table the batch took up (blob_frames: a replayed graph reads the same table)
+	unsigned start[A2D_MAXBATCH];
+	for(int f = 0, acc = 0; f < c->blob_nfrags; ++f) {
+		start[f] = (unsigned)acc;
+		acc += (int)c->blob_frames[f];
+	}
+	unsigned n = 0;
+	for(int slice = 0; slice < (int)out->ysplit; ++slice) {
+		int c_lo, c_hi, nslices;
+		if(!a2d_osc2_slice(c->blob_nfrags, (int)out->ysplit, slice, &c_lo, &c_hi, &nslices))
+			break;
+		for(int s_lo = c_lo; s_lo < c_hi; s_lo += A2D_OSC2_SCH / A2D_OSC2_FCH, ++n) {
+			const int s_hi = std::min(c_hi, s_lo + A2D_OSC2_SCH / A2D_OSC2_FCH);
+			const int fa = s_lo * A2D_OSC2_FCH, fb = std::min(c->blob_nfrags, s_hi * A2D_OSC2_FCH);
+			if(out->voice_major && a2d_osc2_whole(start[fa], start[fb - 1], c->blob_frames[fb - 1], fb - fa))
+				++out->superchunks_voice_major;
+			else {
+				++out->superchunks_chunk_major;
+				if(n < 64)
+					out->chunk_major_mask |= 1ull << n;
+			}
+		}
+	}
+	return A2AMD_OK;
+}
+
 int a2amd_last_batch_fbdpan(const a2amd_ctx *c, a2amd_fbdpan_batch_info *out)
 {
 	if(!c || !out)

@@ -1847,9 +1847,17 @@ static int launch_leaves(a2amd_ctx *c, LeafPass &lp)
 		int vpw, ysplit;
 		// (its own chunk length; 16 time slices: 2.19 ms against 2.25 with 32 at configs[3], round 3)
 		pick_fast_shape(c->sw, osc2pan.count, c->nfrags * A2D_FAST_FCH / A2D_OSC2_FCH, &vpw, &ysplit, 16);
+		// (A2AMD_DEBUG bit 16: no voice-major walk, every super-chunk chunk by chunk - A/B and tests)
+		const int voice_major = !(c->sw.debug & 16);
 		if(a2d_launch_leaf_osc2pan(c->d_params, c->hparams, list + osc2pan.first, osc2pan.count,
-				vpw, ysplit, c->d_ustage.d, c->d_staged.d + osc2pan.first, c->stream, &pend.c[pend.n]))
+				vpw, ysplit, c->d_ustage.d, c->d_staged.d + osc2pan.first, c->stream, &pend.c[pend.n], voice_major, &ysplit))
 			return c->fail(A2AMD_EHIP, "2-osc leaf launch failed: %s", hipGetErrorString(hipGetLastError()));
+		// (a2amd_last_batch_osc2(): the launch as it went out; the walks follow from it and the batch's fragment lengths)
+		c->last_osc2.launched = 1;
+		c->last_osc2.voices = (uint32_t)osc2pan.count;
+		c->last_osc2.vpw = (uint32_t)std::min(std::max(vpw, 1), 64);
+		c->last_osc2.ysplit = (uint32_t)ysplit;
+		c->last_osc2.voice_major = (uint32_t)voice_major;
 		if(pend.c[pend.n].nlist)
 			++pend.n;
 		++c->stats.launches;
@@ -2026,6 +2034,7 @@ static int issue_leaf_phase(a2amd_ctx *c, bool consume, bool consume_sub, hipEve
 	c->last_bare.gliding_voices = c->n_bare_gliding;
 	c->last_bare.record_voices = c->n_bare_records;
 	c->last_bare.mono_drivers = c->n_mono_drivers;
+	c->last_osc2 = a2amd_osc2_batch_info{};
 	// The batch's other leaf kernels - the quiet kernels of the classes, the records kernels where the window kernels
 	// are not in use, the general kernel - as a block that runs once: normally behind the window kernels, and
 	// (round 6) from INSIDE issue_windows, between its control passes and its render passes, when a speculative VM

@@ -217,3 +217,28 @@ DEV void flush_acc(int *busmem, int off, int nch, int f0, int nf, int lane, int 
 	}
 }
 
+// The same sums kept in LDS, [fragment][channel][lane] (k_leaf_osc2pan's voice-major walk: sums for more fragments
+// than registers hold).  A lane adds into its own words only, so the adds are free of conflicts, need no order among
+// the lanes, and their result is not used: ds_add_u32 at an immediate offset from the lane's word, off the vector ALU.
+DEV void tile_add(int *w, int x)
+{
+	(void)__hip_atomic_fetch_add(w, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+}
+
+// ... and their flush_acc(): the first nf of the tile's nrows used rows go to the bus, all nrows are cleared
+DEV void flush_tile(int *busmem, int off, int nch, int f0, int nf, int nrows, int lane, int dbg, int (*tile)[2][A2D_FRAG])
+{
+	for(int r = 0; r < nrows; ++r) {
+		const int a0 = tile[r][0][lane], a1 = tile[r][1][lane];
+		tile[r][0][lane] = 0;
+		tile[r][1][lane] = 0;
+		if(r < nf && off >= 0 && !(dbg & 1)) {
+			int *dst = busmem + off + (size_t)(f0 + r) * nch * A2D_FRAG;
+			if(a0)
+				atomicAdd(&dst[lane], a0);
+			if(a1)
+				atomicAdd(&dst[A2D_FRAG + lane], a1);
+		}
+	}
+}
+

@@ -126,6 +126,15 @@ class a2amd_bare_batch_info(C.Structure):
         return "bare_batch_info(" + ", ".join(f"{n}={getattr(self, n)}" for n, _ in self._fields_) + ")"
 
 
+class a2amd_osc2_batch_info(C.Structure):
+    """include/a2amd_osc2.h: how k_leaf_osc2pan walked the settled voices of the most recent batch"""
+    _fields_ = [(n, C.c_uint32) for n in ("launched", "voices", "vpw", "ysplit", "voice_major", "superchunks_voice_major",
+                                          "superchunks_chunk_major", "reserved")] + [("chunk_major_mask", C.c_uint64)]
+
+    def __repr__(self):
+        return "osc2_batch_info(" + ", ".join(f"{n}={getattr(self, n)}" for n, _ in self._fields_) + ")"
+
+
 class a2amd_fbdpan_batch_info(C.Structure):
     """include/a2amd_fbdpan.h: who rendered the pan-tailed delay chains (inline; fbdelay x 1..4; panmix >) of the most recent batch"""
     _fields_ = [(n, C.c_uint32) for n in ("launched", "class_voices", "quiet_voices", "gliding_voices", "record_voices",
@@ -221,6 +230,9 @@ class Backend:
         self._last_batch_bare = None
         if hasattr(lib, prefix + "last_batch_bare"):
             self._last_batch_bare = fn("last_batch_bare", i32, vp, C.POINTER(a2amd_bare_batch_info))
+        self._last_batch_osc2 = None
+        if hasattr(lib, prefix + "last_batch_osc2"):
+            self._last_batch_osc2 = fn("last_batch_osc2", i32, vp, C.POINTER(a2amd_osc2_batch_info))
         self._last_batch_fbdpan = None
         if hasattr(lib, prefix + "last_batch_fbdpan"):
             self._last_batch_fbdpan = fn("last_batch_fbdpan", i32, vp, C.POINTER(a2amd_fbdpan_batch_info))
@@ -384,6 +396,16 @@ class Backend:
             raise RuntimeError(f"this library has no {self.prefix}last_batch_bare")
         bi = a2amd_bare_batch_info()
         self._chk(self._last_batch_bare(self.ctx, C.byref(bi)), "last_batch_bare")
+        return bi
+
+    def last_batch_osc2(self):
+        """a2amd_last_batch_osc2: whether k_leaf_osc2pan was launched for the most recent batch, the voices on its list,
+        its launch shape, and the super-chunks of the batch by the walk their settled voices took - voice by voice
+        (whole fragments only) or chunk by chunk (a short fragment among them, or A2AMD_DEBUG bit 16)"""
+        if self._last_batch_osc2 is None:
+            raise RuntimeError(f"this library has no {self.prefix}last_batch_osc2")
+        bi = a2amd_osc2_batch_info()
+        self._chk(self._last_batch_osc2(self.ctx, C.byref(bi)), "last_batch_osc2")
         return bi
 
     def last_batch_fbdpan(self):

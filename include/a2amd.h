@@ -461,5 +461,7 @@ int  a2amd_last_batch(const a2amd_ctx *ctx, a2amd_batch_info *bi);
 #include "a2amd_buswin.h"
 /* Who ran the device VM's voices (a2amd_vm.h) of the most recent batch: a2amd_last_batch_vm(). */
 #include "a2amd_vmbatch.h"
+/* How k_leaf_osc2pan walked its settled voices in the most recent batch, voice by voice or chunk by chunk: a2amd_last_batch_osc2(). */
+#include "a2amd_osc2.h"
 
 #endif /* A2AMD_H */
