@@ -86,7 +86,8 @@ struct A2DWave {
 	uint32_t period;
 	uint32_t size[A2D_MIPS];
 	uint32_t off[A2D_MIPS];
-	uint32_t pad;
+	uint32_t periodic;	// bit l: level l's pads are the periodic continuation of its payload (a2amd_wavepads.h; set by
+				// a2amd_wave_upload from the samples it is handed, clear for the waves the device renders)
 };
 
 // one voice = one unit chain (host owned)
@@ -194,6 +195,7 @@ enum { XW_SLOT = 0, XW_MODE = 1 };
 #define A2D_FAST_FCH 8	// k_leaf_oscpan: fragments per chunk (the host sizes the time slices by it)
 #define A2D_OSC2_FCH 4	// k_leaf_osc2pan: fragments per chunk
 #define A2D_OSC2_SCH 16	// ... and per super-chunk (a multiple of the chunk): what a wavefront keeps bus sums for in LDS
+#define A2D_OSC2_LDS_ENT 128	// ... and coefficient entries a wavefront may keep in LDS for the voice it walks (1 536 bytes)
 #define A2D_MAXVPW   32       // voices one wavefront may walk per fragment
 
 struct A2DParams {
@@ -252,6 +254,17 @@ A2D_HD bool a2d_osc2_slice(int nfrags, int ysplit, int slice, int *c_lo, int *c_
 A2D_HD bool a2d_osc2_whole(unsigned start_first, unsigned start_last, unsigned frames_last, int n)
 {
 	return start_last + frames_last - start_first == (unsigned)n * A2D_FRAG;
+}
+
+// Which of a settled voice's two oscillators read their taps from the wavefront's copy of the level in LDS on the
+// voice-major walk: bit o = oscillator o.  A level is a candidate when its pads are periodic (A2DWave::periodic), so that
+// its payload entries indexed modulo the size are all a tap can reach (a2amd_wavepads.h), the size is a power of two -
+// the modulus is a bit field - and at most A2D_OSC2_LDS_ENT.  Oscillator 0 first, then oscillator 1 if both still fit.
+A2D_HD unsigned a2d_osc2_stage(unsigned size0, unsigned periodic0, unsigned size1, unsigned periodic1)
+{
+	const bool c0 = periodic0 && size0 && !(size0 & (size0 - 1)) && size0 <= A2D_OSC2_LDS_ENT;
+	const bool c1 = periodic1 && size1 && !(size1 & (size1 - 1)) && size1 <= A2D_OSC2_LDS_ENT;
+	return (c0 ? 1u : 0u) | (c1 && (c0 ? size0 : 0u) + size1 <= A2D_OSC2_LDS_ENT ? 2u : 0u);
 }
 
 // A noise oscillator's default window - a fragment without records for its voice - takes the engine's RNG word from
@@ -426,7 +439,8 @@ int a2d_launch_leaf_oscfiltpan(const A2DParams *dparams, const A2DParams &hp, co
 // runs[idx[i]] = val[i] for the few voices whose record run changed this batch
 int a2d_launch_scatter_runs(const int *didx, const A2DRun *dval, int n, A2DRun *druns, void *stream);
 int a2d_launch_leaf_osc2pan(const A2DParams *dparams, const A2DParams &hp, const int *dlist, int nlist,
-		int vpw, int ysplit, int *ustage, unsigned char *staged, void *stream, A2DCommit *defer, int voice_major, int *ysplit_used);
+		int vpw, int ysplit, int *ustage, unsigned char *staged, void *stream, A2DCommit *defer, int voice_major, int lds_taps,
+		int *ysplit_used);
 // wtosc[+wtosc] [-> filter12] -> panmix voices that carry records this batch (nosc = 1 | 2, filt = 0 | 1)
 // skip_empty: the list's voices get their records from the device VM (a2amd_vm.hip); those it left
 // without any this batch are rendered by their class's quiet kernel

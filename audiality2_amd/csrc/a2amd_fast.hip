@@ -308,7 +308,8 @@ enum { DV_SETTLED = 0, DV_MM, DV_DPH, DV_SIZEM, DV_DOFF, DV_V0, DV_V1, DV_NWORDS
 // The four words DV_MM .. DV_DOFF (k_leaf_osc2pan's OD_MM .. OD_DOFF) of an oscillator at a constant pitch on wave w:
 // mip level, increment there, that level's size and place in the pool.  False: no wave for the settled paths - or
 // 'settled' was false already, and then the descriptor's test words are not read (k_leaf_osc2pan's second oscillator).
-DEV bool settled_wave(const A2DWave *w, unsigned dphase, int *d, bool settled = true)
+// periodic: A2DWave::periodic's bit of that level (k_leaf_osc2pan: may the level be copied to LDS)
+DEV bool settled_wave(const A2DWave *w, unsigned dphase, int *d, bool settled = true, unsigned *periodic = nullptr)
 {
 	unsigned dph;
 	const unsigned mm = a2s_mip(dphase, w->period, &dph);
@@ -316,6 +317,8 @@ DEV bool settled_wave(const A2DWave *w, unsigned dphase, int *d, bool settled = 
 	d[1] = (int)dph;
 	d[2] = (int)w->size[mm];
 	d[3] = (int)w->off[mm];
+	if(periodic)
+		*periodic = (w->periodic >> mm) & 1u;
 	return settled && a2s_wave_ok(w->size[0], w->flags, dph);
 }
 
@@ -736,15 +739,21 @@ DEV void osc_to_lanes(int (&so)[OV_NWORDS], const OscS &o, bool me)
 // In: ph = the phase, at the level, at the chunk's first frame, wrapped or not.  Out: xs = the samples in the scratch
 // buffer, ph = the phase behind the chunk's fourth fragment, and for park (wave-uniform) end = the unwrapped end phase
 // of the last of the chunk's nf real fragments, wtosc.c:284: its wrapped start plus its frames x the increment.
+// ST: a2d_osc2_stage()'s mask - oscillator o with its bit set reads its entries from the wavefront's copy of the level
+// in LDS, lv.level[o] (1 << lv.lg[o] entries), the other from the table (lv is not read where ST is 0).
 struct Osc2Voice {
 	unsigned dph[2], sizem[2];
 	int cb[2], amp[2];
 	uint64_t ph[2], end[2];
 };
+struct Osc2Lds {
+	const LdsInt *level[2];
+	unsigned lg[2];
+};
 
-template<bool WHOLE>
+template<bool WHOLE, int ST = 0>
 DEV void osc2_chunk(const CoefRsrc &crs, Osc2Voice &s, const unsigned (&ldph)[2], const int (&nfr)[OSC2_FCH],
-		const unsigned (&pre)[OSC2_FCH], int nf, bool park, int (&xs)[OSC2_FCH])
+		const unsigned (&pre)[OSC2_FCH], int nf, bool park, int (&xs)[OSC2_FCH], const Osc2Lds &lv = Osc2Lds())
 {
 	// the coefficient entries of BOTH oscillators (4 fragments x 2 taps x 2: 48 registers) are in
 	// flight before either is used (one oscillator after the other, 24 registers in flight at a
@@ -776,8 +785,13 @@ DEV void osc2_chunk(const CoefRsrc &crs, Osc2Voice &s, const unsigned (&ldph)[2]
 			pa[o][j] = tap_phase(phs[j], ldph[o]);
 			asm("" : "+v"(pa[o][j]));	// (32 bit offsets: scalar-base loads, as in k_leaf_oscpan)
 			pb[o][j] = pa[o][j] + (dph >> 17);
-			ka[o][j] = coef_at(crs, s.cb[o], pa[o][j]);
-			kb[o][j] = coef_at(crs, s.cb[o], pb[o][j]);
+			if((ST >> o) & 1) {
+				ka[o][j] = coef_lds(lv.level[o], pa[o][j], lv.lg[o]);
+				kb[o][j] = coef_lds(lv.level[o], pb[o][j], lv.lg[o]);
+			} else {
+				ka[o][j] = coef_at(crs, s.cb[o], pa[o][j]);
+				kb[o][j] = coef_at(crs, s.cb[o], pb[o][j]);
+			}
 		}
 		if(park) {
 			uint64_t e = ph;	// (a full chunk: behind its fourth fragment)
@@ -817,6 +831,94 @@ DEV void osc2_voice_from_lanes(Osc2Voice &s, unsigned (&ldph)[2], unsigned (&mm)
 	}
 }
 
+// One settled voice over a super-chunk of nsc chunks - nfs whole fragments - on the voice-major walk: its samples into
+// the wavefront's tile, and behind the batch's last chunk (last) its end phases back into lane v.
+template<int ST>
+DEV void osc2_voice_chunks(const CoefRsrc &crs, Osc2Voice &s, const unsigned (&ldph)[2], const unsigned (&mm)[2],
+		const Osc2Lds &lv, int nsc, int nfs, bool last, int v0, int v1, int v, int lane, int (*tile)[2][A2D_FRAG],
+		int (&phlo_l)[2], int (&phhi_l)[2])
+{
+	const int nopre_i[OSC2_FCH] = { 0, 0, 0, 0 };
+	const unsigned nopre_u[OSC2_FCH] = { 0, 0, 0, 0 };
+	for(int k = 0; k < nsc; ++k) {
+		// (a last chunk of fewer than 4 fragments: the rows past the batch's end are computed - from
+		// phases inside the wave - and never flushed)
+		const bool park = last && k == nsc - 1;
+		int xs[OSC2_FCH];
+		osc2_chunk<true, ST>(crs, s, ldph, nopre_i, nopre_u, nfs - k * OSC2_FCH, park, xs, lv);
+#pragma unroll
+		for(int j = 0; j < OSC2_FCH; ++j) {
+			tile_add(&tile[k * OSC2_FCH + j][0][lane], mul64s(xs[j], v0, 24));
+			tile_add(&tile[k * OSC2_FCH + j][1][lane], mul64s(xs[j], v1, 24));
+		}
+		if(park) {
+			const bool me = lane == v;
+#pragma unroll
+			for(int o = 0; o < 2; ++o) {
+				const uint64_t endph = s.end[o] << mm[o];
+				WRL(phlo_l[o], (int)(unsigned)endph);
+				WRL(phhi_l[o], (int)(unsigned)(endph >> 32));
+			}
+		}
+	}
+}
+
+// A super-chunk of nsc chunks - nfs whole fragments from fragment fa on - walked voice by voice: every settled voice of
+// the wavefront's nv in turn, the tile flushed where the bus changes and at the end.  STAGE: voices may have levels to
+// copy to LDS (the mask rides in settled_l above the settled bit); without it every voice takes the gathers' body.
+template<bool STAGE>
+DEV void osc2_superchunk(const CoefRsrc &crs, const int *wavecoef, int *busmem, const int (&od)[2][OD_NWORDS],
+		const int (&amp_l)[2], int (&phlo_l)[2], int (&phhi_l)[2], int settled_l, int my_off, int my_nch, int v0l, int v1l,
+		int nv, int nsc, int fa, int nfs, bool last, unsigned before, int lane, int dbg, int (*tile)[2][A2D_FRAG],
+		LdsInt *level)
+{
+	int cur_off = rdl(my_off, 0), cur_nch = rdl(my_nch, 0);
+	for(int v = 0; v < nv; ++v) {
+		const int sl = rdl(settled_l, v);
+		if(!sl)
+			continue;
+		const int voff = rdl(my_off, v);
+		if(voff != cur_off) {
+			flush_tile(busmem, cur_off, cur_nch, fa, nfs, nsc * OSC2_FCH, lane, dbg, tile);
+			cur_off = voff;
+			cur_nch = rdl(my_nch, v);
+		}
+		const int v0 = rdl(v0l, v), v1 = rdl(v1l, v);
+		Osc2Voice s;
+		unsigned ldph[2], mm[2];
+		osc2_voice_from_lanes(s, ldph, mm, od, amp_l, phlo_l, phhi_l, v, before, lane);
+		Osc2Lds lv = { { level, level }, { 0, 0 } };
+		if(!STAGE) {
+			osc2_voice_chunks<0>(crs, s, ldph, mm, lv, nsc, nfs, last, v0, v1, v, lane, tile, phlo_l, phhi_l);
+			continue;
+		}
+		// the voice's staged levels, oscillator 1 behind oscillator 0: lanes read what other lanes wrote, and
+		// write where other lanes read for the voice before - a wavefront fence on both sides of the stores
+		const int st = sl >> 1;
+		if(st) {
+			lds_wave_fence();
+			if(st & 1) {
+				lv.lg[0] = (unsigned)__builtin_ctz(s.sizem[0]);
+				stage_level(level, wavecoef, s.cb[0], s.sizem[0], lane);
+			}
+			if(st & 2) {
+				LdsInt *const l1 = (st & 1) ? level + s.sizem[0] * A2D_COEF_WORDS : level;
+				lv.level[1] = l1;
+				lv.lg[1] = (unsigned)__builtin_ctz(s.sizem[1]);
+				stage_level(l1, wavecoef, s.cb[1], s.sizem[1], lane);
+			}
+			lds_wave_fence();
+		}
+		switch(st) {
+		case 0: osc2_voice_chunks<0>(crs, s, ldph, mm, lv, nsc, nfs, last, v0, v1, v, lane, tile, phlo_l, phhi_l); break;
+		case 1: osc2_voice_chunks<1>(crs, s, ldph, mm, lv, nsc, nfs, last, v0, v1, v, lane, tile, phlo_l, phhi_l); break;
+		case 2: osc2_voice_chunks<2>(crs, s, ldph, mm, lv, nsc, nfs, last, v0, v1, v, lane, tile, phlo_l, phhi_l); break;
+		default: osc2_voice_chunks<3>(crs, s, ldph, mm, lv, nsc, nfs, last, v0, v1, v, lane, tile, phlo_l, phhi_l); break;
+		}
+	}
+	flush_tile(busmem, cur_off, cur_nch, fa, nfs, nsc * OSC2_FCH, lane, dbg, tile);
+}
+
 #define OSC2_WPE 4	// (round 2: 3 wavefronts per SIMD with 143 registers and no spills beat 4 with 128 and 39 spills by a
 			// fifth.  Round 3: with only the settled loop's values parked in registers the kernel needs 118 -
 			// 4 wavefronts without spills: 2.30 -> 2.24 ms at configs[3]; 3 wavefronts of the same code: 2.40)
@@ -825,7 +927,7 @@ void k_leaf_osc2pan(const A2DParams *__restrict__ pp, const int *__restrict__ li
 		int ysplit, const A2DVoice *__restrict__ voices, const int *ustate, int *ustage,
 		const int16_t *__restrict__ wavepool, const A2DWave *__restrict__ waves,
 		const uint32_t *__restrict__ ptab, int *__restrict__ busmem, const int *__restrict__ wavecoef,
-		unsigned char *__restrict__ staged, int vmajor)
+		unsigned char *__restrict__ staged, int vmajor, int lds_taps)
 {
 	const A2DParams &p = *pp;
 	const int wv = rfl((int)(threadIdx.x >> 6));	// (wave-uniform, and known to the compiler as such)
@@ -875,6 +977,7 @@ void k_leaf_osc2pan(const A2DParams *__restrict__ pp, const int *__restrict__ li
 		my_nch = vc.out_nch;
 		bool settled = true;
 		int wave_l[2], dphase_l[2];
+		unsigned periodic[2] = { 0, 0 };
 #pragma unroll
 		for(int o = 0; o < 2; ++o) {
 			uu[o] = vc.unit[o];
@@ -896,12 +999,16 @@ void k_leaf_osc2pan(const A2DParams *__restrict__ pp, const int *__restrict__ li
 		if(settled) {
 #pragma unroll
 			for(int o = 0; o < 2; ++o)
-				settled = settled_wave(waves + wave_l[o], (unsigned)dphase_l[o], od[o], settled);
+				settled = settled_wave(waves + wave_l[o], (unsigned)dphase_l[o], od[o], settled, &periodic[o]);
 			a2s_pan_gains(sp[PW_VOL], sp[PW_PAN], a2s_pan_over(sp[PW_PAN]), &v0l, &v1l);
 		}
+		// (bit 0: settled; bits 1 and 2: which of its oscillators the voice-major walk reads from LDS)
 		settled_l = settled ? 1 : 0;
+		if(settled && lds_taps)
+			settled_l |= (int)a2d_osc2_stage((unsigned)od[0][OD_SIZEM], periodic[0], (unsigned)od[1][OD_SIZEM], periodic[1]) << 1;
 	}
 	const unsigned long long unsettled_mask = __ballot(mine && !settled_l);
+	const bool any_staged = __ballot(settled_l > 1) != 0;
 
 	// ---- settled voices: this slice, in super-chunks of up to OSC2_SCH fragments ----
 	// One of whole fragments only (a2d_osc2_whole) is walked voice by voice: a voice's constants leave their lanes
@@ -909,8 +1016,13 @@ void k_leaf_osc2pan(const A2DParams *__restrict__ pp, const int *__restrict__ li
 	// bus sums of the super-chunk's fragments - more than registers hold - are this wavefront's tile in LDS.  One
 	// with a short fragment (a cut window), and every one with vmajor off (A2AMD_DEBUG bit 16), is walked chunk by
 	// chunk with the sums in registers.
+	// On the voice-major walk a voice's small mip levels (a2d_osc2_stage: periodic pads, a power of two of at most
+	// A2D_OSC2_LDS_ENT entries together) are copied to this wavefront's own 1 536 bytes of LDS first, and their taps read
+	// there instead of gathered through the texture addressers (lds_taps off - A2AMD_DEBUG bit 17 - no voice has the bits).
 	__shared__ int tiles[FAST_WPB][OSC2_SCH][2][A2D_FRAG];
+	__shared__ int levels[FAST_WPB][A2D_OSC2_LDS_ENT * A2D_COEF_WORDS];
 	int (*const tile)[2][A2D_FRAG] = tiles[wv];
+	LdsInt *const level = (LdsInt *)levels[wv];
 	if(vmajor)
 #pragma unroll
 		for(int r = 0; r < OSC2_SCH; ++r)
@@ -921,46 +1033,15 @@ void k_leaf_osc2pan(const A2DParams *__restrict__ pp, const int *__restrict__ li
 		const bool last = last_slice && s_hi == c_hi;
 		const unsigned before = (unsigned)frames_of(fst, fa);	// (frames of the batch before the super-chunk)
 		if(vmajor && a2d_osc2_whole(before, (unsigned)frames_of(fst, fa + nfs - 1), (unsigned)frames_of(ffr, fa + nfs - 1), nfs)) {
-			const int nsc = s_hi - s_lo;
-			const int nopre_i[OSC2_FCH] = { 0, 0, 0, 0 };
-			const unsigned nopre_u[OSC2_FCH] = { 0, 0, 0, 0 };
-			int cur_off = rdl(my_off, 0), cur_nch = rdl(my_nch, 0);
-			for(int v = 0; v < nv; ++v) {
-				if(!rdl(settled_l, v))
-					continue;
-				const int voff = rdl(my_off, v);
-				if(voff != cur_off) {
-					flush_tile(busmem, cur_off, cur_nch, fa, nfs, nsc * OSC2_FCH, lane, dbg, tile);
-					cur_off = voff;
-					cur_nch = rdl(my_nch, v);
-				}
-				const int v0 = rdl(v0l, v), v1 = rdl(v1l, v);
-				Osc2Voice s;
-				unsigned ldph[2], mm[2];
-				osc2_voice_from_lanes(s, ldph, mm, od, amp_l, phlo_l, phhi_l, v, before, lane);
-				for(int k = 0; k < nsc; ++k) {
-					// (a last chunk of fewer than 4 fragments: the rows past the batch's end are computed - from
-					// phases inside the wave - and never flushed)
-					const bool park = last && k == nsc - 1;
-					int xs[OSC2_FCH];
-					osc2_chunk<true>(crs, s, ldph, nopre_i, nopre_u, nfs - k * OSC2_FCH, park, xs);
-#pragma unroll
-					for(int j = 0; j < OSC2_FCH; ++j) {
-						tile_add(&tile[k * OSC2_FCH + j][0][lane], mul64s(xs[j], v0, 24));
-						tile_add(&tile[k * OSC2_FCH + j][1][lane], mul64s(xs[j], v1, 24));
-					}
-					if(park) {
-						const bool me = lane == v;
-#pragma unroll
-						for(int o = 0; o < 2; ++o) {
-							const uint64_t endph = s.end[o] << mm[o];
-							WRL(phlo_l[o], (int)(unsigned)endph);
-							WRL(phhi_l[o], (int)(unsigned)(endph >> 32));
-						}
-					}
-				}
-			}
-			flush_tile(busmem, cur_off, cur_nch, fa, nfs, nsc * OSC2_FCH, lane, dbg, tile);
+			// (a wavefront none of whose voices stages a level - every one under A2AMD_DEBUG bit 17 - walks them through the
+			// loop without the staging and the choice of a body per voice: those cost some 30 scalar instructions and 6
+			// branches a voice and super-chunk, 1 % of the kernel's time, profiles/osc2_lds_taps.md)
+			if(any_staged)
+				osc2_superchunk<true>(crs, wavecoef, busmem, od, amp_l, phlo_l, phhi_l, settled_l, my_off, my_nch, v0l, v1l,
+						nv, s_hi - s_lo, fa, nfs, last, before, lane, dbg, tile, level);
+			else
+				osc2_superchunk<false>(crs, wavecoef, busmem, od, amp_l, phlo_l, phhi_l, settled_l, my_off, my_nch, v0l, v1l,
+						nv, s_hi - s_lo, fa, nfs, last, before, lane, dbg, tile, level);
 			continue;
 		}
 		for(int c = s_lo; c < s_hi; ++c) {
@@ -3290,7 +3371,8 @@ int a2d_launch_leaf_oscpan(const A2DParams *dparams, const A2DParams &hp, const 
 }
 
 int a2d_launch_leaf_osc2pan(const A2DParams *dparams, const A2DParams &hp, const int *dlist, int nlist,
-		int vpw, int ysplit, int *ustage, unsigned char *staged, void *stream, A2DCommit *defer, int voice_major, int *ysplit_used)
+		int vpw, int ysplit, int *ustage, unsigned char *staged, void *stream, A2DCommit *defer, int voice_major, int lds_taps,
+		int *ysplit_used)
 {
 	if(nlist <= 0)
 		return 0;
@@ -3303,7 +3385,7 @@ int a2d_launch_leaf_osc2pan(const A2DParams *dparams, const A2DParams &hp, const
 	int nblocks = (nwaves + FAST_WPB - 1) / FAST_WPB;
 	hipLaunchKernelGGL(k_leaf_osc2pan, dim3(nblocks, ysplit), dim3(64 * FAST_WPB), 0, (hipStream_t)stream,
 			dparams, dlist, nlist, vpw, ysplit, hp.voices, (const int *)hp.ustate,
-			ysplit > 1 ? ustage : hp.ustate, hp.wavepool, hp.waves, hp.ptab, hp.busmem, hp.wavecoef, staged, voice_major);
+			ysplit > 1 ? ustage : hp.ustate, hp.wavepool, hp.waves, hp.ptab, hp.busmem, hp.wavecoef, staged, voice_major, lds_taps);
 	if(ysplit > 1) {
 		A2DCommit cm = { dlist, nlist, 2, ustage, staged };
 		if(defer)

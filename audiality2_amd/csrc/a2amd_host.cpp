@@ -17,6 +17,7 @@
 #include "a2amd_noisemap.h"
 #include "a2amd_cutsweep.h"
 #include "a2amd_settled.h"
+#include "a2amd_wavepads.h"
 
 namespace a2h { thread_local char g_err[256] = ""; }
 
@@ -415,6 +416,9 @@ static int wave_place(a2amd_ctx *c, uint64_t key, const a2amd_wavedesc *w, const
 		if(!cap) {
 			HIPCHK(c, hipMemcpy(c->d_wavepool.d + pos, w->data[l], n * sizeof(int16_t), hipMemcpyHostToDevice));
 			c->wave_h2d_bytes += n * sizeof(int16_t);
+			// (k_leaf_osc2pan may keep such a level's payload entries in LDS: a2d_osc2_stage)
+			if((w->flags & 0x100u) && a2w_pads_periodic(w->data[l], w->size[l], A2AMD_WAVEPRE, A2AMD_WAVEPOST))
+				hw.dw.periodic |= 1u << l;
 		}
 		loff[l] = (uint32_t)(pos - pos0);
 		lsize[l] = w->size[l];

@@ -2,6 +2,7 @@
 // where a quiet batch repeats), the master bus and the taps back to the host; a2amd_collect,
 // a2amd_replay, statistics.  (Split out of a2amd_host.cpp in round 3.)
 #include "a2amd_host.h"
+#include "a2amd_wavepads.h"
 
 extern "C" {
 // ---- render -------------------------------------------------------------------------
@@ -529,6 +530,16 @@ int a2amd_last_batch_osc2(const a2amd_ctx *c, a2amd_osc2_batch_info *out)
 		}
 	}
 	return A2AMD_OK;
+}
+
+unsigned a2amd_osc2_stage_rule(unsigned size0, int periodic0, unsigned size1, int periodic1)
+{
+	return a2d_osc2_stage(size0, periodic0 != 0, size1, periodic1 != 0);
+}
+
+int a2amd_wave_level_periodic(const int16_t *level, unsigned size)
+{
+	return a2w_pads_periodic(level, size, A2AMD_WAVEPRE, A2AMD_WAVEPOST);
 }
 
 int a2amd_last_batch_fbdpan(const a2amd_ctx *c, a2amd_fbdpan_batch_info *out)

@@ -1849,8 +1849,10 @@ static int launch_leaves(a2amd_ctx *c, LeafPass &lp)
 		pick_fast_shape(c->sw, osc2pan.count, c->nfrags * A2D_FAST_FCH / A2D_OSC2_FCH, &vpw, &ysplit, 16);
 		// (A2AMD_DEBUG bit 16: no voice-major walk, every super-chunk chunk by chunk - A/B and tests)
 		const int voice_major = !(c->sw.debug & 16);
+		// (... bit 17: that walk stages no level in LDS, every tap is a gather - include/a2amd_osc2lds.h)
+		const int lds_taps = !(c->sw.debug & (1 << 17));
 		if(a2d_launch_leaf_osc2pan(c->d_params, c->hparams, list + osc2pan.first, osc2pan.count,
-				vpw, ysplit, c->d_ustage.d, c->d_staged.d + osc2pan.first, c->stream, &pend.c[pend.n], voice_major, &ysplit))
+				vpw, ysplit, c->d_ustage.d, c->d_staged.d + osc2pan.first, c->stream, &pend.c[pend.n], voice_major, lds_taps, &ysplit))
 			return c->fail(A2AMD_EHIP, "2-osc leaf launch failed: %s", hipGetErrorString(hipGetLastError()));
 		// (a2amd_last_batch_osc2(): the launch as it went out; the walks follow from it and the batch's fragment lengths)
 		c->last_osc2.launched = 1;

@@ -159,6 +159,46 @@ DEV Coef4 coef_at(const CoefRsrc rs, int cb, unsigned ph)
 	return a2d_coef_load(rs, (int)(ph >> 8), 0, cb, 0);
 }
 
+// ... and from a wavefront's copy of a whole mip level in LDS (k_leaf_osc2pan's staged oscillators, a2d_osc2_stage): the
+// level's size payload entries in the table's own layout, written by stage_level() below.  The level's size is
+// 1 << lg and its pads are periodic, so entry i is entry i mod size for every i a tap can reach (a2amd_wavepads.h):
+// the index is a bit field of the phase - one extract where the gather had none, and one multiply-add for the
+// address - and the entry three dword reads at immediate offsets 0, 4, 8.  (Entries are 4-byte aligned: the pointer
+// says so, and the three reads must not become one 12-byte read, which is only fast at 16-byte alignment.)
+typedef __attribute__((address_space(3))) int LdsInt;
+DEV Coef4 coef_lds(const LdsInt *level, unsigned ph, unsigned lg)
+{
+	const LdsInt *e = level + A2D_COEF_WORDS * __builtin_amdgcn_ubfe(ph, 8, lg);
+	Coef4 k;
+	k.x = e[0];
+	k.y = e[1];
+	k.z = e[2];
+	return k;
+}
+
+// The copy: entries [0, size) of the level whose first payload entry stands at byte cb of the table, size <=
+// A2D_OSC2_LDS_ENT, as coalesced dword loads (at most 6 a lane) and dword stores in the same linear layout.  Lanes
+// read entries other lanes wrote: the caller fences on both sides (the compiler cannot see that dependency).
+DEV void stage_level(LdsInt *level, const int *wavecoef, int cb, unsigned size, int lane)
+{
+	const int *src = wavecoef + ((unsigned)cb >> 2);
+	const unsigned n = size * A2D_COEF_WORDS;
+#pragma unroll
+	for(int r = 0; r < A2D_OSC2_LDS_ENT * A2D_COEF_WORDS / 64; ++r) {
+		const unsigned i = (unsigned)(r * 64 + lane);
+		if(i < n)
+			level[i] = src[i];
+	}
+}
+
+// what orders a wavefront's LDS stores against its other lanes' reads (LDS operations of one wavefront execute in
+// order: nothing to wait for, the compiler must only keep them where they are)
+DEV void lds_wave_fence()
+{
+	__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+	__builtin_amdgcn_wave_barrier();
+}
+
 // The 24:8 phase of a tap: (ph + lane * dph) >> 16 for a wave-uniform 64 bit phase ph and
 // ldph = lane * dph (below 2^31: dph <= A2D_MAXPHINC << 16 on the settled paths).  Split at
 // bit 16 the sum needs no 64 bit vector arithmetic: the halves of ph stay scalar, the lane

@@ -233,6 +233,11 @@ class Backend:
         self._last_batch_osc2 = None
         if hasattr(lib, prefix + "last_batch_osc2"):
             self._last_batch_osc2 = fn("last_batch_osc2", i32, vp, C.POINTER(a2amd_osc2_batch_info))
+        # include/a2amd_osc2lds.h: pure functions, no context (the product library only)
+        self._osc2_stage_rule = self._wave_level_periodic = None
+        if hasattr(lib, prefix + "osc2_stage_rule"):
+            self._osc2_stage_rule = fn("osc2_stage_rule", u32, u32, i32, u32, i32)
+            self._wave_level_periodic = fn("wave_level_periodic", i32, C.POINTER(C.c_int16), u32)
         self._last_batch_fbdpan = None
         if hasattr(lib, prefix + "last_batch_fbdpan"):
             self._last_batch_fbdpan = fn("last_batch_fbdpan", i32, vp, C.POINTER(a2amd_fbdpan_batch_info))
@@ -407,6 +412,22 @@ class Backend:
         bi = a2amd_osc2_batch_info()
         self._chk(self._last_batch_osc2(self.ctx, C.byref(bi)), "last_batch_osc2")
         return bi
+
+    def osc2_stage_rule(self, size0, periodic0, size1, periodic1):
+        """a2amd_osc2_stage_rule: the mask of a settled `wtosc; wtosc; panmix` voice's oscillators whose taps
+        k_leaf_osc2pan's voice-major walk reads from a copy of the mip level in LDS, from the sizes of the levels they
+        play and whether those levels' pads are periodic (bit 0: the first oscillator, bit 1: the second)"""
+        if self._osc2_stage_rule is None:
+            raise RuntimeError(f"this library has no {self.prefix}osc2_stage_rule")
+        return int(self._osc2_stage_rule(size0, int(bool(periodic0)), size1, int(bool(periodic1))))
+
+    def wave_level_periodic(self, level):
+        """a2amd_wave_level_periodic: are the pads of this level - int16, WAVEPRE + size + WAVEPOST samples, as
+        wave_upload() takes it - the periodic continuation of its payload"""
+        if self._wave_level_periodic is None:
+            raise RuntimeError(f"this library has no {self.prefix}wave_level_periodic")
+        arr = np.ascontiguousarray(level, dtype=np.int16)
+        return bool(self._wave_level_periodic(arr.ctypes.data_as(C.POINTER(C.c_int16)), len(arr) - WAVEPRE - WAVEPOST))
 
     def last_batch_fbdpan(self):
         """a2amd_last_batch_fbdpan: whether k_bus_fbdpan was launched for the most recent batch, the bus owners of its

@@ -463,5 +463,7 @@ int  a2amd_last_batch(const a2amd_ctx *ctx, a2amd_batch_info *bi);
 #include "a2amd_vmbatch.h"
 /* How k_leaf_osc2pan walked its settled voices in the most recent batch, voice by voice or chunk by chunk: a2amd_last_batch_osc2(). */
 #include "a2amd_osc2.h"
+/* ... and which of their oscillators read their taps from a copy of the mip level in LDS: a2amd_osc2_stage_rule(). */
+#include "a2amd_osc2lds.h"
 
 #endif /* A2AMD_H */
