@@ -359,6 +359,9 @@ int a2d_launch_leaf_noisefiltpan(const A2DParams *dparams, const A2DParams &hp, 
 // a2amd_oscbare.hip: k_leaf_oscbare, the quiet kernel of bare wtosc voices (one unit, wired, adding into channel 0 of the
 // output bus): the voices of the list without records this batch, gliding or not, 'vpw' (at most 64) of them per wavefront
 int a2d_launch_leaf_oscbare(const A2DParams *dparams, const A2DParams &hp, const int *dlist, int nlist, int vpw, void *stream);
+// a2amd_osc3filtpan.hip: k_leaf_osc3filtpan, the quiet kernel of 3 x wtosc -> filter12 -> panmix voices: the voices of the list
+// without a run this batch, gliding or not; a workgroup per 'vpg' (at most 64) voices, its filter wavefront lane = voice
+int a2d_launch_leaf_osc3filtpan(const A2DParams *dparams, const A2DParams &hp, const int *dlist, int nlist, int vpg, void *stream);
 
 // a2amd_vm.hip: the count pass (emit = 0) or the emit pass of the VM kernel
 int a2d_launch_vm(const A2DVmParams &vp, int emit, void *stream);

@@ -217,12 +217,13 @@ struct HVoice {
 };
 
 enum { CLS_GENERIC = 0, CLS_OSCPAN, CLS_OSCFILTPAN, CLS_BUSDRIVER, CLS_BUSGENERIC, CLS_OSC2PAN, CLS_FMPAN, CLS_FBDCHAIN,
-	CLS_OSC2FILTPAN, CLS_NOISEPAN, CLS_NOISEFILTPAN, CLS_OSCBARE, CLS_FBDPAN, CLS_N };	// (cls_lists below has a row per class, in this order)
+	CLS_OSC2FILTPAN, CLS_NOISEPAN, CLS_NOISEFILTPAN, CLS_OSCBARE, CLS_FBDPAN, CLS_OSC3FILTPAN, CLS_N };	// (cls_lists below has a row per class, in this order)
 
 // ---- the launch lists: one table of ranges ----
 // a2amd_ctx::list_all (on the device: d_list), rebuilt when the voice tree changes, holds every listed voice by launch class:
 //   [ wtosc-panmix | 2 x wtosc-panmix | wtosc-filter12-panmix | fm-panmix | general leaves | 2 x wtosc-filter12-panmix |
-//     wtosc (noise)-panmix | wtosc (noise)-filter12-panmix | bare wtosc | per nesting depth, 0 first: driver chains |
+//     wtosc (noise)-panmix | wtosc (noise)-filter12-panmix | bare wtosc | 3 x wtosc-filter12-panmix |
+//     per nesting depth, 0 first: driver chains |
 //     delay chains | pan-tailed delay chains | general bus voices ]
 // a2amd_ctx::leaf[LEAF_*] are the leaf segments IN LIST ORDER (2 x wtosc-filter12-panmix was appended behind the general
 // leaves in round 6 and stays there: the order shows in d_list offsets and in the device VM's lists), depth_ranges[d] the
@@ -236,7 +237,7 @@ enum { CLS_GENERIC = 0, CLS_OSCPAN, CLS_OSCFILTPAN, CLS_BUSDRIVER, CLS_BUSGENERI
 // d_dyn, which moves when the blob grows (a2amd_vm.cpp).
 struct ListRange { int first = 0, count = 0; };
 enum { LEAF_OSCPAN = 0, LEAF_OSC2PAN, LEAF_OSCFILTPAN, LEAF_FMPAN, LEAF_GENERIC, LEAF_OSC2FILTPAN, LEAF_NOISEPAN, LEAF_NOISEFILTPAN,
-	LEAF_OSCBARE, LEAF_N };
+	LEAF_OSCBARE, LEAF_OSC3FILTPAN, LEAF_N };	// (a new segment goes last: the others' offsets in d_list stay)
 enum { DYN_OSC1 = 0, DYN_OSC2, DYN_FILT, DYN_FILT2, DYN_REST, DYN_N };
 // (ramp: in d_dyn, this batch's driver chains without records whose volume or pan may still glide - k_bus_driver's
 // second launch of the depth, one workgroup a voice)
@@ -256,7 +257,10 @@ static const struct { int8_t leaf, dyn; } cls_lists[CLS_N] = {
 	// gliding or not; with records it is the general kernel's, as it was before the class had a kernel
 	{ LEAF_OSCBARE, DYN_REST },
 	// inline; fbdelay x 1..4; panmix wired and adding: a bus owner, on its depth's list for k_bus_fbdpan
-	{ -1, -1 } };
+	{ -1, -1 },
+	// 3 x wtosc-filter12-panmix: a segment of its own for k_leaf_osc3filtpan, which takes its voices without a run, gliding or
+	// not; with a run it is the general kernel's, as it was before the class had a kernel
+	{ LEAF_OSC3FILTPAN, DYN_REST } };
 // wtosc (noise)-filter12-panmix voices without a record in a batch from which k_leaf_noisefiltpan takes them (A2Switches::nzf_min,
 // A2AMD_NZF_MIN, 64): a launch lasts as long as its filter wavefront's chain through the batch however few of its lanes are
 // busy, behind the window kernels on the context's one stream, which render a few such voices inside the launch they make
@@ -537,6 +541,9 @@ struct a2amd_ctx {
 	// batches that take upload()'s quiet path, which are the last full one again - and the mono owners on k_bus_driver's lists
 	uint32_t n_bare_quiet = 0, n_bare_gliding = 0, n_bare_records = 0, n_mono_drivers = 0;
 	a2amd_bare_batch_info last_bare = {};	// a2amd_last_batch_bare()
+	// 3 x wtosc-filter12-panmix voices (CLS_OSC3FILTPAN): likewise, the segment's voices by who renders them this batch
+	uint32_t n_o3f_quiet = 0, n_o3f_gliding = 0, n_o3f_records = 0;
+	a2amd_osc3filt_batch_info last_osc3filt = {};	// a2amd_last_batch_osc3filt()
 	a2amd_osc2_batch_info last_osc2 = {};	// a2amd_last_batch_osc2(): the launch; the walks are counted when asked for
 	a2amd_fbdpan_batch_info last_fbdpan = {};	// a2amd_last_batch_fbdpan(): upload() counts, launch_depth() sets launched
 	a2amd_bus_windows_info last_buswin = {};	// a2amd_last_batch_bus_windows(): likewise, reset by every upload()

@@ -1,0 +1,372 @@
+// a2amd_osc3filtpan.hip - k_leaf_osc3filtpan: the quiet kernel of "wtosc (replacing) + wtosc (adding) + wtosc (adding) ->
+// filter12 (1 ch) -> panmix 1->2, wired, adding" leaf voices - the three-oscillator subtractive lead,
+// `struct { wtosc; wtosc o2; wtosc o3; filter12; panmix }` - in the batches in which they carry no record.
+//
+// Ownership and pipeline are k_leaf_noisefiltpan's (a2amd_noisefiltpan.hip): a workgroup of 8 wavefronts owns up to 64
+// voices of its run of the bus-sorted list for the WHOLE batch and walks its fragments in order - no time slices, no
+// staged commit.  Per fragment three stages meet over a ring of three [voices][64 + 1] LDS tiles, a barrier per step:
+//   K/A(f)    workers.  Lane = voice, once per fragment: osc_window_v() (a2amd_winctl.h) steps each of the voice's three
+//             oscillators over the window - pitch and amplitude rampers, mip level, the wrap of a looped wave, a one-shot
+//             wave's end, a pitch out of range, an unloaded wave - and leaves the closed-form words of the window, as in
+//             k_leaf_oscbare (a2amd_oscbare.hip).  Then lane = frame, voice by voice: the words out of the lanes, two
+//             coefficient-table taps per oscillator that plays, the next voice's loads issued before this voice's
+//             arithmetic; the replacing oscillator's value (0 where it is silent) and the two adders' in wtosc.c's wrapping
+//             add; the row stored already shifted (x5 = sum >> 5, filter12.c:105: the shift is of the SUM)
+//   B(f - 1)  wavefront 0, lane = voice: the q ramper prepared and run per fragment, filt_row (a2amd_filt.h) in place
+//   C(f - 2)  workers.  Lane = voice: panmix_process12's head (panmix.c:84-95: the clamp flag in front of a2_PrepareRamper,
+//             as ctl_window has it) on the voice's volume and pan rampers; lane = frame: the rows x the two gains - constant
+//             where volume and pan rest, value + delta * frame otherwise (win_pan's arithmetic, a2amd_win.hip) - summed
+//             over the voices of one output bus (the list is sorted by bus).  Where all the workgroup's voices mix into ONE
+//             stereo bus the workers' sums meet in LDS and
+//   D(f - 3)  the idle wavefront adds the workgroup's total to the bus in device memory: one atomic add per (fragment,
+//             channel, frame) and workgroup.  A workgroup that spans several buses adds per worker and bus run instead.
+// At the end every word the windows moved is stored with plain vector stores, as the general kernel or ctl_store would
+// have left it: the three oscillators' (oscv_store) and the panmix's two rampers by the worker that carried them, the q
+// ramper and FW_D1A / FW_D2A by wavefront 0 - a voice can change hands in either direction between any two batches.
+//
+// A gliding voice is this kernel's too (the host gives the class no stand-in record): every ramper is stepped here.
+// A voice with a run this batch (runs[v].count != 0: records of its own, the stand-in of a sweeping cutoff or of a
+// device-seeded noise oscillator) is the general kernel's and is skipped untouched, and so is a voice one of whose
+// oscillators is neither on a mip-mapped wave nor off, or whose filter has a coefficient ramp pending (only records
+// leave one): every wavefront of the workgroup reads the same words and comes to the same answer.
+#include <hip/hip_runtime.h>
+#include "a2amd_device.h"
+#include "a2amd_dsp.h"
+#include "a2amd_taps.h"
+#include "a2amd_winctl.h"
+#include "a2amd_filt.h"
+
+#define O3F_MAXV  64	// voices per workgroup: the lanes of the filter wavefront
+#define O3F_PITCH 65	// (+1: row and column accesses both bank-conflict free)
+// Wavefronts per workgroup, as k_leaf_noisefiltpan: the filter wavefront, six workers, and wavefront 4 - which was
+// observed to share the filter's SIMD - with no voices: it adds the workgroup's sums to the bus.
+#define O3F_WAVES 8
+#define O3F_WORKERS 6
+
+// one oscillator's two taps of a frame, issued (k_leaf_oscbare's BareTaps); all zero for an oscillator that is silent
+// in the window: it then comes out as 0
+struct O3Taps { Coef4 k1, k2; unsigned t1, t2; int ak, da; };
+
+DEV void o3_clear(O3Taps &T)
+{
+	T.k1 = T.k2 = Coef4{ 0, 0, 0 };
+	T.t1 = T.t2 = 0;
+	T.ak = T.da = 0;
+}
+
+// voice v's window words out of the lanes; where this lane's frame fl reads the wave; the loads
+DEV void o3_issue(const int (&w)[6], int v, const CoefRsrc rs, unsigned fl, O3Taps &T)
+{
+	const unsigned phlo = (unsigned)rdl(w[WO_B], v), phhi = (unsigned)rdl(w[WO_C], v), dph = (unsigned)rdl(w[WO_DPH], v);
+	const int cb = coef_base((unsigned)rdl(w[WO_A], v));
+	T.ak = rdl(w[WO_AK], v);
+	T.da = rdl(w[WO_DA], v);
+	T.t1 = tap_phase((uint64_t)phlo | ((uint64_t)phhi << 32), fl * dph);
+	T.t2 = T.t1 + ((dph >> 16) >> 1);
+	T.k1 = coef_at(rs, cb, T.t1);
+	T.k2 = coef_at(rs, cb, T.t2);
+}
+
+// wtosc_do_fragment's sample of frame fl, wtosc.c:227-229 (the amplitude ramper run frame by frame)
+DEV int o3_finish(const O3Taps &T, unsigned fl)
+{
+	const int h = inter_coefs(T.k1, T.t1, T.k2, T.t2);
+	return mul64s(h, wadd(T.ak, wmul(T.da, (int)fl)), 17);
+}
+
+__global__ __launch_bounds__(64 * O3F_WAVES)
+void k_leaf_osc3filtpan(const A2DParams *__restrict__ pp, const int *__restrict__ list, int nlist, int vpg,
+		const A2DVoice *__restrict__ voices, const A2DRun *__restrict__ runs, int *ustate,
+		const A2DWave *__restrict__ waves, const uint32_t *__restrict__ ptab, const int *__restrict__ wavecoef,
+		int nfrags, int *__restrict__ busmem)
+{
+	extern __shared__ __attribute__((aligned(16))) int o3_tiles[];	// 3 x [vpg][O3F_PITCH]
+	// the pitch table: read in every window of a gliding voice, from LDS (as k_win_ctl)
+	__shared__ PTab s_ptab;
+	// the workgroup's share of its bus, fragment by fragment, where it has one bus (stage D)
+	__shared__ int o3_acc[3][2][A2D_FRAG];
+	for(int k = (int)threadIdx.x; k < 128; k += 64 * O3F_WAVES)
+		s_ptab[k] = ptab[k];
+	for(int k = (int)threadIdx.x; k < 3 * 2 * A2D_FRAG; k += 64 * O3F_WAVES)
+		(&o3_acc[0][0][0])[k] = 0;
+	__syncthreads();
+	const int wv = rfl((int)(threadIdx.x >> 6));
+	const int lane = threadIdx.x & 63;
+	const int first = (int)blockIdx.x * vpg;
+	const int nv = min(vpg, nlist - first);
+	if(nv <= 0)
+		return;		// (the whole workgroup: the grid has none such)
+	const int tsize = vpg * O3F_PITCH;
+
+	// lane v: voice v of this workgroup, in every wavefront
+	int uo0 = 0, uo1 = 0, uo2 = 0, uf = 0, up = 0, my_off = -1, my_nch = 2;
+	int lp_l = 0, bp_l = 0, hp_l = 0;
+	bool ok = false;
+	if(lane < nv) {
+		const int slot = list[first + lane];
+		if(runs[slot].count == 0) {
+			const A2DVoice &vc = voices[slot];
+			uo0 = vc.unit[0]; uo1 = vc.unit[1]; uo2 = vc.unit[2];
+			uf = vc.unit[3];
+			up = vc.unit[4];
+			my_off = vc.out_off;
+			my_nch = vc.out_nch;
+			const int m0 = ustate[(size_t)uo0 * A2D_USTATE + OW_MODE], m1 = ustate[(size_t)uo1 * A2D_USTATE + OW_MODE],
+					m2 = ustate[(size_t)uo2 * A2D_USTATE + OW_MODE];
+			const int *wf = ustate + (size_t)uf * A2D_USTATE;
+			lp_l = wf[FW_LP]; bp_l = wf[FW_BP]; hp_l = wf[FW_HP];
+			ok = vc.nunits == 5 && my_off >= 0 && my_nch >= 2 && !wf[FW_RAMP] &&
+					(m0 == A2D_OSC_MIPWAVE || m0 == A2D_OSC_OFF) && (m1 == A2D_OSC_MIPWAVE || m1 == A2D_OSC_OFF) &&
+					(m2 == A2D_OSC_MIPWAVE || m2 == A2D_OSC_OFF);
+		}
+	}
+	const unsigned long long todo = __ballot(ok);
+	if(!todo)
+		return;		// (the whole workgroup)
+	// The row format of the batch (filt_step): pure low pass filters in the whole workgroup leave l in the rows and the pan
+	// stage applies lp - 12 dependent instructions per frame instead of 15.
+	const bool lpraw = __all(!ok || (bp_l == 0 && hp_l == 0));
+	const int wg_off = rdl(my_off, (int)__builtin_ctzll(todo));
+	const bool wgbus = __all(!ok || (my_off == wg_off && my_nch == 2));
+	const int nsteps = nfrags + 3;
+
+	if(wv == 0) {
+		// ================= the filter wavefront: lane = voice =================
+		Ramp q = { 0, 0, 0, 0 };
+		int ff_l = 0, d1_l = 0, d2_l = 0;
+		if(ok) {
+			const int *wf = ustate + (size_t)uf * A2D_USTATE;
+			q = ramp_load(wf + FW_Q);
+			ff_l = wf[FW_F1] >> 12;		// f12_process's f, filter12.c:99 (no coefficient ramp: df = 0)
+			d1_l = wf[FW_D1A];
+			d2_l = wf[FW_D2A];
+		}
+		__builtin_amdgcn_s_setprio(3);
+		for(int st = 0; st < nsteps; ++st) {
+			const int f = st - 1;
+			if(f >= 0 && f < nfrags) {
+				const int n = min((int)pp->fragframes[f], A2D_FRAG);
+				if(n > 0) {
+					// f12_process's head, filter12.c:86-96
+					if(ok)
+						ramp_prepare_v(q, n);
+					const bool qrest = __all(!ok || q.delta == 0);
+					if(ok) {
+						int *row = o3_tiles + (f % 3) * tsize + lane * O3F_PITCH;
+						int qv = q.value;
+						if(qrest) {
+							if(lpraw)
+								filt_row<true, true>(row, n, ff_l, lp_l, bp_l, hp_l, d1_l, d2_l, qv, 0);
+							else
+								filt_row<false, true>(row, n, ff_l, lp_l, bp_l, hp_l, d1_l, d2_l, qv, 0);
+						} else {
+							if(lpraw)
+								filt_row<true, false>(row, n, ff_l, lp_l, bp_l, hp_l, d1_l, d2_l, qv, q.delta);
+							else
+								filt_row<false, false>(row, n, ff_l, lp_l, bp_l, hp_l, d1_l, d2_l, qv, q.delta);
+						}
+						ramp_run(q, n);
+					}
+				}
+			}
+			filt_barrier();
+		}
+		// state out: the filter's words as f12_process / ctl_store leave them
+		if(ok) {
+			int *wf = ustate + (size_t)uf * A2D_USTATE;
+			ramp_store(wf + FW_Q, q);
+			wf[FW_D1A] = d1_l;
+			wf[FW_D2A] = d2_l;
+		}
+		return;
+	}
+
+	// ================= workers: voices [vb, ve) of the workgroup =================
+	const int widx = wv < 4 ? wv - 1 : wv - 2;	// (wavefront 4 shares the filter's SIMD: no voices)
+	int vb = 0, ve = 0;
+	if(wv != 4) {
+		const int per = nv / O3F_WORKERS, extra = nv % O3F_WORKERS;
+		vb = widx * per + min(widx, extra);
+		ve = vb + per + (widx < extra ? 1 : 0);
+	}
+	// my voices among the ones to render
+	unsigned long long mine = 0;
+	if(ve > vb)
+		mine = todo & ((ve >= 64 ? ~0ull : ((1ull << ve) - 1ull)) & ~((1ull << vb) - 1ull));
+	// (wave-uniform, and known to the compiler as such)
+	mine = (unsigned long long)(unsigned)rfl((int)(unsigned)mine) | ((unsigned long long)(unsigned)rfl((int)(unsigned)(mine >> 32)) << 32);
+	const bool mylane = (mine >> lane) & 1ull;
+
+	// lane v, my voices only: the three oscillators as ctl_load loads them, the panmix's rampers
+	OscV o0, o1, o2;
+	oscv_clear(o0);
+	oscv_clear(o1);
+	oscv_clear(o2);
+	Ramp vol = { 0, 0, 0, 0 }, pan = { 0, 0, 0, 0 };
+	if(mylane) {
+		oscv_load(o0, ustate + (size_t)uo0 * A2D_USTATE);
+		oscv_load(o1, ustate + (size_t)uo1 * A2D_USTATE);
+		oscv_load(o2, ustate + (size_t)uo2 * A2D_USTATE);
+		const int *wp = ustate + (size_t)up * A2D_USTATE;
+		vol = ramp_load(wp + PW_VOL);
+		pan = ramp_load(wp + PW_PAN);
+	}
+	const CoefRsrc rs = coef_rsrc(wavecoef);
+
+	// one fragment's sums of this wavefront's bus run
+	auto bus_add = [&](int off, int nch, int f, int acc0, int acc1) __attribute__((always_inline)) {
+		if(wgbus) {
+			if(acc0) atomicAdd(&o3_acc[f % 3][0][lane], acc0);
+			if(acc1) atomicAdd(&o3_acc[f % 3][1][lane], acc1);
+		} else {
+			int *dst = busmem + off + (size_t)f * nch * A2D_FRAG;
+			if(acc0) atomicAdd(&dst[lane], acc0);
+			if(acc1) atomicAdd(&dst[A2D_FRAG + lane], acc1);
+		}
+	};
+
+	for(int st = 0; st < nsteps; ++st) {
+		// ---- D(st - 3): the workgroup's sum of a fragment, complete since the last barrier ----
+		if(wv == 4 && wgbus && st >= 3) {
+			const int f = st - 3;
+			if((int)pp->fragframes[f] > 0) {
+				const int a0 = o3_acc[f % 3][0][lane], a1 = o3_acc[f % 3][1][lane];
+				o3_acc[f % 3][0][lane] = 0;
+				o3_acc[f % 3][1][lane] = 0;
+				int *dst = busmem + wg_off + (size_t)f * 2 * A2D_FRAG;
+				if(a0) atomicAdd(&dst[lane], a0);
+				if(a1) atomicAdd(&dst[A2D_FRAG + lane], a1);
+			}
+		}
+		// ---- K/A(st) ----
+		if(st < nfrags && mine) {
+			const int f = st;
+			const int n = min((int)pp->fragframes[f], A2D_FRAG);
+			if(n > 0) {
+				// control, lane = voice: the window's words of each oscillator and what its frames are made of
+				int w0[6] = { 0, 0, 0, 0, 0, 0 }, w1[6] = { 0, 0, 0, 0, 0, 0 }, w2[6] = { 0, 0, 0, 0, 0, 0 };
+				int md0 = WM_SILENT, md1 = WM_SILENT, md2 = WM_SILENT;
+				if(mylane) {
+					md0 = osc_window_v(waves, s_ptab, o0, n, w0);
+					md1 = osc_window_v(waves, s_ptab, o1, n, w1);
+					md2 = osc_window_v(waves, s_ptab, o2, n, w2);
+				}
+				const unsigned long long t0 = __ballot(md0 == WM_TAPS), t1 = __ballot(md1 == WM_TAPS), t2 = __ballot(md2 == WM_TAPS);
+				// render, lane = frame.  (lanes beyond the fragment's frames: the last frame's address, stored as 0)
+				int *tile = o3_tiles + (f % 3) * tsize;
+				const unsigned fl = (unsigned)min(lane, n - 1);
+				const bool in = lane < n;
+				auto issue = [&](int v, O3Taps &A, O3Taps &B, O3Taps &C) __attribute__((always_inline)) {
+					if((t0 >> v) & 1ull) o3_issue(w0, v, rs, fl, A); else o3_clear(A);
+					if((t1 >> v) & 1ull) o3_issue(w1, v, rs, fl, B); else o3_clear(B);
+					if((t2 >> v) & 1ull) o3_issue(w2, v, rs, fl, C); else o3_clear(C);
+				};
+				unsigned long long m = mine;
+				int k = (int)__builtin_ctzll(m);
+				m &= m - 1;
+				O3Taps A0, B0, C0;
+				issue(k, A0, B0, C0);
+				for(;;) {
+					const int kn = m ? (int)__builtin_ctzll(m) : -1;
+					O3Taps A1, B1, C1;
+					if(kn >= 0)
+						issue(kn, A1, B1, C1);
+					// wtosc_do_fragment replacing, then twice adding (A2_PROCADD: wrapping)
+					const int x = wadd(wadd(o3_finish(A0, fl), o3_finish(B0, fl)), o3_finish(C0, fl));
+					tile[k * O3F_PITCH + lane] = in ? x >> 5 : 0;
+					if(kn < 0)
+						break;
+					m &= m - 1;
+					k = kn;
+					A0 = A1; B0 = B1; C0 = C1;
+				}
+			}
+		}
+		// ---- C(st - 2) ----
+		if(st >= 2 && st - 2 < nfrags && mine) {
+			const int f = st - 2;
+			const int n = min((int)pp->fragframes[f], A2D_FRAG);
+			if(n > 0) {
+				// control, lane = voice: panmix_process12's head, panmix.c:84-95 (the clamp variant chosen in front of
+				// a2_PrepareRamper), the rampers stepped over the window
+				int pv = 0, pdv = 0, ppn = 0, pdp = 0, g0 = 0, g1 = 0;
+				bool pcl = false;
+				if(mylane) {
+					pcl = a2s_pan_over(pan.target) || a2s_pan_over(pan.value);
+					ramp_prepare_v(vol, n);
+					ramp_prepare_v(pan, n);
+					pv = vol.value; pdv = vol.delta;
+					ppn = pan.value; pdp = pan.delta;
+					// (volume and pan at rest: the window's two gains)
+					a2s_pan_gains(pv, ppn, pcl, &g0, &g1);
+					ramp_run(vol, n);
+					ramp_run(pan, n);
+				}
+				const unsigned long long mramp = __ballot((pdv | pdp) != 0), mclamp = __ballot(pcl);
+				// lane = frame
+				const int *tile = o3_tiles + (f % 3) * tsize;
+				const bool in = lane < n;
+				int acc0 = 0, acc1 = 0;
+				int cur_off = -1, cur_nch = 2;
+				for(unsigned long long m = mine; m; m &= m - 1) {
+					const int v = (int)__builtin_ctzll(m);
+					const int voff = rdl(my_off, v);
+					if(voff != cur_off) {
+						if(cur_off >= 0)
+							bus_add(cur_off, cur_nch, f, acc0, acc1);
+						acc0 = acc1 = 0;
+						cur_off = voff;
+						cur_nch = rdl(my_nch, v);
+					}
+					int y = tile[v * O3F_PITCH + lane];
+					if(lpraw)
+						y = wmul(y, rdl(lp_l, v)) >> 3;	// (filt_step: the row holds l)
+					int v0 = rdl(g0, v), v1 = rdl(g1, v);
+					if((mramp >> v) & 1ull) {
+						// win_pan's arithmetic for a window in which volume or pan moves
+						const int vk = wadd(rdl(pv, v), wmul(rdl(pdv, v), lane));
+						const int pk = wadd(rdl(ppn, v), wmul(rdl(pdp, v), lane));
+						const int vp = mul64s(pk, vk, 24);
+						v0 = wsub(vk, vp);
+						v1 = wadd(vk, vp);
+						if((mclamp >> v) & 1ull) {
+							const int lim = wshl(vk, 1);
+							if(v0 > lim) v0 = lim;
+							if(v1 > lim) v1 = lim;
+						}
+					}
+					if(in) {
+						acc0 = wadd(acc0, mul64s(y, v0, 24));
+						acc1 = wadd(acc1, mul64s(y, v1, 24));
+					}
+				}
+				if(cur_off >= 0)
+					bus_add(cur_off, cur_nch, f, acc0, acc1);
+			}
+		}
+		filt_barrier();
+	}
+
+	// state out: ctl_store's words of the oscillators and the panmix
+	if(mylane) {
+		oscv_store(ustate + (size_t)uo0 * A2D_USTATE, o0);
+		oscv_store(ustate + (size_t)uo1 * A2D_USTATE, o1);
+		oscv_store(ustate + (size_t)uo2 * A2D_USTATE, o2);
+		int *wp = ustate + (size_t)up * A2D_USTATE;
+		ramp_store(wp + PW_VOL, vol);
+		ramp_store(wp + PW_PAN, pan);
+	}
+}
+
+// voices per workgroup: at most O3F_MAXV (one per lane of the filter wavefront)
+int a2d_launch_leaf_osc3filtpan(const A2DParams *dparams, const A2DParams &hp, const int *dlist, int nlist, int vpg, void *stream)
+{
+	if(nlist <= 0)
+		return 0;
+	vpg = vpg < 1 ? 1 : vpg > O3F_MAXV ? O3F_MAXV : vpg;
+	const dim3 grid((nlist + vpg - 1) / vpg), block(64 * O3F_WAVES);
+	const size_t dyn = (size_t)3 * vpg * O3F_PITCH * sizeof(int);
+	hipLaunchKernelGGL(k_leaf_osc3filtpan, grid, block, dyn, (hipStream_t)stream, dparams, dlist, nlist, vpg, hp.voices, hp.runs,
+			hp.ustate, hp.waves, hp.ptab, hp.wavecoef, hp.nfrags, hp.busmem);
+	return hipGetLastError() != hipSuccess;
+}

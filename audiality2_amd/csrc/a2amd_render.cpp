@@ -499,6 +499,14 @@ int a2amd_last_batch_bare(const a2amd_ctx *c, a2amd_bare_batch_info *out)
 	return A2AMD_OK;
 }
 
+int a2amd_last_batch_osc3filt(const a2amd_ctx *c, a2amd_osc3filt_batch_info *out)
+{
+	if(!c || !out)
+		return A2AMD_EINVAL;
+	*out = c->last_osc3filt;
+	return A2AMD_OK;
+}
+
 int a2amd_last_batch_osc2(const a2amd_ctx *c, a2amd_osc2_batch_info *out)
 {
 	if(!c || !out)

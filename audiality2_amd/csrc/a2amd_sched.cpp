@@ -262,6 +262,28 @@ bool is_osc2filtpan_chain(const a2amd_ctx *c, const HVoice &v)
 			(pm.flags & A2AMD_PROCADD);
 }
 
+// wtosc (replacing) + wtosc (adding) + wtosc (adding) -> filter12 (1 channel, replacing) -> panmix 1->2 adding into the
+// output bus: the three-oscillator subtractive lead, k_leaf_osc3filtpan's (a2amd_osc3filtpan.hip).  An oscillator on the
+// noise generator is not of the class (no quiet kernel renders noise in this chain): the voice is the general kernel's, as
+// before.  A 'w' write to or from noise marks the class stale and - with A2AMD_NOISE_QUIET on - rebuilds the lists; until a
+// rebuild such a voice has a run in every batch (its R_NOISESEED records or the noise stand-in), which the kernel skips.
+bool is_osc3filtpan_chain(const a2amd_ctx *c, const HVoice &v)
+{
+	if(v.nunits != 5 || v.out_nch < 2)
+		return false;
+	const HUnit &a = c->units[v.unit[0]], &b = c->units[v.unit[1]], &d = c->units[v.unit[2]], &f = c->units[v.unit[3]],
+			&pm = c->units[v.unit[4]];
+	return a.kind == A2AMD_WTOSC && !(a.flags & A2AMD_PROCADD) && !a.wired &&
+			leaf_mode(a.mode) && a.mode != A2D_OSC_NOISE &&
+			b.kind == A2AMD_WTOSC && (b.flags & A2AMD_PROCADD) && !b.wired &&
+			leaf_mode(b.mode) && b.mode != A2D_OSC_NOISE &&
+			d.kind == A2AMD_WTOSC && (d.flags & A2AMD_PROCADD) && !d.wired &&
+			leaf_mode(d.mode) && d.mode != A2D_OSC_NOISE &&
+			f.kind == A2AMD_FILTER12 && f.nin == 1 && !f.wired && !(f.flags & A2AMD_PROCADD) &&
+			pm.kind == A2AMD_PANMIX && pm.nin == 1 && pm.nout == 2 && pm.wired &&
+			(pm.flags & A2AMD_PROCADD);
+}
+
 // fmN -> panmix 1->2 adding into the output bus
 bool is_fmpan_chain(const a2amd_ctx *c, const HVoice &v)
 {
@@ -869,7 +891,11 @@ int upload(a2amd_ctx *c)
 							!(c->sw.no_fast & 16) && is_fmpan_chain(c, v) ? CLS_FMPAN :
 							// (a voice the device VM runs stays with the general kernel: the host cannot tell in which
 							// batches the VM writes it records - adoption and recall mark the class stale, a2amd_vm.cpp)
-							!(c->sw.no_fast & 256) && v.vm < 0 && is_oscbare_chain(c, v) ? CLS_OSCBARE : CLS_GENERIC;
+							!(c->sw.no_fast & 256) && v.vm < 0 && is_oscbare_chain(c, v) ? CLS_OSCBARE :
+							// (likewise, and - as for the two-oscillator note - not while an oscillator leaves the mip-mapped
+							// waves somewhere in this batch)
+							!(c->sw.no_fast & 1024) && v.vm < 0 && !v.mode_mix && is_osc3filtpan_chain(c, v) ? CLS_OSC3FILTPAN :
+							CLS_GENERIC;
 				if(v.out_off == 0)
 					owners_ok = false;	// adds straight into the master bus
 				leaf[cls_lists[v.cls].leaf].push_back((int)vi);
@@ -945,9 +971,11 @@ int upload(a2amd_ctx *c)
 				if(v.cls == CLS_OSC2FILTPAN)
 					v.dynf2_run = c->serial_base;
 				dyn[ok ? cls_lists[v.cls].dyn : DYN_REST].push_back(vi);
-			} else if(v.cls == CLS_OSCBARE) {
+			} else if(v.cls == CLS_OSCBARE || v.cls == CLS_OSC3FILTPAN) {
 				// (a bare wtosc with records - or the stand-in run of a noise oscillator in a device-seeded stretch: the general
-				// kernel's, which renders the voices on its exception list; k_leaf_oscbare skips a voice that has a run)
+				// kernel's, which renders the voices on its exception list; k_leaf_oscbare skips a voice that has a run.
+				// 3 x wtosc-filter12-panmix likewise: records of its own, the stand-in of a cutoff in the batch's sweep table or of
+				// a noise oscillator - k_leaf_osc3filtpan skips it)
 				dyn[DYN_REST].push_back(vi);
 			} else if((v.cls == CLS_BUSDRIVER || v.cls == CLS_FBDCHAIN || v.cls == CLS_FBDPAN) && v.depth < (int)dyn_bus.size()) {
 				// A pan-tailed delay chain whose run is windows only and tiles its fragments (seg_rows(); the classes are fresh
@@ -1086,6 +1114,20 @@ int upload(a2amd_ctx *c)
 			}
 			++c->n_bare_quiet;
 			c->n_bare_gliding += v.moving_until > c->vm.batch_time;
+		}
+		// a2amd_last_batch_osc3filt(): the 3 x wtosc-filter12-panmix voices, the same way.  One with a run - records of its own,
+		// the stand-in of a cutoff in the batch's sweep table or of a noise oscillator - stands on the general kernel's list
+		// above; the others are k_leaf_osc3filtpan's, gliding ones included: runs[v].count == 0 <=> rendered by that kernel.
+		c->n_o3f_quiet = c->n_o3f_gliding = c->n_o3f_records = 0;
+		const ListRange o3f = c->leaf[LEAF_OSC3FILTPAN];
+		for(int k = 0; k < o3f.count; ++k) {
+			const HVoice &v = c->voices[c->list_all[o3f.first + k]];
+			if(!v.recs.empty() || v.moving_run == c->serial_base) {
+				++c->n_o3f_records;
+				continue;
+			}
+			++c->n_o3f_quiet;
+			c->n_o3f_gliding += v.moving_until > c->vm.batch_time;
 		}
 	}
 
@@ -1840,6 +1882,20 @@ static int launch_leaves(a2amd_ctx *c, LeafPass &lp)
 		c->last_bare.launched = 1;
 		c->last_bare.vpw = (uint32_t)vpw;
 	}
+	// 3 x wtosc-filter12-panmix voices without a run this batch, settled or gliding (upload() counted them: none, and the
+	// segment's voices are all the general kernel's - no launch).  A workgroup keeps its voices - at most 64, the lanes of
+	// its filter wavefront - for the whole batch, as k_leaf_noisefiltpan's does: spread first (one workgroup per CU, 256),
+	// then fill.  A2AMD_F2VPW forces the voices per workgroup.
+	const ListRange o3f = c->leaf[LEAF_OSC3FILTPAN];
+	if(o3f.count && c->n_o3f_quiet) {
+		const int vpg = std::min(std::max(c->sw.f2vpw ? c->sw.f2vpw : (o3f.count + 255) / 256, 1), 64);
+		if(a2d_launch_leaf_osc3filtpan(c->d_params, c->hparams, list + o3f.first, o3f.count, vpg, c->stream))
+			return c->fail(A2AMD_EHIP, "3-osc filter leaf launch failed: %s", hipGetErrorString(hipGetLastError()));
+		++c->stats.launches;
+		c->last_osc3filt.launched = 1;
+		c->last_osc3filt.vpg = (uint32_t)vpg;
+		c->last_osc3filt.workgroups = (uint32_t)((o3f.count + vpg - 1) / vpg);
+	}
 	const ListRange osc2pan = c->leaf[LEAF_OSC2PAN];
 	if(osc2pan.count && none_quiet(1, osc2pan.count))
 		++c->vm.quiet_skipped;
@@ -2036,6 +2092,11 @@ static int issue_leaf_phase(a2amd_ctx *c, bool consume, bool consume_sub, hipEve
 	c->last_bare.gliding_voices = c->n_bare_gliding;
 	c->last_bare.record_voices = c->n_bare_records;
 	c->last_bare.mono_drivers = c->n_mono_drivers;
+	c->last_osc3filt = a2amd_osc3filt_batch_info{};
+	c->last_osc3filt.class_voices = (uint32_t)c->leaf[LEAF_OSC3FILTPAN].count;
+	c->last_osc3filt.quiet_voices = c->n_o3f_quiet;
+	c->last_osc3filt.gliding_voices = c->n_o3f_gliding;
+	c->last_osc3filt.record_voices = c->n_o3f_records;
 	c->last_osc2 = a2amd_osc2_batch_info{};
 	// The batch's other leaf kernels - the quiet kernels of the classes, the records kernels where the window kernels
 	// are not in use, the general kernel - as a block that runs once: normally behind the window kernels, and

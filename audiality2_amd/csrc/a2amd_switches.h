@@ -23,7 +23,7 @@ static inline int within(const char *name, int lo, int hi) { const int v = num(n
 	X(int, dbg_walk, a2sw::num("A2AMD_DBG_WALK", 0))	/* 0. Bits: 1 a2amd_voice_process() never takes its short path, 2 ... never reports the default window (debugging the walk) */ \
 	X(int, debug, a2sw::num("A2AMD_DEBUG", 0))		/* 0. A2DParams::debug, ablations: 1 no bus atomics (breaks the audio on purpose), 4 no shadow lanes in the FM kernel, 8 k_leaf_oscfiltpan's wavefronts add to the bus themselves, not through the workgroup's LDS sums, 16 k_leaf_osc2pan walks no super-chunk voice by voice (a launch argument; include/a2amd_osc2.h), 1 << 17 that walk stages no mip level in LDS (a launch argument; include/a2amd_osc2lds.h) */ \
 	X(bool, debug_noise, a2sw::set("A2AMD_DEBUG_NOISE"))	/* unset. Set: trace the noise oscillators' seeds (debugging aid) */ \
-	X(int, f2vpw, a2sw::num("A2AMD_F2VPW", 0))		/* 0 = the launcher's own choice: voices per workgroup of k_leaf_osc2filtpan */ \
+	X(int, f2vpw, a2sw::num("A2AMD_F2VPW", 0))		/* 0 = the launcher's own choice: voices per workgroup of k_leaf_osc2filtpan; and, clamped to 1..64, of k_leaf_osc3filtpan (0: by count) */ \
 	X(bool, fmvpw_set, a2sw::set("A2AMD_FMVPW")) X(int, fmvpw, a2sw::num("A2AMD_FMVPW", 0))	/* unset = by count: voices per wavefront of k_leaf_fmpan. Set: no one-launch FM path */ \
 	X(bool, fvpw_set, a2sw::set("A2AMD_FVPW")) X(int, fvpw, a2sw::num("A2AMD_FVPW", 0))	/* unset = by count: voices per wavefront of k_leaf_oscfiltpan */ \
 	X(bool, hosttiming, a2sw::set("A2AMD_HOSTTIMING")) X(int, hosttiming_level, a2sw::num("A2AMD_HOSTTIMING", 0))	/* unset: host timing counters and their dump at exit; the level (2, 3) adds per-batch traces */ \

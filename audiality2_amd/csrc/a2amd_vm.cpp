@@ -531,8 +531,9 @@ int vm_take_back(a2amd_ctx *c, int vi, bool inclusive, a2amd_vm_state *out, a2am
 	if((size_t)slot < m.snap_have.size())
 		m.snap_have[slot] = 0;
 	vv.vm = -1;
-	// (a bare wtosc is of k_leaf_oscbare's class only while the host makes its records: classified anew)
-	if(vv.nunits == 1 && c->units[vv.unit[0]].kind == A2AMD_WTOSC) {
+	// (a bare wtosc is of k_leaf_oscbare's class only while the host makes its records: classified anew; a three-oscillator
+	// chain of k_leaf_osc3filtpan's likewise)
+	if((vv.nunits == 1 && c->units[vv.unit[0]].kind == A2AMD_WTOSC) || (vv.nunits == 5 && c->units[vv.unit[2]].kind == A2AMD_WTOSC)) {
 		vv.cls_stale = true;
 		c->lists_dirty = true;
 	}
@@ -1576,8 +1577,9 @@ int a2amd_vm_adopt(a2amd_ctx *c, int head, int prog, const a2amd_vm_state *st, c
 	m.pending.push_back(slot);
 	v.vm = slot;
 	// (a bare wtosc leaves k_leaf_oscbare's class for the general kernel, which takes a voice with or without records:
-	// whether the device VM writes it any in a batch the host cannot tell)
-	if(v.nunits == 1 && c->units[v.unit[0]].kind == A2AMD_WTOSC) {
+	// whether the device VM writes it any in a batch the host cannot tell; a three-oscillator chain leaves
+	// k_leaf_osc3filtpan's class the same way)
+	if((v.nunits == 1 && c->units[v.unit[0]].kind == A2AMD_WTOSC) || (v.nunits == 5 && c->units[v.unit[2]].kind == A2AMD_WTOSC)) {
 		v.cls_stale = true;
 		c->lists_dirty = true;
 	}

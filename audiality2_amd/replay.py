@@ -126,6 +126,15 @@ class a2amd_bare_batch_info(C.Structure):
         return "bare_batch_info(" + ", ".join(f"{n}={getattr(self, n)}" for n, _ in self._fields_) + ")"
 
 
+class a2amd_osc3filt_batch_info(C.Structure):
+    """include/a2amd_osc3filt.h: who rendered the 3 x wtosc-filter12-panmix voices of the most recent batch"""
+    _fields_ = [(n, C.c_uint32) for n in ("launched", "class_voices", "quiet_voices", "gliding_voices", "record_voices",
+                                          "vpg", "workgroups", "reserved")]
+
+    def __repr__(self):
+        return "osc3filt_batch_info(" + ", ".join(f"{n}={getattr(self, n)}" for n, _ in self._fields_) + ")"
+
+
 class a2amd_osc2_batch_info(C.Structure):
     """include/a2amd_osc2.h: how k_leaf_osc2pan walked the settled voices of the most recent batch"""
     _fields_ = [(n, C.c_uint32) for n in ("launched", "voices", "vpw", "ysplit", "voice_major", "superchunks_voice_major",
@@ -230,6 +239,9 @@ class Backend:
         self._last_batch_bare = None
         if hasattr(lib, prefix + "last_batch_bare"):
             self._last_batch_bare = fn("last_batch_bare", i32, vp, C.POINTER(a2amd_bare_batch_info))
+        self._last_batch_osc3filt = None
+        if hasattr(lib, prefix + "last_batch_osc3filt"):
+            self._last_batch_osc3filt = fn("last_batch_osc3filt", i32, vp, C.POINTER(a2amd_osc3filt_batch_info))
         self._last_batch_osc2 = None
         if hasattr(lib, prefix + "last_batch_osc2"):
             self._last_batch_osc2 = fn("last_batch_osc2", i32, vp, C.POINTER(a2amd_osc2_batch_info))
@@ -401,6 +413,16 @@ class Backend:
             raise RuntimeError(f"this library has no {self.prefix}last_batch_bare")
         bi = a2amd_bare_batch_info()
         self._chk(self._last_batch_bare(self.ctx, C.byref(bi)), "last_batch_bare")
+        return bi
+
+    def last_batch_osc3filt(self):
+        """a2amd_last_batch_osc3filt: whether k_leaf_osc3filtpan was launched for the most recent batch, the voices of its
+        launch class (3 x wtosc; filter12; panmix) by who rendered them - the kernel (of which still gliding), the general
+        kernel (those with a run) - its voices per workgroup and its workgroups"""
+        if self._last_batch_osc3filt is None:
+            raise RuntimeError(f"this library has no {self.prefix}last_batch_osc3filt")
+        bi = a2amd_osc3filt_batch_info()
+        self._chk(self._last_batch_osc3filt(self.ctx, C.byref(bi)), "last_batch_osc3filt")
         return bi
 
     def last_batch_osc2(self):

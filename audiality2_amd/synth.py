@@ -304,6 +304,16 @@ class Scene:
                 oscs, pan = units[:2], units[3]
                 be.unit_write(units[2], 0, p + fix(2.5))      # cutoff
                 be.unit_write(units[2], 1, fix(3.0))          # q
+            elif chain == "osc3-filter-pan":
+                # `struct { wtosc; wtosc o2; wtosc o3; filter12; panmix }`: the three-oscillator subtractive lead
+                units = [be.unit_init(key, K_WTOSC, 0, 0, 1, 0),
+                         be.unit_init(key, K_WTOSC, PROCADD, 0, 1, 0),
+                         be.unit_init(key, K_WTOSC, PROCADD, 0, 1, 0),
+                         be.unit_init(key, K_FILTER12, 0, 1, 1, 0),
+                         be.unit_init(key, K_PANMIX, PROCADD, 1, 2, 1)]
+                oscs, pan = units[:3], units[4]
+                be.unit_write(units[3], 0, p + fix(2.5))      # cutoff
+                be.unit_write(units[3], 1, fix(3.0))          # q
             elif chain == "osc2-pan":
                 units = [be.unit_init(key, K_WTOSC, 0, 0, 1, 0),
                          be.unit_init(key, K_WTOSC, PROCADD, 0, 1, 0),
@@ -364,7 +374,8 @@ class Scene:
             for j, o in enumerate(oscs):
                 be.unit_write(o, 0, self.private_ids[(k + j) % len(self.private_ids)] if private else
                               self.wave_ids[(7 * k + j) % len(self.wave_ids)])
-                be.unit_write(o, 1, p + (fix(0.01) if j == 0 else -fix(0.01)) * (len(oscs) > 1))
+                # (a third oscillator: an octave down)
+                be.unit_write(o, 1, p - fix(1.0) if j == 2 else p + (fix(0.01) if j == 0 else -fix(0.01)) * (len(oscs) > 1))
                 be.unit_write(o, 2, amp)
                 be.unit_write(o, 3, (k * 2654435761) % 65536)
             if pan is not None:
