@@ -86,9 +86,14 @@ struct A2DWave {
 	uint32_t period;
 	uint32_t size[A2D_MIPS];
 	uint32_t off[A2D_MIPS];
-	uint32_t periodic;	// bit l: level l's pads are the periodic continuation of its payload (a2amd_wavepads.h; set by
+	// (two half words in the place of the one word 'periodic' had before 'tame' came: A2D_MIPS bits each, and the struct
+	// keeps its 96 bytes - every kernel that indexes waves[] keeps its instructions)
+	uint16_t periodic;	// bit l: level l's pads are the periodic continuation of its payload (a2amd_wavepads.h; set by
 				// a2amd_wave_upload from the samples it is handed, clear for the waves the device renders)
+	uint16_t tame;		// bit l: no product of a2_Hermite wraps anywhere in level l (a2amd_wavetame.h; set and cleared as periodic is)
 };
+
+static_assert(A2D_MIPS <= 16 && sizeof(A2DWave) == 96, "A2DWave: a bit per level in a half word, 96 bytes");
 
 // one voice = one unit chain (host owned)
 struct A2DVoice {
@@ -228,6 +233,9 @@ struct A2DParams {
 	int32_t         debug;		// A2AMD_DEBUG ablation bits (perf experiments only)
 	uint8_t         fragframes[A2D_MAXBATCH];
 	uint16_t        fragstart[A2D_MAXBATCH];	// frames before each fragment
+	// (last: the members above keep the offsets every other kernel was compiled with)
+	const int32_t  *wavecoef4;	// [wave pool index][4]: a, b << 8, c << 8, d0 << 8 of the window at that sample, for the fused steps on
+					// tame levels (a2amd_wavetame.h; k_leaf_osc2pan), or null: the pool outgrew the footprint policy's entries
 };
 
 // How k_leaf_osc2pan walks a batch, for the kernel and for the host's report of it (include/a2amd_osc2.h) alike.
@@ -265,6 +273,15 @@ A2D_HD unsigned a2d_osc2_stage(unsigned size0, unsigned periodic0, unsigned size
 	const bool c0 = periodic0 && size0 && !(size0 & (size0 - 1)) && size0 <= A2D_OSC2_LDS_ENT;
 	const bool c1 = periodic1 && size1 && !(size1 & (size1 - 1)) && size1 <= A2D_OSC2_LDS_ENT;
 	return (c0 ? 1u : 0u) | (c1 && (c0 ? size0 : 0u) + size1 <= A2D_OSC2_LDS_ENT ? 2u : 0u);
+}
+
+// Does a settled voice of k_leaf_osc2pan's voice-major walk take the fused multiply-add steps (a2amd_taps.h:
+// hermite_fused)?  When both its oscillators play tame levels (A2DWave::tame).  Its staged levels (a2d_osc2_stage, the
+// same rule and the same masks for both kinds of voices) are then copied to LDS as 16 byte entries: A2D_OSC2_LDS_ENT of
+// them are 2 048 bytes a wavefront, and the kernel's four workgroups still fit a CU's 160 KiB together.
+A2D_HD unsigned a2d_osc2_tame(unsigned tame0, unsigned tame1)
+{
+	return tame0 && tame1 ? 1u : 0u;
 }
 
 // A noise oscillator's default window - a fragment without records for its voice - takes the engine's RNG word from
@@ -422,7 +439,7 @@ int a2d_launch_add_bus(int32_t *dst, int32_t *src, unsigned words, void *stream)
 // bus[f][ch][64] (nch channels per fragment) += inj[f][ch][64] (8 channels per fragment), ch < n
 int a2d_launch_add_inject(const int32_t *inj, int32_t *bus, int nch, int n, int nfrags, void *stream);
 // Hermite coefficient entries for wave pool samples [lo, hi) (reads pool[lo-1 .. hi+1])
-int a2d_launch_build_coef(const int16_t *pool, int *coef, unsigned lo, unsigned hi, void *stream);
+int a2d_launch_build_coef(const int16_t *pool, int *coef, int *coef4, unsigned lo, unsigned hi, void *stream);	// (coef4: the 16 byte table, or null)
 // a2amd_wavecap.hip
 int a2d_launch_capture(const int32_t *bus, int32_t *dst, const uint32_t *fragpos, int nfrags, int nch, void *stream);
 int a2d_launch_wave_from_pcm(const int32_t *pcm, int16_t *pool, const uint32_t *off, const uint32_t *size, int levels, int looped,
@@ -443,7 +460,7 @@ int a2d_launch_leaf_oscfiltpan(const A2DParams *dparams, const A2DParams &hp, co
 int a2d_launch_scatter_runs(const int *didx, const A2DRun *dval, int n, A2DRun *druns, void *stream);
 int a2d_launch_leaf_osc2pan(const A2DParams *dparams, const A2DParams &hp, const int *dlist, int nlist,
 		int vpw, int ysplit, int *ustage, unsigned char *staged, void *stream, A2DCommit *defer, int voice_major, int lds_taps,
-		int *ysplit_used);
+		int tame, unsigned long long *tame_count, int *ysplit_used);
 // wtosc[+wtosc] [-> filter12] -> panmix voices that carry records this batch (nosc = 1 | 2, filt = 0 | 1)
 // skip_empty: the list's voices get their records from the device VM (a2amd_vm.hip); those it left
 // without any this batch are rendered by their class's quiet kernel

@@ -36,7 +36,9 @@
 
 #include "a2amd_taps.h"
 
-__global__ void k_build_coef(const int16_t *__restrict__ pool, int *__restrict__ coef, unsigned lo, unsigned hi)
+// (coef4: the 16 byte entries of the fused steps, a2amd_taps.h: hermite_fused - or null, the host keeps no such table)
+__global__ void k_build_coef(const int16_t *__restrict__ pool, int *__restrict__ coef, int *__restrict__ coef4, unsigned lo,
+		unsigned hi)
 {
 	const unsigned j = lo + blockIdx.x * blockDim.x + threadIdx.x;
 	if(j >= hi)
@@ -49,14 +51,16 @@ __global__ void k_build_coef(const int16_t *__restrict__ pool, int *__restrict__
 	e[0] = a;
 	e[1] = b;
 	e[2] = (int)(((unsigned)c << 16) | ((unsigned)d0 & 0xffffu));
+	if(coef4)
+		*(Coef4x *)(coef4 + 4 * (size_t)j) = Coef4x{ a, (int)((unsigned)b << 8), (int)((unsigned)c << 8), (int)((unsigned)d0 << 8) };
 }
 
 // coefficient entries for pool samples [lo, hi): needs pool[lo - 1 .. hi + 1]
-int a2d_launch_build_coef(const int16_t *pool, int *coef, unsigned lo, unsigned hi, void *stream)
+int a2d_launch_build_coef(const int16_t *pool, int *coef, int *coef4, unsigned lo, unsigned hi, void *stream)
 {
 	if(hi <= lo)
 		return 0;
-	hipLaunchKernelGGL(k_build_coef, dim3((hi - lo + 255) / 256), dim3(256), 0, (hipStream_t)stream, pool, coef, lo, hi);
+	hipLaunchKernelGGL(k_build_coef, dim3((hi - lo + 255) / 256), dim3(256), 0, (hipStream_t)stream, pool, coef, coef4, lo, hi);
 	return (int)hipGetLastError();
 }
 
@@ -309,7 +313,9 @@ enum { DV_SETTLED = 0, DV_MM, DV_DPH, DV_SIZEM, DV_DOFF, DV_V0, DV_V1, DV_NWORDS
 // mip level, increment there, that level's size and place in the pool.  False: no wave for the settled paths - or
 // 'settled' was false already, and then the descriptor's test words are not read (k_leaf_osc2pan's second oscillator).
 // periodic: A2DWave::periodic's bit of that level (k_leaf_osc2pan: may the level be copied to LDS)
-DEV bool settled_wave(const A2DWave *w, unsigned dphase, int *d, bool settled = true, unsigned *periodic = nullptr)
+// tame: A2DWave::tame's bit of it (k_leaf_osc2pan: may the level's taps take the fused steps)
+DEV bool settled_wave(const A2DWave *w, unsigned dphase, int *d, bool settled = true, unsigned *periodic = nullptr,
+		unsigned *tame = nullptr)
 {
 	unsigned dph;
 	const unsigned mm = a2s_mip(dphase, w->period, &dph);
@@ -319,6 +325,8 @@ DEV bool settled_wave(const A2DWave *w, unsigned dphase, int *d, bool settled = 
 	d[3] = (int)w->off[mm];
 	if(periodic)
 		*periodic = (w->periodic >> mm) & 1u;
+	if(tame)
+		*tame = (w->tame >> mm) & 1u;
 	return settled && a2s_wave_ok(w->size[0], w->flags, dph);
 }
 
@@ -741,6 +749,10 @@ DEV void osc_to_lanes(int (&so)[OV_NWORDS], const OscS &o, bool me)
 // of the last of the chunk's nf real fragments, wtosc.c:284: its wrapped start plus its frames x the increment.
 // ST: a2d_osc2_stage()'s mask - oscillator o with its bit set reads its entries from the wavefront's copy of the level
 // in LDS, lv.level[o] (1 << lv.lg[o] entries), the other from the table (lv is not read where ST is 0).
+// TAME: both oscillators play tame levels (a2d_osc2_tame) - crs and s.cb are then the 16 byte table's, a staged level is
+// a copy in that table's layout with lv.lg[o] = (size - 1) << 4, and the taps take the fused steps (hermite_fused).
+template<bool TAME> struct Osc2Entry { typedef Coef4 T; };
+template<> struct Osc2Entry<true> { typedef Coef4x T; };
 struct Osc2Voice {
 	unsigned dph[2], sizem[2];
 	int cb[2], amp[2];
@@ -751,14 +763,16 @@ struct Osc2Lds {
 	unsigned lg[2];
 };
 
-template<bool WHOLE, int ST = 0>
+template<bool WHOLE, int ST = 0, bool TAME = false>
 DEV void osc2_chunk(const CoefRsrc &crs, Osc2Voice &s, const unsigned (&ldph)[2], const int (&nfr)[OSC2_FCH],
 		const unsigned (&pre)[OSC2_FCH], int nf, bool park, int (&xs)[OSC2_FCH], const Osc2Lds &lv = Osc2Lds())
 {
 	// the coefficient entries of BOTH oscillators (4 fragments x 2 taps x 2: 48 registers) are in
 	// flight before either is used (one oscillator after the other, 24 registers in flight at a
-	// time, was 4 % slower)
-	Coef4 ka[2][OSC2_FCH], kb[2][OSC2_FCH];
+	// time, was 4 % slower).  TAME: the 16 byte entries of both would be 64 registers, and the loop then spills 9 vector
+	// registers at 4 wavefronts per SIMD.  There 32 registers are in flight at a time, in halves: the second oscillator's
+	// entries are asked for, two fragments at a time, as the first oscillator's are used up (profiles/osc2_tame.md).
+	typename Osc2Entry<TAME>::T ka[2][TAME ? OSC2_FCH / 2 : OSC2_FCH], kb[2][TAME ? OSC2_FCH / 2 : OSC2_FCH];
 	unsigned pa[2][OSC2_FCH], pb[2][OSC2_FCH];
 #pragma unroll
 	for(int o = 0; o < 2; ++o) {
@@ -785,7 +799,9 @@ DEV void osc2_chunk(const CoefRsrc &crs, Osc2Voice &s, const unsigned (&ldph)[2]
 			pa[o][j] = tap_phase(phs[j], ldph[o]);
 			asm("" : "+v"(pa[o][j]));	// (32 bit offsets: scalar-base loads, as in k_leaf_oscpan)
 			pb[o][j] = pa[o][j] + (dph >> 17);
-			if((ST >> o) & 1) {
+			if constexpr(TAME) {
+				// (fetched below)
+			} else if((ST >> o) & 1) {
 				ka[o][j] = coef_lds(lv.level[o], pa[o][j], lv.lg[o]);
 				kb[o][j] = coef_lds(lv.level[o], pb[o][j], lv.lg[o]);
 			} else {
@@ -803,27 +819,69 @@ DEV void osc2_chunk(const CoefRsrc &crs, Osc2Voice &s, const unsigned (&ldph)[2]
 		}
 		s.ph[o] = ph;
 	}
+	if constexpr(TAME) {
+		// Steps of two fragments (H): oscillator 0's first and second half are asked for; then, before each half is used,
+		// the half of oscillator 1 that will take its registers.  The scheduler is held to that order: left alone it starts
+		// on the arithmetic at once and waits for every entry in turn.
+		constexpr int H = OSC2_FCH / 2;
+		auto fetch = [&](int o, int h, int slot) {
 #pragma unroll
-	for(int o = 0; o < 2; ++o)
+			for(int j = 0; j < H; ++j) {
+				if((ST >> o) & 1) {
+					ka[slot][j] = coef4_lds(lv.level[o], pa[o][h * H + j], lv.lg[o]);
+					kb[slot][j] = coef4_lds(lv.level[o], pb[o][h * H + j], lv.lg[o]);
+				} else {
+					ka[slot][j] = coef4_at(crs, s.cb[o], pa[o][h * H + j]);
+					kb[slot][j] = coef4_at(crs, s.cb[o], pb[o][h * H + j]);
+				}
+			}
+		};
+		auto use = [&](int o, int h, int slot) {
 #pragma unroll
-		for(int j = 0; j < OSC2_FCH; ++j) {
-			const int y = mul64s(inter_coefs(ka[o][j], pa[o][j], kb[o][j], pb[o][j]), s.amp[o], 17);
-			// the second oscillator adds into the scratch buffer (wrap-around)
-			xs[j] = o ? wadd(xs[j], y) : y;
-		}
+			for(int j = 0; j < H; ++j) {
+				const int x = wadd(hermite_fused(ka[slot][j], pa[o][h * H + j]), hermite_fused(kb[slot][j], pb[o][h * H + j]));
+				const int y = mul64s(x, s.amp[o], 17);
+				xs[h * H + j] = o ? wadd(xs[h * H + j], y) : y;
+			}
+		};
+		fetch(0, 0, 0);
+		fetch(0, 1, 1);
+		__builtin_amdgcn_sched_barrier(0);
+		use(0, 0, 0);
+		__builtin_amdgcn_sched_barrier(0);
+		fetch(1, 0, 0);
+		__builtin_amdgcn_sched_barrier(0);
+		use(0, 1, 1);
+		__builtin_amdgcn_sched_barrier(0);
+		fetch(1, 1, 1);
+		__builtin_amdgcn_sched_barrier(0);
+		use(1, 0, 0);
+		use(1, 1, 1);
+		return;
+	} else {
+#pragma unroll
+		for(int o = 0; o < 2; ++o)
+#pragma unroll
+			for(int j = 0; j < OSC2_FCH; ++j) {
+				const int y = mul64s(inter_coefs(ka[o][j], pa[o][j], kb[o][j], pb[o][j]), s.amp[o], 17);
+				// the second oscillator adds into the scratch buffer (wrap-around)
+				xs[j] = o ? wadd(xs[j], y) : y;
+			}
+	}
 }
 
 // a voice's constants for osc2_chunk() out of the lanes that keep them, its phases at the frame 'before' of the batch
-// (mm: the level of each, for the way back to the state's phase)
+// (mm: the level of each, for the way back to the state's phase; tame: its table is the 16 byte one)
 DEV void osc2_voice_from_lanes(Osc2Voice &s, unsigned (&ldph)[2], unsigned (&mm)[2], const int (&od)[2][OD_NWORDS],
-		const int (&amp_l)[2], const int (&phlo_l)[2], const int (&phhi_l)[2], int v, unsigned before, int lane)
+		const int (&amp_l)[2], const int (&phlo_l)[2], const int (&phhi_l)[2], int v, unsigned before, int lane,
+		bool tame = false)
 {
 #pragma unroll
 	for(int o = 0; o < 2; ++o) {
 		mm[o] = (unsigned)rdl(od[o][OD_MM], v);
 		s.dph[o] = (unsigned)rdl(od[o][OD_DPH], v);
 		s.sizem[o] = (unsigned)rdl(od[o][OD_SIZEM], v);
-		s.cb[o] = coef_base((unsigned)rdl(od[o][OD_DOFF], v));
+		s.cb[o] = tame ? coef4_base((unsigned)rdl(od[o][OD_DOFF], v)) : coef_base((unsigned)rdl(od[o][OD_DOFF], v));
 		s.amp[o] = rdl(amp_l[o], v);
 		const uint64_t phase = (uint64_t)(unsigned)rdl(phlo_l[o], v) | ((uint64_t)(unsigned)rdl(phhi_l[o], v) << 32);
 		s.ph[o] = (phase >> mm[o]) + (uint64_t)before * s.dph[o];
@@ -833,7 +891,7 @@ DEV void osc2_voice_from_lanes(Osc2Voice &s, unsigned (&ldph)[2], unsigned (&mm)
 
 // One settled voice over a super-chunk of nsc chunks - nfs whole fragments - on the voice-major walk: its samples into
 // the wavefront's tile, and behind the batch's last chunk (last) its end phases back into lane v.
-template<int ST>
+template<int ST, bool TAME = false>
 DEV void osc2_voice_chunks(const CoefRsrc &crs, Osc2Voice &s, const unsigned (&ldph)[2], const unsigned (&mm)[2],
 		const Osc2Lds &lv, int nsc, int nfs, bool last, int v0, int v1, int v, int lane, int (*tile)[2][A2D_FRAG],
 		int (&phlo_l)[2], int (&phhi_l)[2])
@@ -845,7 +903,7 @@ DEV void osc2_voice_chunks(const CoefRsrc &crs, Osc2Voice &s, const unsigned (&l
 		// phases inside the wave - and never flushed)
 		const bool park = last && k == nsc - 1;
 		int xs[OSC2_FCH];
-		osc2_chunk<true, ST>(crs, s, ldph, nopre_i, nopre_u, nfs - k * OSC2_FCH, park, xs, lv);
+		osc2_chunk<true, ST, TAME>(crs, s, ldph, nopre_i, nopre_u, nfs - k * OSC2_FCH, park, xs, lv);
 #pragma unroll
 		for(int j = 0; j < OSC2_FCH; ++j) {
 			tile_add(&tile[k * OSC2_FCH + j][0][lane], mul64s(xs[j], v0, 24));
@@ -866,12 +924,17 @@ DEV void osc2_voice_chunks(const CoefRsrc &crs, Osc2Voice &s, const unsigned (&l
 // A super-chunk of nsc chunks - nfs whole fragments from fragment fa on - walked voice by voice: every settled voice of
 // the wavefront's nv in turn, the tile flushed where the bus changes and at the end.  STAGE: voices may have levels to
 // copy to LDS (the mask rides in settled_l above the settled bit); without it every voice takes the gathers' body.
-template<bool STAGE>
+// TAME (implies STAGE's choices): voices may be tame as well (bit 3 of settled_l) - those read the 16 byte table
+// wavecoef4 through crs4, stage their levels in its layout and take the fused steps' bodies.
+template<bool STAGE, bool TAME = false>
 DEV void osc2_superchunk(const CoefRsrc &crs, const int *wavecoef, int *busmem, const int (&od)[2][OD_NWORDS],
 		const int (&amp_l)[2], int (&phlo_l)[2], int (&phhi_l)[2], int settled_l, int my_off, int my_nch, int v0l, int v1l,
 		int nv, int nsc, int fa, int nfs, bool last, unsigned before, int lane, int dbg, int (*tile)[2][A2D_FRAG],
-		LdsInt *level)
+		LdsInt *level, const int *wavecoef4 = nullptr)
 {
+	CoefRsrc crs4 = crs;
+	if(TAME)
+		crs4 = coef4_rsrc(wavecoef4);
 	int cur_off = rdl(my_off, 0), cur_nch = rdl(my_nch, 0);
 	for(int v = 0; v < nv; ++v) {
 		const int sl = rdl(settled_l, v);
@@ -886,6 +949,33 @@ DEV void osc2_superchunk(const CoefRsrc &crs, const int *wavecoef, int *busmem, 
 		const int v0 = rdl(v0l, v), v1 = rdl(v1l, v);
 		Osc2Voice s;
 		unsigned ldph[2], mm[2];
+		if(TAME && (sl & 8)) {
+			// a tame voice: the same walk on the 16 byte entries
+			osc2_voice_from_lanes(s, ldph, mm, od, amp_l, phlo_l, phhi_l, v, before, lane, true);
+			Osc2Lds lv = { { level, level }, { 0, 0 } };
+			const int st = (sl >> 1) & 3;
+			if(st) {
+				lds_wave_fence();
+				if(st & 1) {
+					lv.lg[0] = (s.sizem[0] - 1) << 4;
+					stage_level4(level, wavecoef4, s.cb[0], s.sizem[0], lane);
+				}
+				if(st & 2) {
+					LdsInt *const l1 = (st & 1) ? level + s.sizem[0] * 4 : level;
+					lv.level[1] = l1;
+					lv.lg[1] = (s.sizem[1] - 1) << 4;
+					stage_level4(l1, wavecoef4, s.cb[1], s.sizem[1], lane);
+				}
+				lds_wave_fence();
+			}
+			switch(st) {
+			case 0: osc2_voice_chunks<0, true>(crs4, s, ldph, mm, lv, nsc, nfs, last, v0, v1, v, lane, tile, phlo_l, phhi_l); break;
+			case 1: osc2_voice_chunks<1, true>(crs4, s, ldph, mm, lv, nsc, nfs, last, v0, v1, v, lane, tile, phlo_l, phhi_l); break;
+			case 2: osc2_voice_chunks<2, true>(crs4, s, ldph, mm, lv, nsc, nfs, last, v0, v1, v, lane, tile, phlo_l, phhi_l); break;
+			default: osc2_voice_chunks<3, true>(crs4, s, ldph, mm, lv, nsc, nfs, last, v0, v1, v, lane, tile, phlo_l, phhi_l); break;
+			}
+			continue;
+		}
 		osc2_voice_from_lanes(s, ldph, mm, od, amp_l, phlo_l, phhi_l, v, before, lane);
 		Osc2Lds lv = { { level, level }, { 0, 0 } };
 		if(!STAGE) {
@@ -894,6 +984,8 @@ DEV void osc2_superchunk(const CoefRsrc &crs, const int *wavecoef, int *busmem, 
 		}
 		// the voice's staged levels, oscillator 1 behind oscillator 0: lanes read what other lanes wrote, and
 		// write where other lanes read for the voice before - a wavefront fence on both sides of the stores
+		// (no tame bit above the mask here: a tame voice went the other way above, and without TAME no voice of the
+		// wavefront has one - any_tame)
 		const int st = sl >> 1;
 		if(st) {
 			lds_wave_fence();
@@ -922,12 +1014,19 @@ DEV void osc2_superchunk(const CoefRsrc &crs, const int *wavecoef, int *busmem, 
 #define OSC2_WPE 4	// (round 2: 3 wavefronts per SIMD with 143 registers and no spills beat 4 with 128 and 39 spills by a
 			// fifth.  Round 3: with only the settled loop's values parked in registers the kernel needs 118 -
 			// 4 wavefronts without spills: 2.30 -> 2.24 ms at configs[3]; 3 wavefronts of the same code: 2.40)
+// TAME_K: the kernel that holds the tame voices' bodies.  It is compiled twice: with the fused steps' walk in it the
+// register allocator spills 198 scalar registers where it spilled 108, and the lane moves cost the OTHER voices' walks
+// 1 - 2 % (profiles/osc2_tame.md) - so a launch in which no voice can be tame (A2AMD_DEBUG bit 18, or no 16 byte table)
+// takes the instantiation without them, which is the kernel as it was: wavecoef4, tame and tame_count are not read there.
+// tame_count: the voices given the tame bit, summed over the launches (a2amd_osc2_tame_voices(): tests).
+template<bool TAME_K>
 __global__ __launch_bounds__(64 * FAST_WPB) __attribute__((amdgpu_waves_per_eu(OSC2_WPE, OSC2_WPE)))
 void k_leaf_osc2pan(const A2DParams *__restrict__ pp, const int *__restrict__ list, int nlist, int vpw,
 		int ysplit, const A2DVoice *__restrict__ voices, const int *ustate, int *ustage,
 		const int16_t *__restrict__ wavepool, const A2DWave *__restrict__ waves,
 		const uint32_t *__restrict__ ptab, int *__restrict__ busmem, const int *__restrict__ wavecoef,
-		unsigned char *__restrict__ staged, int vmajor, int lds_taps)
+		unsigned char *__restrict__ staged, int vmajor, int lds_taps, const int *__restrict__ wavecoef4, int tame,
+		unsigned long long *__restrict__ tame_count)
 {
 	const A2DParams &p = *pp;
 	const int wv = rfl((int)(threadIdx.x >> 6));	// (wave-uniform, and known to the compiler as such)
@@ -977,7 +1076,7 @@ void k_leaf_osc2pan(const A2DParams *__restrict__ pp, const int *__restrict__ li
 		my_nch = vc.out_nch;
 		bool settled = true;
 		int wave_l[2], dphase_l[2];
-		unsigned periodic[2] = { 0, 0 };
+		unsigned periodic[2] = { 0, 0 }, tame_lv[2] = { 0, 0 };
 #pragma unroll
 		for(int o = 0; o < 2; ++o) {
 			uu[o] = vc.unit[o];
@@ -999,16 +1098,24 @@ void k_leaf_osc2pan(const A2DParams *__restrict__ pp, const int *__restrict__ li
 		if(settled) {
 #pragma unroll
 			for(int o = 0; o < 2; ++o)
-				settled = settled_wave(waves + wave_l[o], (unsigned)dphase_l[o], od[o], settled, &periodic[o]);
+				settled = settled_wave(waves + wave_l[o], (unsigned)dphase_l[o], od[o], settled, &periodic[o],
+						TAME_K ? &tame_lv[o] : nullptr);
 			a2s_pan_gains(sp[PW_VOL], sp[PW_PAN], a2s_pan_over(sp[PW_PAN]), &v0l, &v1l);
 		}
-		// (bit 0: settled; bits 1 and 2: which of its oscillators the voice-major walk reads from LDS)
+		// (bit 0: settled; bits 1 and 2: which of its oscillators the voice-major walk reads from LDS; bit 3: that walk
+		// takes the fused steps for it, a2d_osc2_tame)
 		settled_l = settled ? 1 : 0;
 		if(settled && lds_taps)
 			settled_l |= (int)a2d_osc2_stage((unsigned)od[0][OD_SIZEM], periodic[0], (unsigned)od[1][OD_SIZEM], periodic[1]) << 1;
+		if(TAME_K && settled && tame)
+			settled_l |= (int)a2d_osc2_tame(tame_lv[0], tame_lv[1]) << 3;
 	}
 	const unsigned long long unsettled_mask = __ballot(mine && !settled_l);
-	const bool any_staged = __ballot(settled_l > 1) != 0;
+	const bool any_staged = __ballot((settled_l & 6) != 0) != 0;
+	const unsigned long long tame_mask = TAME_K ? __ballot((settled_l & 8) != 0) : 0ull;
+	const bool any_tame = tame_mask != 0;
+	if(TAME_K && any_tame && slice == 0 && lane == 0)
+		atomicAdd(tame_count, (unsigned long long)__popcll(tame_mask));
 
 	// ---- settled voices: this slice, in super-chunks of up to OSC2_SCH fragments ----
 	// One of whole fragments only (a2d_osc2_whole) is walked voice by voice: a voice's constants leave their lanes
@@ -1019,8 +1126,11 @@ void k_leaf_osc2pan(const A2DParams *__restrict__ pp, const int *__restrict__ li
 	// On the voice-major walk a voice's small mip levels (a2d_osc2_stage: periodic pads, a power of two of at most
 	// A2D_OSC2_LDS_ENT entries together) are copied to this wavefront's own 1 536 bytes of LDS first, and their taps read
 	// there instead of gathered through the texture addressers (lds_taps off - A2AMD_DEBUG bit 17 - no voice has the bits).
+	// A voice both of whose levels are tame (a2amd_wavetame.h: no product of the interpolation wraps there) takes the fused
+	// multiply-add steps on that walk, from the 16 byte table and from 16 byte copies: 2 048 bytes of LDS a wavefront
+	// (tame off - A2AMD_DEBUG bit 18, or no such table - no voice has the bit, and the walk is the one without it).
 	__shared__ int tiles[FAST_WPB][OSC2_SCH][2][A2D_FRAG];
-	__shared__ int levels[FAST_WPB][A2D_OSC2_LDS_ENT * A2D_COEF_WORDS];
+	__shared__ __attribute__((aligned(16))) int levels[FAST_WPB][A2D_OSC2_LDS_ENT * (TAME_K ? 4 : A2D_COEF_WORDS)];
 	int (*const tile)[2][A2D_FRAG] = tiles[wv];
 	LdsInt *const level = (LdsInt *)levels[wv];
 	if(vmajor)
@@ -1036,7 +1146,10 @@ void k_leaf_osc2pan(const A2DParams *__restrict__ pp, const int *__restrict__ li
 			// (a wavefront none of whose voices stages a level - every one under A2AMD_DEBUG bit 17 - walks them through the
 			// loop without the staging and the choice of a body per voice: those cost some 30 scalar instructions and 6
 			// branches a voice and super-chunk, 1 % of the kernel's time, profiles/osc2_lds_taps.md)
-			if(any_staged)
+			if(TAME_K && any_tame)
+				osc2_superchunk<true, TAME_K>(crs, wavecoef, busmem, od, amp_l, phlo_l, phhi_l, settled_l, my_off, my_nch, v0l, v1l,
+						nv, s_hi - s_lo, fa, nfs, last, before, lane, dbg, tile, level, wavecoef4);
+			else if(any_staged)
 				osc2_superchunk<true>(crs, wavecoef, busmem, od, amp_l, phlo_l, phhi_l, settled_l, my_off, my_nch, v0l, v1l,
 						nv, s_hi - s_lo, fa, nfs, last, before, lane, dbg, tile, level);
 			else
@@ -3372,7 +3485,7 @@ int a2d_launch_leaf_oscpan(const A2DParams *dparams, const A2DParams &hp, const 
 
 int a2d_launch_leaf_osc2pan(const A2DParams *dparams, const A2DParams &hp, const int *dlist, int nlist,
 		int vpw, int ysplit, int *ustage, unsigned char *staged, void *stream, A2DCommit *defer, int voice_major, int lds_taps,
-		int *ysplit_used)
+		int tame, unsigned long long *tame_count, int *ysplit_used)
 {
 	if(nlist <= 0)
 		return 0;
@@ -3383,9 +3496,17 @@ int a2d_launch_leaf_osc2pan(const A2DParams *dparams, const A2DParams &hp, const
 		*ysplit_used = ysplit;
 	int nwaves = (nlist + vpw - 1) / vpw;
 	int nblocks = (nwaves + FAST_WPB - 1) / FAST_WPB;
-	hipLaunchKernelGGL(k_leaf_osc2pan, dim3(nblocks, ysplit), dim3(64 * FAST_WPB), 0, (hipStream_t)stream,
-			dparams, dlist, nlist, vpw, ysplit, hp.voices, (const int *)hp.ustate,
-			ysplit > 1 ? ustage : hp.ustate, hp.wavepool, hp.waves, hp.ptab, hp.busmem, hp.wavecoef, staged, voice_major, lds_taps);
+	// (no voice can be tame: the kernel without the tame bodies, k_leaf_osc2pan<TAME_K>'s comment)
+	if(tame && hp.wavecoef4 && tame_count)
+		hipLaunchKernelGGL(k_leaf_osc2pan<true>, dim3(nblocks, ysplit), dim3(64 * FAST_WPB), 0, (hipStream_t)stream,
+				dparams, dlist, nlist, vpw, ysplit, hp.voices, (const int *)hp.ustate,
+				ysplit > 1 ? ustage : hp.ustate, hp.wavepool, hp.waves, hp.ptab, hp.busmem, hp.wavecoef, staged, voice_major, lds_taps,
+				hp.wavecoef4, 1, tame_count);
+	else
+		hipLaunchKernelGGL(k_leaf_osc2pan<false>, dim3(nblocks, ysplit), dim3(64 * FAST_WPB), 0, (hipStream_t)stream,
+				dparams, dlist, nlist, vpw, ysplit, hp.voices, (const int *)hp.ustate,
+				ysplit > 1 ? ustage : hp.ustate, hp.wavepool, hp.waves, hp.ptab, hp.busmem, hp.wavecoef, staged, voice_major, lds_taps,
+				(const int *)nullptr, 0, (unsigned long long *)nullptr);
 	if(ysplit > 1) {
 		A2DCommit cm = { dlist, nlist, 2, ustage, staged };
 		if(defer)

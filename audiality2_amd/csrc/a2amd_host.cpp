@@ -18,6 +18,7 @@
 #include "a2amd_cutsweep.h"
 #include "a2amd_settled.h"
 #include "a2amd_wavepads.h"
+#include "a2amd_wavetame.h"
 
 namespace a2h { thread_local char g_err[256] = ""; }
 
@@ -87,6 +88,12 @@ int a2amd_open(const a2amd_config *cfg, a2amd_ctx **out)
 	c->d_wavepool.cap = 8u << 20;
 	OPENCHK(hipMalloc((void **)&c->d_wavecoef.d, (size_t)(8u << 20) * A2D_COEF_WORDS * sizeof(int32_t)));
 	c->d_wavecoef.cap = 8u << 20;
+	if(coef4_wanted(c, 0)) {	// (not under A2AMD_RAW=1 or a budget of nothing: the policy plays samples from the start)
+		OPENCHK(hipMalloc((void **)&c->d_wavecoef4.d, (size_t)(8u << 20) * 4 * sizeof(int32_t)));
+		c->d_wavecoef4.cap = 8u << 20;
+	}
+	OPENCHK(hipMalloc((void **)&c->d_tame_count, sizeof(unsigned long long)));
+	OPENCHK(hipMemset(c->d_tame_count, 0, sizeof(unsigned long long)));
 #undef OPENCHK
 	*out = c;
 	return A2AMD_OK;
@@ -129,7 +136,7 @@ void a2amd_close(a2amd_ctx *c)
 	for(int k = 0; k < 5; ++k)
 		if(c->win_ev[k])
 			hipEventDestroy(c->win_ev[k]);
-	hipFree(c->d_waves.d); hipFree(c->d_wavepool.d); hipFree(c->d_wavecoef.d); hipFree(c->d_busmem.d);
+	hipFree(c->d_waves.d); hipFree(c->d_wavepool.d); hipFree(c->d_wavecoef.d); hipFree(c->d_wavecoef4.d); hipFree(c->d_tame_count); hipFree(c->d_busmem.d);
 	vm_close(c);
 	hipFree(c->capture.d); hipFree(c->capture.d_fragpos); hipFree(c->d_wavepost.d);
 	hipFree(c->d_fbdmem.d); hipFree(c->d_fmstate.d); hipFree(c->d_xio.d); hipFree(c->d_fmsine); hipFree(c->d_list.d); hipFree(c->d_staged.d); hipFree(c->d_scatter.d); hipFree(c->d_ptab); hipFree(c->d_blob.d);
@@ -168,11 +175,36 @@ int a2amd_get_pitch_table(const a2amd_ctx *c, uint32_t *t)
 // streaming set), every wave of 4 096 samples or more is played from its samples.  A2AMD_RAW=0 / 1 forces
 // the choice for all waves (A/B measurements, tests).
 namespace a2h {
+// The 16 byte table of the fused steps (k_leaf_osc2pan's tame voices) is kept only while this policy keeps coefficient
+// entries: a pool of pool_samples is not 'big' and A2AMD_RAW does not force samples.  Once it says no the table goes for
+// good, and no voice is tame for the kernel (a bank of private sample waves must not pay 16 more bytes a sample).
+bool coef4_wanted(const a2amd_ctx *c, size_t pool_samples)
+{
+	return c->sw.raw <= 0 && pool_samples * (4 * A2D_COEF_WORDS) <= ((size_t)c->sw.coef_cache_mb << 20);
+}
+
+void coef4_drop(a2amd_ctx *c)
+{
+	if(!c->d_wavecoef4.d)
+		return;
+	hipStreamSynchronize(c->stream);
+	if(c->vm.pred_stream)	// (grow() says why)
+		hipStreamSynchronize(c->vm.pred_stream);
+	hipFree(c->d_wavecoef4.d);
+	c->d_wavecoef4.d = nullptr;
+	c->d_wavecoef4.cap = 0;
+	c->waves_dirty = true;
+	drop_graphs(c);		// (the kernels take the table's address as an argument)
+	c->blob_quiet = false;
+}
+
 void wave_tap_policy(a2amd_ctx *c)
 {
 	const int force = c->sw.raw;
 	const size_t budget = (size_t)c->sw.coef_cache_mb << 20;
 	const bool big = c->wavepool_used * (4 * A2D_COEF_WORDS) > budget;
+	if(!coef4_wanted(c, c->wavepool_used))
+		coef4_drop(c);
 	for(size_t i = 0; i < c->waves.size(); ++i) {
 		HWave &w = c->waves[i];
 		if(!w.live || w.dw.type != A2AMD_WMIPWAVE)
@@ -390,14 +422,24 @@ static int wave_place(a2amd_ctx *c, uint64_t key, const a2amd_wavedesc *w, const
 		}
 	if(pos == (size_t)-1) {
 		if(c->wavepool_used + total > c->d_wavepool.cap) {
-			// (the kernels address the coefficient table by unsigned 32 bit byte offsets, A2D_COEF_WORDS words
-			// per sample: 2^32 / 12 = 357 M samples = 0.7 GB of wave data, 4.3 GB of entries)
-			if((c->wavepool_used + total) * (4 * A2D_COEF_WORDS) > (((size_t)1 << 32) - 4096))
-				return c->fail(A2AMD_ENOMEM, "wave pool beyond %zu samples", (((size_t)1 << 32) - 4096) / (4 * A2D_COEF_WORDS));
+			// The 16 byte table of the fused steps (k_leaf_osc2pan's tame voices) grows with the pool only while the
+			// footprint policy keeps coefficient entries at all (wave_tap_policy: not 'big'); a pool beyond that is a bank
+			// of private sample waves, which must not pay 16 more bytes a sample: the table goes, and no voice is tame.
+			const bool keep4 = c->d_wavecoef4.d && coef4_wanted(c, c->wavepool_used + total);
+			// (the kernels address the coefficient tables by unsigned 32 bit byte offsets: A2D_COEF_WORDS words per sample,
+			// 2^32 / 12 = 357 M samples = 0.7 GB of wave data, 4.3 GB of entries - and 16 bytes per sample, 268 M samples,
+			// while the second table exists)
+			const size_t entry = keep4 ? 16 : 4 * A2D_COEF_WORDS;
+			if((c->wavepool_used + total) * entry > (((size_t)1 << 32) - 4096))
+				return c->fail(A2AMD_ENOMEM, "wave pool beyond %zu samples", (((size_t)1 << 32) - 4096) / entry);
 			if(int r = grow(c, c->d_wavepool, c->wavepool_used + total, 1, true)) return r;
-			// the coefficient table follows the pool: rebuilt for what is in it
+			// the coefficient tables follow the pool: rebuilt for what is in it
 			if(int r = grow(c, c->d_wavecoef, c->d_wavepool.cap, A2D_COEF_WORDS, false)) return r;
-			if(c->wavepool_used > 3 && a2d_launch_build_coef(c->d_wavepool.d, c->d_wavecoef.d, 1,
+			if(keep4) {
+				if(int r = grow(c, c->d_wavecoef4, c->d_wavepool.cap, 4, false)) return r;
+			} else
+				coef4_drop(c);
+			if(c->wavepool_used > 3 && a2d_launch_build_coef(c->d_wavepool.d, c->d_wavecoef.d, c->d_wavecoef4.d, 1,
 					(unsigned)c->wavepool_used - 2, c->stream))
 				return c->fail(A2AMD_EHIP, "coefficient build failed");
 			c->waves_dirty = true;
@@ -419,6 +461,9 @@ static int wave_place(a2amd_ctx *c, uint64_t key, const a2amd_wavedesc *w, const
 			// (k_leaf_osc2pan may keep such a level's payload entries in LDS: a2d_osc2_stage)
 			if((w->flags & 0x100u) && a2w_pads_periodic(w->data[l], w->size[l], A2AMD_WAVEPRE, A2AMD_WAVEPOST))
 				hw.dw.periodic |= 1u << l;
+			// (... and take the fused steps on a level none of whose products wraps: a2d_osc2_tame)
+			if(a2w_level_tame(w->data[l], w->size[l], A2AMD_WAVEPRE, A2AMD_WAVEPOST))
+				hw.dw.tame |= 1u << l;
 		}
 		loff[l] = (uint32_t)(pos - pos0);
 		lsize[l] = w->size[l];
@@ -440,7 +485,7 @@ static int wave_place(a2amd_ctx *c, uint64_t key, const a2amd_wavedesc *w, const
 	} else
 		++c->waves_uploaded;
 	// Hermite coefficients of every window of the region (a2amd_fast.hip: k_build_coef)
-	if(total > 3 && a2d_launch_build_coef(c->d_wavepool.d, c->d_wavecoef.d, (unsigned)hw.pool_off + 1,
+	if(total > 3 && a2d_launch_build_coef(c->d_wavepool.d, c->d_wavecoef.d, c->d_wavecoef4.d, (unsigned)hw.pool_off + 1,
 			(unsigned)(hw.pool_off + total) - 2, c->stream))
 		return c->fail(A2AMD_EHIP, "coefficient build failed");
 	c->mwaves[id] = hw.dw;

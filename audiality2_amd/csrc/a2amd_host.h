@@ -588,6 +588,10 @@ struct a2amd_ctx {
 	DevBuf<A2DWave> d_waves;
 	DevBuf<int16_t> d_wavepool;
 	DevBuf<int32_t> d_wavecoef;	// cap in pool samples, A2D_COEF_WORDS words each (a2amd_fast.hip: Coef4)
+	DevBuf<int32_t> d_wavecoef4;	// ... and 4 words each: the fused steps' entries (a2amd_taps.h: Coef4x), kept beside it until the
+					// pool outgrows the footprint policy's entries or the policy is forced to raw taps (coef4_wanted), then
+					// dropped for good
+	unsigned long long *d_tame_count = nullptr;	// voices k_leaf_osc2pan gave the tame bit, summed over its launches (a2amd_osc2_tame_voices)
 	DevBuf<int32_t> d_busmem;
 	DevBuf<int32_t> d_fbdmem;	// cap in buffer pairs
 	DevBuf<int32_t> d_fmstate;	// cap in slots of A2D_FMSTATE words
@@ -790,6 +794,8 @@ int build_graph(a2amd_ctx *c, int slot, int steps, unsigned phases = A2AMD_RENDE
 long long now_serial(const a2amd_ctx *c);
 // a2amd_host.cpp
 void wave_tap_policy(a2amd_ctx *c);
+bool coef4_wanted(const a2amd_ctx *c, size_t pool_samples);
+void coef4_drop(a2amd_ctx *c);
 int capture_append(a2amd_ctx *c);	// a2amd_render(): the batch just rendered joins the capture
 // a2amd_render.cpp
 double *dbg_counters();	// (A2AMD_HOSTTIMING counters)

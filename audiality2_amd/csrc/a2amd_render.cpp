@@ -3,6 +3,7 @@
 // a2amd_replay, statistics.  (Split out of a2amd_host.cpp in round 3.)
 #include "a2amd_host.h"
 #include "a2amd_wavepads.h"
+#include "a2amd_wavetame.h"
 
 extern "C" {
 // ---- render -------------------------------------------------------------------------
@@ -548,6 +549,28 @@ unsigned a2amd_osc2_stage_rule(unsigned size0, int periodic0, unsigned size1, in
 int a2amd_wave_level_periodic(const int16_t *level, unsigned size)
 {
 	return a2w_pads_periodic(level, size, A2AMD_WAVEPRE, A2AMD_WAVEPOST);
+}
+
+int a2amd_wave_level_tame(const int16_t *level, unsigned size)
+{
+	return a2w_level_tame(level, size, A2AMD_WAVEPRE, A2AMD_WAVEPOST);
+}
+
+unsigned a2amd_osc2_tame_rule(int tame0, int tame1)
+{
+	return a2d_osc2_tame(tame0 != 0, tame1 != 0);
+}
+
+int a2amd_osc2_tame_voices(a2amd_ctx *c, uint64_t *out)
+{
+	if(!c || !out)
+		return A2AMD_EINVAL;
+	use_device(c);
+	unsigned long long n = 0;
+	HIPCHK(c, hipStreamSynchronize(c->stream));
+	HIPCHK(c, hipMemcpy(&n, c->d_tame_count, sizeof(n), hipMemcpyDeviceToHost));
+	*out = n;
+	return A2AMD_OK;
 }
 
 int a2amd_last_batch_fbdpan(const a2amd_ctx *c, a2amd_fbdpan_batch_info *out)

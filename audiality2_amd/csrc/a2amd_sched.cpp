@@ -1142,6 +1142,7 @@ int upload(a2amd_ctx *c)
 	p.waves = c->d_waves.d;
 	p.wavepool = c->d_wavepool.d;
 	p.wavecoef = c->d_wavecoef.d;
+	p.wavecoef4 = c->d_wavecoef4.d;
 	p.busmem = c->d_busmem.d;
 	p.fbdmem = c->d_fbdmem.d;
 	p.ptab = c->d_ptab;
@@ -1907,8 +1908,10 @@ static int launch_leaves(a2amd_ctx *c, LeafPass &lp)
 		const int voice_major = !(c->sw.debug & 16);
 		// (... bit 17: that walk stages no level in LDS, every tap is a gather - include/a2amd_osc2lds.h)
 		const int lds_taps = !(c->sw.debug & (1 << 17));
+		// (... bit 18: no voice takes the fused steps of tame levels - include/a2amd_osc2tame.h)
+		const int tame = !(c->sw.debug & (1 << 18));
 		if(a2d_launch_leaf_osc2pan(c->d_params, c->hparams, list + osc2pan.first, osc2pan.count,
-				vpw, ysplit, c->d_ustage.d, c->d_staged.d + osc2pan.first, c->stream, &pend.c[pend.n], voice_major, lds_taps, &ysplit))
+				vpw, ysplit, c->d_ustage.d, c->d_staged.d + osc2pan.first, c->stream, &pend.c[pend.n], voice_major, lds_taps, tame, c->d_tame_count, &ysplit))
 			return c->fail(A2AMD_EHIP, "2-osc leaf launch failed: %s", hipGetErrorString(hipGetLastError()));
 		// (a2amd_last_batch_osc2(): the launch as it went out; the walks follow from it and the batch's fragment lengths)
 		c->last_osc2.launched = 1;

@@ -191,6 +191,75 @@ DEV void stage_level(LdsInt *level, const int *wavecoef, int cb, unsigned size, 
 	}
 }
 
+// ---- tame levels: the fused steps (a2amd_wavetame.h) ----
+// An entry of the second table: a, b << 8, c << 8, d0 << 8 of the window at a pool sample (k_build_coef), 16 bytes, read
+// through a descriptor of its own with stride 16 - one buffer_load_dwordx4, indexed like the 12 byte entry.
+typedef int Coef4x __attribute__((ext_vector_type(4)));
+extern "C" __device__ Coef4x a2d_coef4_load(CoefRsrc rsrc, int vindex, int voffset, int soffset, int aux)
+		__asm("llvm.amdgcn.struct.buffer.load.v4i32");
+
+DEV CoefRsrc coef4_rsrc(const int *wavecoef4)
+{
+	const uint64_t b = (uint64_t)wavecoef4;
+	CoefRsrc r;
+	r.x = rfl((int)(unsigned)b);
+	r.y = rfl((int)(((unsigned)(b >> 32) & 0xffffu) | (16u << 16)));
+	r.z = -1;
+	r.w = 0x00020000;
+	return r;
+}
+
+DEV int coef4_base(unsigned doff) { return (int)(doff * 16u); }
+
+DEV Coef4x coef4_at(const CoefRsrc rs, int cb, unsigned ph)
+{
+	return a2d_coef4_load(rs, (int)(ph >> 8), 0, cb, 0);
+}
+
+// a2_Hermite from such an entry at the 24:8 phase ph, its d[i] term included, on a level where no product wraps: per
+// step one 24 bit multiply-add - the addend is the next coefficient, 8 bits up - and one arithmetic shift.  Exact there:
+// the addend is a multiple of 256 and >> is a floor, so (v * f + (k << 8)) >> 8 = floor(v * f / 256) + k, and
+// floor(v * f / 256) is the reference's (v * x) >> 15 while v * f stays inside [-2^24, 2^24).  Operands: |a| < 2^17,
+// the steps' sums below 2^19 (hermite_step), f <= 255: inside the multiplier's 24 bits; |v * f + (k << 8)| < 2^27.
+// (The 24 bit multiply is asked for by name and the compiler folds the add into it - v_mad_i32_i24; spelled as an
+// instruction string it costs a wait state behind every one that feeds the shift.)
+DEV int mad24(int v, int f, int k)
+{
+	return wadd(__mul24(v, f), k);
+}
+
+DEV int hermite_fused(const Coef4x k, unsigned ph)
+{
+	const int f = (int)(ph & 0xffu);
+	int t = mad24(k.x, f, k.y) >> 8;
+	t = mad24(t, f, k.z) >> 8;
+	return mad24(t, f, k.w) >> 8;
+}
+
+// ... from a wavefront's copy of a whole level in LDS, in this table's layout (stage_level4): 1 << lg entries at a
+// 16 byte stride, so the entry's byte offset is a shift and a mask of the phase - (ph >> 4) & ((size - 1) << 4) - and the
+// entry one aligned 16 byte read.  mask16 = (size - 1) << 4, wave-uniform.
+typedef __attribute__((address_space(3))) Coef4x LdsCoef4x;
+DEV Coef4x coef4_lds(const LdsInt *level, unsigned ph, unsigned mask16)
+{
+	typedef __attribute__((address_space(3))) char LdsChar;
+	return *(const LdsCoef4x *)((const LdsChar *)level + ((ph >> 4) & mask16));
+}
+
+// The copy: entries [0, size) of the level whose first payload entry stands at byte cb of the 16 byte table, size <=
+// A2D_OSC2_LDS_ENT: an entry a lane, at most two rounds.  The caller fences on both sides, as for stage_level().
+DEV void stage_level4(LdsInt *level, const int *wavecoef4, int cb, unsigned size, int lane)
+{
+	const Coef4x *src = (const Coef4x *)(wavecoef4 + ((unsigned)cb >> 2));
+	LdsCoef4x *dst = (LdsCoef4x *)level;
+#pragma unroll
+	for(int r = 0; r < A2D_OSC2_LDS_ENT / 64; ++r) {
+		const unsigned i = (unsigned)(r * 64 + lane);
+		if(i < size)
+			dst[i] = src[i];
+	}
+}
+
 // what orders a wavefront's LDS stores against its other lanes' reads (LDS operations of one wavefront execute in
 // order: nothing to wait for, the compiler must only keep them where they are)
 DEV void lds_wave_fence()

@@ -250,6 +250,12 @@ class Backend:
         if hasattr(lib, prefix + "osc2_stage_rule"):
             self._osc2_stage_rule = fn("osc2_stage_rule", u32, u32, i32, u32, i32)
             self._wave_level_periodic = fn("wave_level_periodic", i32, C.POINTER(C.c_int16), u32)
+        # include/a2amd_osc2tame.h: likewise
+        self._osc2_tame_rule = self._wave_level_tame = None
+        if hasattr(lib, prefix + "osc2_tame_rule"):
+            self._osc2_tame_rule = fn("osc2_tame_rule", u32, i32, i32)
+            self._wave_level_tame = fn("wave_level_tame", i32, C.POINTER(C.c_int16), u32)
+            self._osc2_tame_voices = fn("osc2_tame_voices", i32, vp, C.POINTER(C.c_uint64))
         self._last_batch_fbdpan = None
         if hasattr(lib, prefix + "last_batch_fbdpan"):
             self._last_batch_fbdpan = fn("last_batch_fbdpan", i32, vp, C.POINTER(a2amd_fbdpan_batch_info))
@@ -442,6 +448,30 @@ class Backend:
         if self._osc2_stage_rule is None:
             raise RuntimeError(f"this library has no {self.prefix}osc2_stage_rule")
         return int(self._osc2_stage_rule(size0, int(bool(periodic0)), size1, int(bool(periodic1))))
+
+    def osc2_tame_rule(self, tame0, tame1):
+        """a2amd_osc2_tame_rule: does a settled `wtosc; wtosc; panmix` voice whose oscillators play levels that are
+        tame or not take the fused multiply-add steps on the voice-major walk"""
+        if self._osc2_tame_rule is None:
+            raise RuntimeError(f"this library has no {self.prefix}osc2_tame_rule")
+        return int(self._osc2_tame_rule(int(bool(tame0)), int(bool(tame1))))
+
+    def osc2_tame_voices(self):
+        """a2amd_osc2_tame_voices: the voices k_leaf_osc2pan gave the tame bit, summed over its launches so far"""
+        if self._osc2_tame_rule is None:
+            raise RuntimeError(f"this library has no {self.prefix}osc2_tame_voices")
+        n = C.c_uint64(0)
+        self._chk(self._osc2_tame_voices(self.ctx, C.byref(n)), "osc2_tame_voices")
+        return int(n.value)
+
+    def wave_level_tame(self, level, size=None):
+        """a2amd_wave_level_tame: does no product of the Hermite interpolation wrap anywhere in this level - int16,
+        WAVEPRE + size + WAVEPOST samples, as wave_upload() takes it"""
+        if self._wave_level_tame is None:
+            raise RuntimeError(f"this library has no {self.prefix}wave_level_tame")
+        arr = np.ascontiguousarray(level, dtype=np.int16)
+        n = len(arr) - WAVEPRE - WAVEPOST if size is None else size
+        return bool(self._wave_level_tame(arr.ctypes.data_as(C.POINTER(C.c_int16)), n))
 
     def wave_level_periodic(self, level):
         """a2amd_wave_level_periodic: are the pads of this level - int16, WAVEPRE + size + WAVEPOST samples, as

@@ -465,6 +465,8 @@ int  a2amd_last_batch(const a2amd_ctx *ctx, a2amd_batch_info *bi);
 #include "a2amd_osc2.h"
 /* ... and which of their oscillators read their taps from a copy of the mip level in LDS: a2amd_osc2_stage_rule(). */
 #include "a2amd_osc2lds.h"
+/* ... and which of them take the interpolation's fused multiply-add steps: a2amd_wave_level_tame(), a2amd_osc2_tame_rule(). */
+#include "a2amd_osc2tame.h"
 /* The quiet kernel of three-oscillator subtractive leads: a2amd_last_batch_osc3filt(). */
 #include "a2amd_osc3filt.h"
 

@@ -2,7 +2,9 @@
 // are made of, on gfx950: 1, 4 and 8 wave64 per SIMD (profiles/r02_valu_rates.txt was made with
 // 4 and 8 only), a long unrolled chain of independent copies of one instruction, cycles from
 // s_memtime.  The SDWA forms of the wavetable taps (a2amd_taps.h) stand beside what they replace:
-// mul24_sdwa_b0 / lshl_sdwa_b0 / add_sdwa_w1, and the dependent pairs mul24sdwa+bfe against mul_lo+ashr.
+// mul24_sdwa_b0 / lshl_sdwa_b0 / add_sdwa_w1, and the dependent pairs mul24sdwa+bfe against mul_lo+ashr; the
+// fused step of tame levels, mad24+ashr, dependent and independent ("i"), beside mul24sdwa+bfe likewise
+// (profiles/osc2_tame.md).
 //   hipcc --offload-arch=gfx950 -O3 -o valu_rates valu_rates.hip && ./valu_rates
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -73,6 +75,12 @@ KERNEL(k_add_sdwa_w1, , OP8("v_add_u32_sdwa %0, %1, %0 dst_sel:DWORD dst_unused:
 KERNEL(k_lshl_sdwa, , OP8("v_lshlrev_b32_sdwa %0, %1, %0 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_0"))
 KERNEL(k_mix_mul24_sdwa_bfe, , OP8("v_mul_i32_i24_sdwa %0, %0, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_0\n v_bfe_i32 %0, %0, 8, 17"))
 KERNEL(k_mix_mul_lo_ashr, , OP8("v_mul_lo_u32 %0, %0, %1\n v_ashrrev_i32 %0, 15, %0"))
+// the fused step of tame levels (a2amd_taps.h: hermite_fused) beside the step it replaces (mul24sdwa+bfe above):
+// dependent - the shift takes the multiply-add's result, eight chains side by side - and independent - it takes
+// the other operand, so no instruction waits for the one before it
+KERNEL(k_mix_mad24_ashr, , OP8("v_mad_i32_i24 %0, %0, %1, %2\n v_ashrrev_i32 %0, 8, %0"))
+KERNEL(k_mix_mad24_ashr_ind, , OP8("v_mad_i32_i24 %0, %1, %2, %1\n v_ashrrev_i32 %0, 8, %1"))
+KERNEL(k_mix_mul24_sdwa_bfe_ind, , OP8("v_mul_i32_i24_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:BYTE_0\n v_bfe_i32 %0, %1, 8, 17"))
 // mixes: 1 add + 1 mul24 ; 2 add + 1 mul24 ; add + bfe ; add + mad_i64
 KERNEL(k_mix_add_mul, , OP8("v_add_u32 %0, %0, %1\n v_mul_i32_i24 %0, %0, %2"))
 KERNEL(k_mix_2add_mul, , OP8("v_add_u32 %0, %0, %1\n v_add_u32 %0, %0, %2\n v_mul_i32_i24 %0, %0, %2"))
@@ -136,6 +144,8 @@ int main()
 		run("mul24sdwa+bfe(2)", k_mix_mul24_sdwa_bfe, w); run("mul_lo+ashr(2)", k_mix_mul_lo_ashr, w);
 		run("add+mul24(2)", k_mix_add_mul, w); run("2add+mul24(3)", k_mix_2add_mul, w); run("add+bfe(2)", k_mix_add_bfe, w);
 		run("mul24+bfe(2)", k_mix_mul_bfe, w);
+		run("mad24+ashr(2)", k_mix_mad24_ashr, w); run("mad24+ashr(2)i", k_mix_mad24_ashr_ind, w);
+		run("mul24sdwa+bfe(2)i", k_mix_mul24_sdwa_bfe_ind, w);
 		printf("\n");
 	}
 	return 0;
