@@ -7,8 +7,10 @@
 // lane = frame and no loop over the draws.  Only the filter is a recurrence in time, and it runs as in k_leaf_oscfiltpan
 // (a2amd_fast.hip, "wtosc -> filter12 (1 ch) -> panmix 1->2"): lane = voice on ONE wavefront, filt_row (a2amd_filt.h).
 //
-// A workgroup owns up to 64 voices for the WHOLE batch and walks its fragments in order - the held sample, the generator
-// word and the filter's d1 / d2 travel from fragment to fragment, so the batch is not cut into time slices.  Per
+// The workgroup - its constants, the split of its voices over the workers, the facts every wavefront derives alike, the
+// bus sums and the bus-run walk - is a2amd_quiet.h's, shared with k_leaf_osc3filtpan.  It owns up to 64 voices for the
+// WHOLE batch and walks its fragments in order - the held sample, the generator word and the filter's d1 / d2 travel from
+// fragment to fragment, so the batch is not cut into time slices.  Per
 // fragment three stages meet over a ring of three [voices][64 + 1] LDS tiles, a barrier per step:
 //   A(f)      workers, lane = frame: per voice the window's draws from its column of the seed table -> a2nm_out at the
 //             oscillator's amplitude -> the row, already shifted (x5 = out >> 5, filter12.c:105); phase, held sample and
@@ -34,44 +36,27 @@
 #include "a2amd_device.h"
 #include "a2amd_noisevoice.h"
 #include "a2amd_filt.h"
+#include "a2amd_quiet.h"
 
-#define NFP_MAXV  64	// voices per workgroup: the lanes of the filter wavefront
-#define NFP_PITCH 65	// (+1: row and column accesses both bank-conflict free)
-// Wavefronts per workgroup: 8 = the filter wavefront, six workers, one idle.
-// The step: a pipeline step is as long as the filter wavefront's chain of dependent instructions - 64 frames x 12 (pure
-// low pass) to 15 instructions, 770 - 960 issues one behind the other, about 4 600 cycles (a2amd_fast.hip) - whatever the
-// number of busy lanes.  A + C cost a worker about 50 vector instructions per voice and fragment (A: five lane reads, the
-// map's multiply-add, the value, the draw count, ds_bpermute, three selects, the amplitude, the tile store, ~35; C: the
-// tile load, two 64-bit products, two adds, ~15), 200 cycles of its SIMD.  64 voices over six workers are 11 each, two
-// workers per SIMD: 22 x 200 = 4 400 cycles - below the filter's chain; with three workers (4 wavefronts) a SIMD would
-// carry 21 - 22 voices alone, the same, but nothing would overlap the workers' own LDS and lane-read latencies.  Where a
-// wavefront runs is the hardware's choice; wavefronts w and w + 4 of a workgroup were observed to share a SIMD
-// (a2amd_fast.hip), so wavefront 4 takes no voices and leaves the filter's SIMD to the filter.
-// LDS: three tiles of 64 x 65 words are 49 920 bytes, the bus sums 1 536 more - three workgroups fit the 160 KB of a CU, which is what the launcher
-// relies on once there are more than 256 workgroups; 16 wavefronts per workgroup would not buy more (one filter wavefront
-// per 64 voices either way) and would leave a CU two workgroups at most.
-#define NFP_WAVES 8
-#define NFP_WORKERS 6
-
-__global__ __launch_bounds__(64 * NFP_WAVES)
+__global__ __launch_bounds__(64 * QUIET_WAVES)
 void k_leaf_noisefiltpan(const A2DParams *__restrict__ pp, const int *__restrict__ list, int nlist, int vpg,
 		const A2DVoice *__restrict__ voices, const A2DRun *__restrict__ runs, int *ustate,
 		const uint32_t *__restrict__ nseed, const int32_t *__restrict__ nslot, int nnoise, int nfrags,
 		int *__restrict__ busmem)
 {
-	extern __shared__ __attribute__((aligned(16))) int nf_tiles[];	// 3 x [vpg][NFP_PITCH]
+	extern __shared__ __attribute__((aligned(16))) int nf_tiles[];	// 3 x [vpg][QUIET_PITCH]
 	const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
 	const int lane = threadIdx.x & 63;
 	const int first = (int)blockIdx.x * vpg;
 	const int nv = min(vpg, nlist - first);
 	if(nv <= 0)
 		return;		// (the whole workgroup: the grid has none such)
-	const int tsize = vpg * NFP_PITCH;
+	const int tsize = vpg * QUIET_PITCH;
 
 	// lane v: voice v of this workgroup, in every wavefront
 	int u0 = 0, u1 = 0, u2 = 0, my_off = -1, my_nch = 2;
 	NoiseV nz = { 0, 0, 0, 0, 0, 0, 0 };
-	int v0_l = 0, v1_l = 0, v0r_l = 0, v1r_l = 0;
+	PanRest pg = { 0, 0, 0, 0 };
 	int qt_l = 0, ff_l = 0, lp_l = 0, bp_l = 0, hp_l = 0, d1_l = 0, d2_l = 0;
 	bool ok = false;
 	if(lane < nv) {
@@ -99,26 +84,15 @@ void k_leaf_noisefiltpan(const A2DParams *__restrict__ pp, const int *__restrict
 				lp_l = w1[FW_LP]; bp_l = w1[FW_BP]; hp_l = w1[FW_HP];
 				d1_l = w1[FW_D1A];
 				d2_l = w1[FW_D2A];
-				// panmix_process12's two gains as k_leaf_noisepan derives them.  Whether they are clamped is decided in front of
-				// a2_PrepareRamper (panmix.c:120-124): the first window still sees the value a finished ramp stopped at, the
-				// others the target
-				const int vol = w2[PW_VOL + 1], pan = w2[PW_PAN + 1];
-				const bool cr = a2s_pan_over(pan), c0 = cr || a2s_pan_over(w2[PW_PAN]);
-				a2s_pan_gains(vol, pan, c0, &v0_l, &v1_l);
-				a2s_pan_gains(vol, pan, cr, &v0r_l, &v1r_l);
+				panrest_load(pg, w2);
 			}
 		}
 	}
-	const unsigned long long todo = __ballot(ok);
-	if(!todo)
+	const QuietWg wg = quiet_wg(ok, bp_l, hp_l, my_off, my_nch);
+	if(!wg.todo)
 		return;		// (the whole workgroup)
-	// The row format of the batch (filt_step): pure low pass filters in the whole workgroup leave l in the rows and the pan
-	// stage applies lp - 12 dependent instructions per frame instead of 15.
-	const bool lpraw = __all(!ok || (bp_l == 0 && hp_l == 0));
-	// the workgroup's share of its bus, fragment by fragment, where it has one bus (stage D)
-	__shared__ int nf_acc[3][2][A2D_FRAG];
-	const int wg_off = rdl(my_off, (int)__builtin_ctzll(todo));
-	const bool wgbus = __all(!ok || (my_off == wg_off && my_nch == 2));
+	const bool lpraw = wg.lpraw, wgbus = wg.wgbus;
+	__shared__ QuietBus nf_acc;
 	const int nsteps = nfrags + 3;
 
 	if(wv == 0) {
@@ -129,7 +103,7 @@ void k_leaf_noisefiltpan(const A2DParams *__restrict__ pp, const int *__restrict
 			if(f >= 0 && f < nfrags) {
 				const int n = min((int)pp->fragframes[f], A2D_FRAG);
 				if(n > 0 && ok) {
-					int *row = nf_tiles + (f % 3) * tsize + lane * NFP_PITCH;
+					int *row = nf_tiles + (f % 3) * tsize + lane * QUIET_PITCH;
 					int qv = qt_l;
 					if(lpraw)
 						filt_row<true, true>(row, n, ff_l, lp_l, bp_l, hp_l, d1_l, d2_l, qv, 0);
@@ -149,42 +123,17 @@ void k_leaf_noisefiltpan(const A2DParams *__restrict__ pp, const int *__restrict
 		return;
 	}
 
-	// ================= workers: lane = frame, voices [vb, ve) of the workgroup =================
-	const int widx = wv < 4 ? wv - 1 : wv - 2;	// (wavefront 4 shares the filter's SIMD: no voices)
-	int vb = 0, ve = 0;
-	if(wv != 4) {
-		const int per = nv / NFP_WORKERS, extra = nv % NFP_WORKERS;
-		vb = widx * per + min(widx, extra);
-		ve = vb + per + (widx < extra ? 1 : 0);
-	}
-	// my voices among the ones to render
-	unsigned long long mine = 0;
-	if(ve > vb)
-		mine = todo & ((ve >= 64 ? ~0ull : ((1ull << ve) - 1ull)) & ~((1ull << vb) - 1ull));
-	// (wave-uniform, and known to the compiler as such)
-	mine = (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)mine) |
-			((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(mine >> 32)) << 32);
+	// ================= workers: lane = frame, a range of the workgroup's voices each =================
+	const unsigned long long mine = quiet_worker_voices(wv, nv, wg.todo);	// (wavefront 4: none)
 	const bool mylane = (mine >> lane) & 1ull;
 
 	// lane j: the map of j + 1 draws
 	uint32_t mapA, mapC;
 	a2nm_map((unsigned)lane + 1u, &mapA, &mapC);
 
-	if(wv == 4 && wgbus) {	// (first used in step 2: two barriers away)
-		for(int k = lane; k < 3 * 2 * A2D_FRAG; k += 64)
-			(&nf_acc[0][0][0])[k] = 0;
-	}
-	// one fragment's sums of this wavefront's bus run
-	auto bus_add = [&](int off, int nch, int f, int acc0, int acc1) __attribute__((always_inline)) {
-		if(wgbus) {
-			if(acc0) atomicAdd(&nf_acc[f % 3][0][lane], acc0);
-			if(acc1) atomicAdd(&nf_acc[f % 3][1][lane], acc1);
-		} else {
-			int *dst = busmem + off + (size_t)f * nch * A2D_FRAG;
-			if(acc0) atomicAdd(&dst[lane], acc0);
-			if(acc1) atomicAdd(&dst[A2D_FRAG + lane], acc1);
-		}
-	};
+	if(wv == 4 && wgbus)	// (first used in step 2: two barriers away)
+		quiet_bus_clear(nf_acc, lane, 64);
+	const QuietOut out = { busmem, &nf_acc, wgbus, lane };
 
 	unsigned total_frames = 0;
 	bool cfirst = true;	// stage C has not met a window yet: the first one's gains
@@ -192,14 +141,8 @@ void k_leaf_noisefiltpan(const A2DParams *__restrict__ pp, const int *__restrict
 		// ---- D(st - 3): the workgroup's sum of a fragment, complete since the last barrier ----
 		if(wv == 4 && wgbus && st >= 3) {
 			const int f = st - 3;
-			if((int)pp->fragframes[f] > 0) {
-				const int a0 = nf_acc[f % 3][0][lane], a1 = nf_acc[f % 3][1][lane];
-				nf_acc[f % 3][0][lane] = 0;
-				nf_acc[f % 3][1][lane] = 0;
-				int *dst = busmem + wg_off + (size_t)f * 2 * A2D_FRAG;
-				if(a0) atomicAdd(&dst[lane], a0);
-				if(a1) atomicAdd(&dst[A2D_FRAG + lane], a1);
-			}
+			if((int)pp->fragframes[f] > 0)
+				quiet_bus_flush(nf_acc, busmem, wg.wg_off, f, lane);
 		}
 		// ---- A(st) ----
 		if(st < nfrags && mine) {
@@ -217,7 +160,7 @@ void k_leaf_noisefiltpan(const A2DParams *__restrict__ pp, const int *__restrict
 					const int x = noisev_window(nz, v, lane, fl, n, mapA, mapC);
 					// wtosc.c:148 at the amplitude, filter12.c:105's shift
 					const int y = a2nm_out(x, rdl(nz.g, v));
-					tile[v * NFP_PITCH + lane] = lane < n ? y >> 5 : 0;
+					tile[v * QUIET_PITCH + lane] = lane < n ? y >> 5 : 0;
 				}
 				// every voice moves on by n frames (all lanes at once)
 				nz.phlo += (unsigned)n * nz.d;
@@ -230,28 +173,19 @@ void k_leaf_noisefiltpan(const A2DParams *__restrict__ pp, const int *__restrict
 			const int n = min((int)pp->fragframes[f], A2D_FRAG);
 			if(n > 0) {
 				const int *tile = nf_tiles + (f % 3) * tsize;
-				int acc0 = 0, acc1 = 0;
-				int cur_off = -1, cur_nch = 2;
+				BusRun run = busrun_begin();
 				for(unsigned long long m = mine; m; m &= m - 1) {
 					const int v = (int)__builtin_ctzll(m);
-					const int voff = rdl(my_off, v);
-					if(voff != cur_off) {
-						if(cur_off >= 0)
-							bus_add(cur_off, cur_nch, f, acc0, acc1);
-						acc0 = acc1 = 0;
-						cur_off = voff;
-						cur_nch = rdl(my_nch, v);
-					}
-					int y = tile[v * NFP_PITCH + lane];
+					busrun_voice(run, out, f, my_off, my_nch, v);
+					int y = tile[v * QUIET_PITCH + lane];
 					if(lpraw)
 						y = wmul(y, rdl(lp_l, v)) >> 3;	// (filt_step: the row holds l)
 					if(lane < n) {
-						acc0 = wadd(acc0, mul64s(y, rdl(cfirst ? v0_l : v0r_l, v), 24));
-						acc1 = wadd(acc1, mul64s(y, rdl(cfirst ? v1_l : v1r_l, v), 24));
+						run.acc0 = wadd(run.acc0, mul64s(y, rdl(cfirst ? pg.v0 : pg.v0r, v), 24));
+						run.acc1 = wadd(run.acc1, mul64s(y, rdl(cfirst ? pg.v1 : pg.v1r, v), 24));
 					}
 				}
-				if(cur_off >= 0)
-					bus_add(cur_off, cur_nch, f, acc0, acc1);
+				busrun_end(run, out, f);
 				cfirst = false;
 			}
 		}
@@ -263,14 +197,14 @@ void k_leaf_noisefiltpan(const A2DParams *__restrict__ pp, const int *__restrict
 		noisev_store(nz, total_frames, ustate + (size_t)u0 * A2D_USTATE, ustate + (size_t)u2 * A2D_USTATE);
 }
 
-// voices per workgroup: at most NFP_MAXV (one per lane of the filter wavefront)
+// voices per workgroup: at most QUIET_MAXV (one per lane of the filter wavefront)
 int a2d_launch_leaf_noisefiltpan(const A2DParams *dparams, const A2DParams &hp, const int *dlist, int nlist, int vpg, void *stream)
 {
 	if(nlist <= 0)
 		return 0;
-	vpg = vpg < 1 ? 1 : vpg > NFP_MAXV ? NFP_MAXV : vpg;
-	const dim3 grid((nlist + vpg - 1) / vpg), block(64 * NFP_WAVES);
-	const size_t dyn = (size_t)3 * vpg * NFP_PITCH * sizeof(int);
+	vpg = vpg < 1 ? 1 : vpg > QUIET_MAXV ? QUIET_MAXV : vpg;
+	const dim3 grid((nlist + vpg - 1) / vpg), block(64 * QUIET_WAVES);
+	const size_t dyn = (size_t)3 * vpg * QUIET_PITCH * sizeof(int);
 	hipLaunchKernelGGL(k_leaf_noisefiltpan, grid, block, dyn, (hipStream_t)stream, dparams, dlist, nlist, vpg, hp.voices, hp.runs,
 			hp.ustate, hp.nseed, hp.nslot, hp.nnoise, hp.nfrags, hp.busmem);
 	return hipGetLastError() != hipSuccess;

@@ -10,7 +10,8 @@
 // A wavefront owns up to 64 voices (one per lane: state words, gains, output bus) for the WHOLE batch and walks its
 // fragments in order - the sample a sparse oscillator holds may come from many fragments back, so the batch is not
 // cut into time slices.  The bus sums of a fragment stay in registers: one atomic add per (fragment, channel, frame)
-// and wavefront, flushed where the output bus changes (the list is sorted by bus).  At the end the wavefront stores
+// and wavefront, flushed where the output bus changes (the list is sorted by bus: a2amd_quiet.h's bus-run walk, which
+// the two quiet filter kernels' workers share).  At the end the wavefront stores
 // what k_win_ctl's ctl_store would have left for the same windows - phase, held sample, generator word, the rampers
 // at their targets - with plain vector stores: nobody else touches the voice during the launch.
 //
@@ -21,6 +22,7 @@
 #include <hip/hip_runtime.h>
 #include "a2amd_device.h"
 #include "a2amd_noisevoice.h"
+#include "a2amd_quiet.h"
 
 #define NP_WPB 4	// wavefronts per workgroup
 
@@ -44,7 +46,7 @@ void k_leaf_noisepan(const A2DParams *__restrict__ pp, const int *__restrict__ l
 	// lane v: voice v of this wavefront's run
 	int u0 = 0, u1 = 0, my_off = -1, my_nch = 2;
 	NoiseV nz = { 0, 0, 0, 0, 0, 0, 0 };
-	int v0_l = 0, v1_l = 0, v0r_l = 0, v1r_l = 0;
+	PanRest pg = { 0, 0, 0, 0 };
 	bool ok = false;
 	if(lane < nv) {
 		const int slot = list[first + lane];
@@ -62,18 +64,14 @@ void k_leaf_noisepan(const A2DParams *__restrict__ pp, const int *__restrict__ l
 					a2s_at_rest(w0 + OW_P) && a2s_at_rest(w0 + OW_A) && a2s_at_rest(w1 + PW_VOL) && a2s_at_rest(w1 + PW_PAN);
 			if(ok) {
 				noisev_load(nz, w0, u0, nseed, nslot, nnoise);
-				// panmix_process12's two gains.  Whether they are clamped is decided in front of a2_PrepareRamper
-				// (panmix.c:120-124): the first window still sees the value a finished ramp stopped at, the others the target
-				const int vol = w1[PW_VOL + 1], pan = w1[PW_PAN + 1];
-				const bool cr = a2s_pan_over(pan), c0 = cr || a2s_pan_over(w1[PW_PAN]);
-				a2s_pan_gains(vol, pan, c0, &v0_l, &v1_l);
-				a2s_pan_gains(vol, pan, cr, &v0r_l, &v1r_l);
+				panrest_load(pg, w1);
 			}
 		}
 	}
 	const unsigned long long todo = __ballot(ok);
 	if(!todo)
 		return;
+	const QuietOut out = { busmem, nullptr, false, lane };	// (a wavefront of its own: straight to the buses)
 
 	unsigned total_frames = 0;
 	for(int f = 0; f < nfrags; ++f) {
@@ -84,43 +82,24 @@ void k_leaf_noisepan(const A2DParams *__restrict__ pp, const int *__restrict__ l
 		// its last window left
 		if(nz.col)
 			nz.seed = noisev_seed(nz, nseed, f, nnoise);
-		int acc0 = 0, acc1 = 0;
-		int cur_off = -1, cur_nch = 2;
+		BusRun run = busrun_begin();
 		const unsigned fl = (unsigned)min(lane, n - 1);	// (lanes beyond the fragment's frames: the last frame's, dropped below)
 		for(unsigned long long m = todo; m; m &= m - 1) {
 			const int v = (int)__builtin_ctzll(m);
-			const int voff = rdl(my_off, v);
-			if(voff != cur_off) {
-				if(cur_off >= 0) {
-					int *dst = busmem + cur_off + (size_t)f * cur_nch * A2D_FRAG;
-					if(acc0)
-						atomicAdd(&dst[lane], acc0);
-					if(acc1)
-						atomicAdd(&dst[A2D_FRAG + lane], acc1);
-				}
-				acc0 = acc1 = 0;
-				cur_off = voff;
-				cur_nch = rdl(my_nch, v);
-			}
+			busrun_voice(run, out, f, my_off, my_nch, v);
 			const int x = noisev_window(nz, v, lane, fl, n, mapA, mapC);
 			if(lane < n) {
 				const int y = a2nm_out(x, rdl(nz.g, v));
-				acc0 = wadd(acc0, mul64s(y, rdl(v0_l, v), 24));
-				acc1 = wadd(acc1, mul64s(y, rdl(v1_l, v), 24));
+				run.acc0 = wadd(run.acc0, mul64s(y, rdl(pg.v0, v), 24));
+				run.acc1 = wadd(run.acc1, mul64s(y, rdl(pg.v1, v), 24));
 			}
 		}
-		if(cur_off >= 0) {
-			int *dst = busmem + cur_off + (size_t)f * cur_nch * A2D_FRAG;
-			if(acc0)
-				atomicAdd(&dst[lane], acc0);
-			if(acc1)
-				atomicAdd(&dst[A2D_FRAG + lane], acc1);
-		}
+		busrun_end(run, out, f);
 		// every voice moves on by n frames (all lanes at once)
 		nz.phlo += (unsigned)n * nz.d;
 		total_frames += (unsigned)n;
-		v0_l = v0r_l;
-		v1_l = v1r_l;
+		pg.v0 = pg.v0r;
+		pg.v1 = pg.v1r;
 	}
 
 	// state out: ctl_store's words for the same windows

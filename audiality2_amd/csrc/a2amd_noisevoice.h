@@ -1,6 +1,7 @@
 // a2amd_noisevoice.h - the quiet noise voice k_leaf_noisepan (a2amd_noisepan.hip) and k_leaf_noisefiltpan
 // (a2amd_noisefiltpan.hip) share, device only: a settled noise oscillator's words carried lane = voice for the whole
-// launch, one window of it lane = frame (a2amd_noisemap.h's closed form), and the state both kernels leave behind.
+// launch, one window of it lane = frame (a2amd_noisemap.h's closed form), the gains of a panmix at rest, and the state
+// both kernels leave behind.
 #pragma once
 #include "a2amd_device.h"
 #include "a2amd_dsp.h"
@@ -52,6 +53,19 @@ DEV int noisev_window(NoiseV &o, int v, int lane, unsigned fl, int n, uint32_t m
 	o.h = me ? hn : o.h;
 	o.seed = me ? sn : o.seed;
 	return x;
+}
+
+// panmix_process12's two gains of a panmix (wp) whose volume and pan are at rest: v0, v1 for the first window the voice
+// meets, v0r, v1r for the later ones.  Whether they are clamped is decided in front of a2_PrepareRamper
+// (panmix.c:120-124): the first window still sees the value a finished ramp stopped at, the others the target.
+struct PanRest { int v0, v1, v0r, v1r; };
+
+DEV void panrest_load(PanRest &g, const int *wp)
+{
+	const int vol = wp[PW_VOL + 1], pan = wp[PW_PAN + 1];
+	const bool cr = a2s_pan_over(pan), c0 = cr || a2s_pan_over(wp[PW_PAN]);
+	a2s_pan_gains(vol, pan, c0, &g.v0, &g.v1);
+	a2s_pan_gains(vol, pan, cr, &g.v0r, &g.v1r);
 }
 
 // state out after 'frames' frames: the oscillator's (w0) and the panmix's (wp) words as ctl_store leaves them for the

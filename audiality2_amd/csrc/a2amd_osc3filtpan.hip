@@ -2,9 +2,11 @@
 // filter12 (1 ch) -> panmix 1->2, wired, adding" leaf voices - the three-oscillator subtractive lead,
 // `struct { wtosc; wtosc o2; wtosc o3; filter12; panmix }` - in the batches in which they carry no record.
 //
-// Ownership and pipeline are k_leaf_noisefiltpan's (a2amd_noisefiltpan.hip): a workgroup of 8 wavefronts owns up to 64
-// voices of its run of the bus-sorted list for the WHOLE batch and walks its fragments in order - no time slices, no
-// staged commit.  Per fragment three stages meet over a ring of three [voices][64 + 1] LDS tiles, a barrier per step:
+// Ownership and pipeline are k_leaf_noisefiltpan's (a2amd_noisefiltpan.hip), and what the two share word for word - the
+// workgroup's constants, the split of its voices over the workers, the facts every wavefront derives alike, the bus sums,
+// the bus-run walk, and the tap pair k_leaf_oscbare uses too - stands in a2amd_quiet.h.  A workgroup of 8 wavefronts owns
+// up to 64 voices of its run of the bus-sorted list for the WHOLE batch and walks its fragments in order - no time slices,
+// no staged commit.  Per fragment three stages meet over a ring of three [voices][64 + 1] LDS tiles, a barrier per step:
 //   K/A(f)    workers.  Lane = voice, once per fragment: osc_window_v() (a2amd_winctl.h) steps each of the voice's three
 //             oscillators over the window - pitch and amplitude rampers, mip level, the wrap of a looped wave, a one-shot
 //             wave's end, a pitch out of range, an unloaded wave - and leaves the closed-form words of the window, as in
@@ -35,60 +37,22 @@
 #include "a2amd_taps.h"
 #include "a2amd_winctl.h"
 #include "a2amd_filt.h"
+#include "a2amd_quiet.h"
 
-#define O3F_MAXV  64	// voices per workgroup: the lanes of the filter wavefront
-#define O3F_PITCH 65	// (+1: row and column accesses both bank-conflict free)
-// Wavefronts per workgroup, as k_leaf_noisefiltpan: the filter wavefront, six workers, and wavefront 4 - which was
-// observed to share the filter's SIMD - with no voices: it adds the workgroup's sums to the bus.
-#define O3F_WAVES 8
-#define O3F_WORKERS 6
-
-// one oscillator's two taps of a frame, issued (k_leaf_oscbare's BareTaps); all zero for an oscillator that is silent
-// in the window: it then comes out as 0
-struct O3Taps { Coef4 k1, k2; unsigned t1, t2; int ak, da; };
-
-DEV void o3_clear(O3Taps &T)
-{
-	T.k1 = T.k2 = Coef4{ 0, 0, 0 };
-	T.t1 = T.t2 = 0;
-	T.ak = T.da = 0;
-}
-
-// voice v's window words out of the lanes; where this lane's frame fl reads the wave; the loads
-DEV void o3_issue(const int (&w)[6], int v, const CoefRsrc rs, unsigned fl, O3Taps &T)
-{
-	const unsigned phlo = (unsigned)rdl(w[WO_B], v), phhi = (unsigned)rdl(w[WO_C], v), dph = (unsigned)rdl(w[WO_DPH], v);
-	const int cb = coef_base((unsigned)rdl(w[WO_A], v));
-	T.ak = rdl(w[WO_AK], v);
-	T.da = rdl(w[WO_DA], v);
-	T.t1 = tap_phase((uint64_t)phlo | ((uint64_t)phhi << 32), fl * dph);
-	T.t2 = T.t1 + ((dph >> 16) >> 1);
-	T.k1 = coef_at(rs, cb, T.t1);
-	T.k2 = coef_at(rs, cb, T.t2);
-}
-
-// wtosc_do_fragment's sample of frame fl, wtosc.c:227-229 (the amplitude ramper run frame by frame)
-DEV int o3_finish(const O3Taps &T, unsigned fl)
-{
-	const int h = inter_coefs(T.k1, T.t1, T.k2, T.t2);
-	return mul64s(h, wadd(T.ak, wmul(T.da, (int)fl)), 17);
-}
-
-__global__ __launch_bounds__(64 * O3F_WAVES)
+__global__ __launch_bounds__(64 * QUIET_WAVES)
 void k_leaf_osc3filtpan(const A2DParams *__restrict__ pp, const int *__restrict__ list, int nlist, int vpg,
 		const A2DVoice *__restrict__ voices, const A2DRun *__restrict__ runs, int *ustate,
 		const A2DWave *__restrict__ waves, const uint32_t *__restrict__ ptab, const int *__restrict__ wavecoef,
 		int nfrags, int *__restrict__ busmem)
 {
-	extern __shared__ __attribute__((aligned(16))) int o3_tiles[];	// 3 x [vpg][O3F_PITCH]
+	extern __shared__ __attribute__((aligned(16))) int o3_tiles[];	// 3 x [vpg][QUIET_PITCH]
 	// the pitch table: read in every window of a gliding voice, from LDS (as k_win_ctl)
 	__shared__ PTab s_ptab;
 	// the workgroup's share of its bus, fragment by fragment, where it has one bus (stage D)
-	__shared__ int o3_acc[3][2][A2D_FRAG];
-	for(int k = (int)threadIdx.x; k < 128; k += 64 * O3F_WAVES)
+	__shared__ QuietBus o3_acc;
+	for(int k = (int)threadIdx.x; k < 128; k += 64 * QUIET_WAVES)
 		s_ptab[k] = ptab[k];
-	for(int k = (int)threadIdx.x; k < 3 * 2 * A2D_FRAG; k += 64 * O3F_WAVES)
-		(&o3_acc[0][0][0])[k] = 0;
+	quiet_bus_clear(o3_acc, (int)threadIdx.x, 64 * QUIET_WAVES);
 	__syncthreads();
 	const int wv = rfl((int)(threadIdx.x >> 6));
 	const int lane = threadIdx.x & 63;
@@ -96,7 +60,7 @@ void k_leaf_osc3filtpan(const A2DParams *__restrict__ pp, const int *__restrict_
 	const int nv = min(vpg, nlist - first);
 	if(nv <= 0)
 		return;		// (the whole workgroup: the grid has none such)
-	const int tsize = vpg * O3F_PITCH;
+	const int tsize = vpg * QUIET_PITCH;
 
 	// lane v: voice v of this workgroup, in every wavefront
 	int uo0 = 0, uo1 = 0, uo2 = 0, uf = 0, up = 0, my_off = -1, my_nch = 2;
@@ -120,14 +84,10 @@ void k_leaf_osc3filtpan(const A2DParams *__restrict__ pp, const int *__restrict_
 					(m2 == A2D_OSC_MIPWAVE || m2 == A2D_OSC_OFF);
 		}
 	}
-	const unsigned long long todo = __ballot(ok);
-	if(!todo)
+	const QuietWg wg = quiet_wg(ok, bp_l, hp_l, my_off, my_nch);
+	if(!wg.todo)
 		return;		// (the whole workgroup)
-	// The row format of the batch (filt_step): pure low pass filters in the whole workgroup leave l in the rows and the pan
-	// stage applies lp - 12 dependent instructions per frame instead of 15.
-	const bool lpraw = __all(!ok || (bp_l == 0 && hp_l == 0));
-	const int wg_off = rdl(my_off, (int)__builtin_ctzll(todo));
-	const bool wgbus = __all(!ok || (my_off == wg_off && my_nch == 2));
+	const bool lpraw = wg.lpraw, wgbus = wg.wgbus;
 	const int nsteps = nfrags + 3;
 
 	if(wv == 0) {
@@ -152,7 +112,7 @@ void k_leaf_osc3filtpan(const A2DParams *__restrict__ pp, const int *__restrict_
 						ramp_prepare_v(q, n);
 					const bool qrest = __all(!ok || q.delta == 0);
 					if(ok) {
-						int *row = o3_tiles + (f % 3) * tsize + lane * O3F_PITCH;
+						int *row = o3_tiles + (f % 3) * tsize + lane * QUIET_PITCH;
 						int qv = q.value;
 						if(qrest) {
 							if(lpraw)
@@ -181,20 +141,8 @@ void k_leaf_osc3filtpan(const A2DParams *__restrict__ pp, const int *__restrict_
 		return;
 	}
 
-	// ================= workers: voices [vb, ve) of the workgroup =================
-	const int widx = wv < 4 ? wv - 1 : wv - 2;	// (wavefront 4 shares the filter's SIMD: no voices)
-	int vb = 0, ve = 0;
-	if(wv != 4) {
-		const int per = nv / O3F_WORKERS, extra = nv % O3F_WORKERS;
-		vb = widx * per + min(widx, extra);
-		ve = vb + per + (widx < extra ? 1 : 0);
-	}
-	// my voices among the ones to render
-	unsigned long long mine = 0;
-	if(ve > vb)
-		mine = todo & ((ve >= 64 ? ~0ull : ((1ull << ve) - 1ull)) & ~((1ull << vb) - 1ull));
-	// (wave-uniform, and known to the compiler as such)
-	mine = (unsigned long long)(unsigned)rfl((int)(unsigned)mine) | ((unsigned long long)(unsigned)rfl((int)(unsigned)(mine >> 32)) << 32);
+	// ================= workers: a range of the workgroup's voices each =================
+	const unsigned long long mine = quiet_worker_voices(wv, nv, wg.todo);	// (wavefront 4: none)
 	const bool mylane = (mine >> lane) & 1ull;
 
 	// lane v, my voices only: the three oscillators as ctl_load loads them, the panmix's rampers
@@ -213,30 +161,14 @@ void k_leaf_osc3filtpan(const A2DParams *__restrict__ pp, const int *__restrict_
 	}
 	const CoefRsrc rs = coef_rsrc(wavecoef);
 
-	// one fragment's sums of this wavefront's bus run
-	auto bus_add = [&](int off, int nch, int f, int acc0, int acc1) __attribute__((always_inline)) {
-		if(wgbus) {
-			if(acc0) atomicAdd(&o3_acc[f % 3][0][lane], acc0);
-			if(acc1) atomicAdd(&o3_acc[f % 3][1][lane], acc1);
-		} else {
-			int *dst = busmem + off + (size_t)f * nch * A2D_FRAG;
-			if(acc0) atomicAdd(&dst[lane], acc0);
-			if(acc1) atomicAdd(&dst[A2D_FRAG + lane], acc1);
-		}
-	};
+	const QuietOut out = { busmem, &o3_acc, wgbus, lane };
 
 	for(int st = 0; st < nsteps; ++st) {
 		// ---- D(st - 3): the workgroup's sum of a fragment, complete since the last barrier ----
 		if(wv == 4 && wgbus && st >= 3) {
 			const int f = st - 3;
-			if((int)pp->fragframes[f] > 0) {
-				const int a0 = o3_acc[f % 3][0][lane], a1 = o3_acc[f % 3][1][lane];
-				o3_acc[f % 3][0][lane] = 0;
-				o3_acc[f % 3][1][lane] = 0;
-				int *dst = busmem + wg_off + (size_t)f * 2 * A2D_FRAG;
-				if(a0) atomicAdd(&dst[lane], a0);
-				if(a1) atomicAdd(&dst[A2D_FRAG + lane], a1);
-			}
+			if((int)pp->fragframes[f] > 0)
+				quiet_bus_flush(o3_acc, busmem, wg.wg_off, f, lane);
 		}
 		// ---- K/A(st) ----
 		if(st < nfrags && mine) {
@@ -256,24 +188,24 @@ void k_leaf_osc3filtpan(const A2DParams *__restrict__ pp, const int *__restrict_
 				int *tile = o3_tiles + (f % 3) * tsize;
 				const unsigned fl = (unsigned)min(lane, n - 1);
 				const bool in = lane < n;
-				auto issue = [&](int v, O3Taps &A, O3Taps &B, O3Taps &C) __attribute__((always_inline)) {
-					if((t0 >> v) & 1ull) o3_issue(w0, v, rs, fl, A); else o3_clear(A);
-					if((t1 >> v) & 1ull) o3_issue(w1, v, rs, fl, B); else o3_clear(B);
-					if((t2 >> v) & 1ull) o3_issue(w2, v, rs, fl, C); else o3_clear(C);
+				auto issue = [&](int v, OscTaps &A, OscTaps &B, OscTaps &C) __attribute__((always_inline)) {
+					if((t0 >> v) & 1ull) osctaps_issue(w0, v, rs, fl, A); else osctaps_clear(A);
+					if((t1 >> v) & 1ull) osctaps_issue(w1, v, rs, fl, B); else osctaps_clear(B);
+					if((t2 >> v) & 1ull) osctaps_issue(w2, v, rs, fl, C); else osctaps_clear(C);
 				};
 				unsigned long long m = mine;
 				int k = (int)__builtin_ctzll(m);
 				m &= m - 1;
-				O3Taps A0, B0, C0;
+				OscTaps A0, B0, C0;
 				issue(k, A0, B0, C0);
 				for(;;) {
 					const int kn = m ? (int)__builtin_ctzll(m) : -1;
-					O3Taps A1, B1, C1;
+					OscTaps A1, B1, C1;
 					if(kn >= 0)
 						issue(kn, A1, B1, C1);
 					// wtosc_do_fragment replacing, then twice adding (A2_PROCADD: wrapping)
-					const int x = wadd(wadd(o3_finish(A0, fl), o3_finish(B0, fl)), o3_finish(C0, fl));
-					tile[k * O3F_PITCH + lane] = in ? x >> 5 : 0;
+					const int x = wadd(wadd(osctaps_finish(A0, fl), osctaps_finish(B0, fl)), osctaps_finish(C0, fl));
+					tile[k * QUIET_PITCH + lane] = in ? x >> 5 : 0;
 					if(kn < 0)
 						break;
 					m &= m - 1;
@@ -306,19 +238,11 @@ void k_leaf_osc3filtpan(const A2DParams *__restrict__ pp, const int *__restrict_
 				// lane = frame
 				const int *tile = o3_tiles + (f % 3) * tsize;
 				const bool in = lane < n;
-				int acc0 = 0, acc1 = 0;
-				int cur_off = -1, cur_nch = 2;
+				BusRun run = busrun_begin();
 				for(unsigned long long m = mine; m; m &= m - 1) {
 					const int v = (int)__builtin_ctzll(m);
-					const int voff = rdl(my_off, v);
-					if(voff != cur_off) {
-						if(cur_off >= 0)
-							bus_add(cur_off, cur_nch, f, acc0, acc1);
-						acc0 = acc1 = 0;
-						cur_off = voff;
-						cur_nch = rdl(my_nch, v);
-					}
-					int y = tile[v * O3F_PITCH + lane];
+					busrun_voice(run, out, f, my_off, my_nch, v);
+					int y = tile[v * QUIET_PITCH + lane];
 					if(lpraw)
 						y = wmul(y, rdl(lp_l, v)) >> 3;	// (filt_step: the row holds l)
 					int v0 = rdl(g0, v), v1 = rdl(g1, v);
@@ -336,12 +260,11 @@ void k_leaf_osc3filtpan(const A2DParams *__restrict__ pp, const int *__restrict_
 						}
 					}
 					if(in) {
-						acc0 = wadd(acc0, mul64s(y, v0, 24));
-						acc1 = wadd(acc1, mul64s(y, v1, 24));
+						run.acc0 = wadd(run.acc0, mul64s(y, v0, 24));
+						run.acc1 = wadd(run.acc1, mul64s(y, v1, 24));
 					}
 				}
-				if(cur_off >= 0)
-					bus_add(cur_off, cur_nch, f, acc0, acc1);
+				busrun_end(run, out, f);
 			}
 		}
 		filt_barrier();
@@ -358,14 +281,14 @@ void k_leaf_osc3filtpan(const A2DParams *__restrict__ pp, const int *__restrict_
 	}
 }
 
-// voices per workgroup: at most O3F_MAXV (one per lane of the filter wavefront)
+// voices per workgroup: at most QUIET_MAXV (one per lane of the filter wavefront)
 int a2d_launch_leaf_osc3filtpan(const A2DParams *dparams, const A2DParams &hp, const int *dlist, int nlist, int vpg, void *stream)
 {
 	if(nlist <= 0)
 		return 0;
-	vpg = vpg < 1 ? 1 : vpg > O3F_MAXV ? O3F_MAXV : vpg;
-	const dim3 grid((nlist + vpg - 1) / vpg), block(64 * O3F_WAVES);
-	const size_t dyn = (size_t)3 * vpg * O3F_PITCH * sizeof(int);
+	vpg = vpg < 1 ? 1 : vpg > QUIET_MAXV ? QUIET_MAXV : vpg;
+	const dim3 grid((nlist + vpg - 1) / vpg), block(64 * QUIET_WAVES);
+	const size_t dyn = (size_t)3 * vpg * QUIET_PITCH * sizeof(int);
 	hipLaunchKernelGGL(k_leaf_osc3filtpan, grid, block, dyn, (hipStream_t)stream, dparams, dlist, nlist, vpg, hp.voices, hp.runs,
 			hp.ustate, hp.waves, hp.ptab, hp.wavecoef, hp.nfrags, hp.busmem);
 	return hipGetLastError() != hipSuccess;

@@ -8,7 +8,8 @@
 // (a2amd_winctl.h) steps the oscillator's control state over the window - pitch and amplitude rampers, mip level, the
 // wrap of a looped wave, a one-shot wave's end, a pitch out of range, an unloaded wave - and leaves the closed-form
 // words k_win_render renders from; then, lane = frame, the voices that play take their turn: the words out of the lanes
-// with v_readlane, two coefficient-table taps as win_taps_issue / win_oscs_finish take them, the next voice's loads
+// with v_readlane, two coefficient-table taps as win_taps_issue / win_oscs_finish take them (a2amd_quiet.h's OscTaps,
+// shared with k_leaf_osc3filtpan), the next voice's loads
 // issued before this one's arithmetic.  The sum of the wavefront's voices stays in a register: one atomic add per
 // (fragment, frame) and wavefront into channel 0, flushed where the output bus changes (the list is sorted by bus;
 // neighbouring buses may have different channel counts).  At the end the wavefront stores every OW_* word of its voices
@@ -22,31 +23,9 @@
 #include "a2amd_dsp.h"
 #include "a2amd_taps.h"
 #include "a2amd_winctl.h"
+#include "a2amd_quiet.h"
 
 #define OB_WPB 4	// wavefronts per workgroup
-
-// one voice's two taps of a frame, issued (win_taps_issue's words for one oscillator)
-struct BareTaps { Coef4 k1, k2; unsigned t1, t2; int ak, da; };
-
-// voice v's window words out of the lanes; where this lane's frame fl reads the wave; the loads
-DEV void bare_issue(const int (&w)[6], int v, const CoefRsrc rs, unsigned fl, BareTaps &T)
-{
-	const unsigned phlo = (unsigned)rdl(w[WO_B], v), phhi = (unsigned)rdl(w[WO_C], v), dph = (unsigned)rdl(w[WO_DPH], v);
-	const int cb = coef_base((unsigned)rdl(w[WO_A], v));
-	T.ak = rdl(w[WO_AK], v);
-	T.da = rdl(w[WO_DA], v);
-	T.t1 = tap_phase((uint64_t)phlo | ((uint64_t)phhi << 32), fl * dph);
-	T.t2 = T.t1 + ((dph >> 16) >> 1);
-	T.k1 = coef_at(rs, cb, T.t1);
-	T.k2 = coef_at(rs, cb, T.t2);
-}
-
-// wtosc_do_fragment's sample of frame fl, wtosc.c:227-229 (the amplitude ramper run frame by frame)
-DEV int bare_finish(const BareTaps &T, unsigned fl)
-{
-	const int h = inter_coefs(T.k1, T.t1, T.k2, T.t2);
-	return mul64s(h, wadd(T.ak, wmul(T.da, (int)fl)), 17);
-}
 
 __global__ __launch_bounds__(64 * OB_WPB)
 void k_leaf_oscbare(const A2DParams *__restrict__ pp, const int *__restrict__ list, int nlist, int vpw,
@@ -106,13 +85,13 @@ void k_leaf_oscbare(const A2DParams *__restrict__ pp, const int *__restrict__ li
 		int acc = 0, cur_off = -1, cur_nch = 1;
 		int k = (int)__builtin_ctzll(m);
 		m &= m - 1;
-		BareTaps T0;
-		bare_issue(w, k, rs, fl, T0);
+		OscTaps T0;
+		osctaps_issue(w, k, rs, fl, T0);
 		for(;;) {
 			const int kn = m ? (int)__builtin_ctzll(m) : -1;
-			BareTaps T1;
+			OscTaps T1;
 			if(kn >= 0)
-				bare_issue(w, kn, rs, fl, T1);
+				osctaps_issue(w, kn, rs, fl, T1);
 			const int voff = rdl(my_off, k);
 			if(voff != cur_off) {
 				if(cur_off >= 0 && acc)
@@ -121,7 +100,7 @@ void k_leaf_oscbare(const A2DParams *__restrict__ pp, const int *__restrict__ li
 				cur_off = voff;
 				cur_nch = rdl(my_nch, k);
 			}
-			const int x = bare_finish(T0, fl);
+			const int x = osctaps_finish(T0, fl);
 			acc = wadd(acc, in ? x : 0);
 			if(kn < 0)
 				break;
