@@ -319,6 +319,25 @@ int a2amd_wave_stats(a2amd_ctx *c, uint64_t *h2d, uint32_t *uploaded, uint32_t *
 	return A2AMD_OK;
 }
 
+// include/a2amd_wavepool.h: the host's bookkeeping as it stands, nothing of the device's
+int a2amd_wave_pool_info(const a2amd_ctx *c, struct a2amd_wave_pool_info *out)
+{
+	if(!c || !out)
+		return A2AMD_EINVAL;
+	memset(out, 0, sizeof(*out));
+	out->used = c->wavepool_used;
+	out->capacity = c->d_wavepool.cap;
+	for(const auto &r : c->wavepool_free)
+		out->free_samples += r.second;
+	out->coef4 = c->d_wavecoef4.d ? 1u : 0u;
+	for(const HWave &w : c->waves)
+		if(w.live && (w.dw.flags & A2D_WF_RAWTAPS))
+			++out->raw_waves;
+	out->reallocations = c->wavepool_reallocs;
+	out->regions_reused = c->wavepool_reused;
+	return A2AMD_OK;
+}
+
 static int wave_place(a2amd_ctx *c, uint64_t key, const a2amd_wavedesc *w, const a2amd_capture *cap, unsigned chunk = 0);
 
 int a2amd_wave_upload(a2amd_ctx *c, uint64_t key, const a2amd_wavedesc *w)
@@ -416,6 +435,7 @@ static int wave_place(a2amd_ctx *c, uint64_t key, const a2amd_wavedesc *w, const
 			c->wavepool_free[k].second -= total;
 			if(!c->wavepool_free[k].second)
 				c->wavepool_free.erase(c->wavepool_free.begin() + (long)k);
+			++c->wavepool_reused;
 			// work in flight may still read the old contents
 			HIPCHK(c, hipStreamSynchronize(c->stream));
 			break;
@@ -433,6 +453,7 @@ static int wave_place(a2amd_ctx *c, uint64_t key, const a2amd_wavedesc *w, const
 			if((c->wavepool_used + total) * entry > (((size_t)1 << 32) - 4096))
 				return c->fail(A2AMD_ENOMEM, "wave pool beyond %zu samples", (((size_t)1 << 32) - 4096) / entry);
 			if(int r = grow(c, c->d_wavepool, c->wavepool_used + total, 1, true)) return r;
+			++c->wavepool_reallocs;
 			// the coefficient tables follow the pool: rebuilt for what is in it
 			if(int r = grow(c, c->d_wavecoef, c->d_wavepool.cap, A2D_COEF_WORDS, false)) return r;
 			if(keep4) {

@@ -576,6 +576,7 @@ struct a2amd_ctx {
 	// end (oscillators still name it until they have rendered a window and noticed)
 	std::vector<std::pair<size_t, size_t>> deferred_wavepool_free;
 	std::vector<int> free_wave_slots, deferred_wave_slots;
+	uint32_t wavepool_reallocs = 0, wavepool_reused = 0;	// a2amd_wave_pool_info (include/a2amd_wavepool.h)
 
 	DevBuf<A2DVoice> d_voices;
 	DevBuf<A2DVoiceExt> d_vext;

@@ -175,6 +175,15 @@ class a2amd_vm_batch_info(C.Structure):
                                              for n, _ in self._fields_) + ")")
 
 
+class a2amd_wave_pool_info(C.Structure):
+    """include/a2amd_wavepool.h: what the host has done with the wave pool and the tables that follow it"""
+    _fields_ = [(n, C.c_uint64) for n in ("used", "capacity", "free_samples")] + \
+               [(n, C.c_uint32) for n in ("coef4", "raw_waves", "reallocations", "regions_reused")]
+
+    def __repr__(self):
+        return "wave_pool_info(" + ", ".join(f"{n}={getattr(self, n)}" for n, _ in self._fields_) + ")"
+
+
 class a2amd_vm_state(C.Structure):
     """include/a2amd_vm.h: A2_vmstate, field for field"""
     _fields_ = [("waketime", C.c_uint32), ("state", C.c_uint8), ("func", C.c_uint8), ("pc", C.c_uint16),
@@ -256,6 +265,17 @@ class Backend:
             self._osc2_tame_rule = fn("osc2_tame_rule", u32, i32, i32)
             self._wave_level_tame = fn("wave_level_tame", i32, C.POINTER(C.c_int16), u32)
             self._osc2_tame_voices = fn("osc2_tame_voices", i32, vp, C.POINTER(C.c_uint64))
+        # include/a2amd_wavepool.h: the wave pool's bookkeeping (the product library only)
+        if hasattr(lib, prefix + "wave_pool_info"):
+            self._wave_pool_info = fn("wave_pool_info", i32, vp, C.POINTER(a2amd_wave_pool_info))
+
+            def wave_pool_info():
+                """a2amd_wave_pool_info: pool samples used, capacity, samples on the free list, whether the 16 byte
+                table exists, live waves flagged raw, pool reallocations and regions reused since open"""
+                pi = a2amd_wave_pool_info()
+                self._chk(self._wave_pool_info(self.ctx, C.byref(pi)), "wave_pool_info")
+                return pi
+            self.wave_pool_info = wave_pool_info
         self._last_batch_fbdpan = None
         if hasattr(lib, prefix + "last_batch_fbdpan"):
             self._last_batch_fbdpan = fn("last_batch_fbdpan", i32, vp, C.POINTER(a2amd_fbdpan_batch_info))

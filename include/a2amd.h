@@ -469,5 +469,7 @@ int  a2amd_last_batch(const a2amd_ctx *ctx, a2amd_batch_info *bi);
 #include "a2amd_osc2tame.h"
 /* The quiet kernel of three-oscillator subtractive leads: a2amd_last_batch_osc3filt(). */
 #include "a2amd_osc3filt.h"
+/* What the host has done with the wave pool and its tables - growth, the footprint policy, reuse: a2amd_wave_pool_info(). */
+#include "a2amd_wavepool.h"
 
 #endif /* A2AMD_H */
