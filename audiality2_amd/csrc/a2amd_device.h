@@ -284,6 +284,67 @@ A2D_HD unsigned a2d_osc2_tame(unsigned tame0, unsigned tame1)
 	return tame0 && tame1 ? 1u : 0u;
 }
 
+// The launch shape both kernels of the class take: voices per wavefront within a wavefront's lanes, and one slice
+// where nothing can be staged for a commit.
+A2D_HD void a2d_osc2_shape(int *vpw, int *ysplit, bool can_stage)
+{
+	*vpw = *vpw < 1 ? 1 : (*vpw > 64 ? 64 : *vpw);
+	if(*ysplit < 1 || !can_stage)
+		*ysplit = 1;
+}
+
+// ---- k_leaf_osc2tame (a2amd_osc2tame.hip): the kernel of whole wavefronts of settled, tame, power-of-two voices ----
+// It is launched in front of k_leaf_osc2pan, with that kernel's shape, for a class of at least A2D_OSC2TAME_MIN voices
+// (fewer: the second launch costs more than the walk saves; profiles/osc2_tame_kernel.md) in a batch all of whose
+// super-chunks are whole in every slice: frames[f] of the nfrags fragments, by the kernel's own rule.
+#define A2D_OSC2TAME_MIN 1024
+A2D_HD bool a2d_osc2_all_whole(const unsigned *frames, int nfrags, int ysplit)
+{
+	if(nfrags <= 0 || ysplit < 1)
+		return false;
+	for(int slice = 0; slice < ysplit; ++slice) {
+		int c_lo, c_hi, nslices;
+		if(!a2d_osc2_slice(nfrags, ysplit, slice, &c_lo, &c_hi, &nslices))
+			break;
+		for(int s_lo = c_lo; s_lo < c_hi; s_lo += A2D_OSC2_SCH / A2D_OSC2_FCH) {
+			const int s_hi = s_lo + A2D_OSC2_SCH / A2D_OSC2_FCH < c_hi ? s_lo + A2D_OSC2_SCH / A2D_OSC2_FCH : c_hi;
+			const int fa = s_lo * A2D_OSC2_FCH, fb = s_hi * A2D_OSC2_FCH < nfrags ? s_hi * A2D_OSC2_FCH : nfrags;
+			unsigned n = 0;
+			for(int f = fa; f < fb; ++f)
+				n += frames[f];
+			if(!a2d_osc2_whole(0, n - frames[fb - 1], frames[fb - 1], fb - fa))
+				return false;
+		}
+	}
+	return true;
+}
+// One voice, from its state at the batch's start.  records: runs[slot].count; osc0, osc1: a2s_osc_settled() of its
+// oscillators; pan: a2s_arrived() of the panmix's rampers; waves: settled_wave() of both (a2s_wave_ok); tame0, tame1:
+// A2DWave::tame's bits of the two levels (a2d_osc2_tame); size, dph: the levels' sizes and increments; ph: the phases AT
+// the levels (the state's phase >> the level); frames: the batch's, nfrags * A2D_FRAG.
+// The sizes are powers of two - the modulus is a mask - and both phases stay on the mask branch of the general kernel's
+// chunk (osc2_chunk: !(ph >> 48)) wherever that kernel would test them: at a super-chunk's first chunk, ph + before * dph
+// with before <= frames, and at every later chunk a wrapped phase plus a fragment's increments, below
+// (size << 24) + A2D_FRAG * dph.
+A2D_HD bool a2d_osc2tame_voice(unsigned records, bool osc0, bool osc1, bool pan, bool waves, unsigned tame0, unsigned tame1,
+		unsigned size0, unsigned size1, unsigned dph0, unsigned dph1, uint64_t ph0, uint64_t ph1, unsigned frames)
+{
+	if(records || !(osc0 && osc1 && pan && waves) || !a2d_osc2_tame(tame0, tame1))
+		return false;
+	if(!size0 || (size0 & (size0 - 1)) || !size1 || (size1 & (size1 - 1)))
+		return false;
+	if((ph0 >> 48) || (ph1 >> 48))
+		return false;
+	if(((ph0 + (uint64_t)frames * dph0) >> 48) || ((ph1 + (uint64_t)frames * dph1) >> 48))
+		return false;
+	return !((((uint64_t)size0 << 24) + (uint64_t)A2D_FRAG * dph0) >> 48) && !((((uint64_t)size1 << 24) + (uint64_t)A2D_FRAG * dph1) >> 48);
+}
+// ... and the wavefront: every one of its nv voices (ok: bit v = a2d_osc2tame_voice() of voice v, no bit from nv on)
+A2D_HD bool a2d_osc2tame_wave(unsigned long long ok, int nv)
+{
+	return nv >= 1 && nv <= 64 && ok == (nv == 64 ? ~0ull : (1ull << nv) - 1);
+}
+
 // A noise oscillator's default window - a fragment without records for its voice - takes the engine's RNG word from
 // the batch's seed table (a window the engine called for carries an R_NOISESEED record instead).
 // Invariant (the host's: a2amd_fragment_repeat_noise, upload()): in a batch with nseed set, a noise oscillator meets a
@@ -460,7 +521,12 @@ int a2d_launch_leaf_oscfiltpan(const A2DParams *dparams, const A2DParams &hp, co
 int a2d_launch_scatter_runs(const int *didx, const A2DRun *dval, int n, A2DRun *druns, void *stream);
 int a2d_launch_leaf_osc2pan(const A2DParams *dparams, const A2DParams &hp, const int *dlist, int nlist,
 		int vpw, int ysplit, int *ustage, unsigned char *staged, void *stream, A2DCommit *defer, int voice_major, int lds_taps,
-		int tame, unsigned long long *tame_count, int *ysplit_used);
+		int tame, unsigned long long *tame_count, int *ysplit_used, const unsigned char *taken = nullptr);
+// a2amd_osc2tame.hip: launched in front of the launch above, with its vpw and ysplit; taken[wavefront of the list]: 1 this
+// kernel rendered it, 0 it is the launch above's; taken_count: the 1s, summed over the launches
+int a2d_launch_leaf_osc2tame(const A2DParams *dparams, const A2DParams &hp, const int *dlist, int nlist, int vpw, int ysplit,
+		int *ustage, unsigned char *staged, void *stream, int lds_taps, unsigned long long *tame_count, unsigned char *taken,
+		unsigned long long *taken_count);
 // wtosc[+wtosc] [-> filter12] -> panmix voices that carry records this batch (nosc = 1 | 2, filt = 0 | 1)
 // skip_empty: the list's voices get their records from the device VM (a2amd_vm.hip); those it left
 // without any this batch are rendered by their class's quiet kernel

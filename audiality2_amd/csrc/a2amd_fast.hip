@@ -309,27 +309,6 @@ enum { SV_MODE = 0, SV_WAVE, SV_DPHASE, SV_PHLO, SV_PHHI, SV_PRAMP, SV_P = 6, SV
 // Extra per-lane words derived once per launch from a voice's state
 enum { DV_SETTLED = 0, DV_MM, DV_DPH, DV_SIZEM, DV_DOFF, DV_V0, DV_V1, DV_NWORDS };
 
-// The four words DV_MM .. DV_DOFF (k_leaf_osc2pan's OD_MM .. OD_DOFF) of an oscillator at a constant pitch on wave w:
-// mip level, increment there, that level's size and place in the pool.  False: no wave for the settled paths - or
-// 'settled' was false already, and then the descriptor's test words are not read (k_leaf_osc2pan's second oscillator).
-// periodic: A2DWave::periodic's bit of that level (k_leaf_osc2pan: may the level be copied to LDS)
-// tame: A2DWave::tame's bit of it (k_leaf_osc2pan: may the level's taps take the fused steps)
-DEV bool settled_wave(const A2DWave *w, unsigned dphase, int *d, bool settled = true, unsigned *periodic = nullptr,
-		unsigned *tame = nullptr)
-{
-	unsigned dph;
-	const unsigned mm = a2s_mip(dphase, w->period, &dph);
-	d[0] = (int)mm;
-	d[1] = (int)dph;
-	d[2] = (int)w->size[mm];
-	d[3] = (int)w->off[mm];
-	if(periodic)
-		*periodic = (w->periodic >> mm) & 1u;
-	if(tame)
-		*tame = (w->tame >> mm) & 1u;
-	return settled && a2s_wave_ok(w->size[0], w->flags, dph);
-}
-
 // an oscillator's state from / to the unit's state words in memory (wave-uniform address)
 // (volatile: what this wavefront stored a chunk ago must come from memory, not from a scalar or
 // vector cache line fetched before)
@@ -358,18 +337,6 @@ DEV void osc_to_mem(int *w, const OscS &o)
 	w[OW_PRAMPING] = o.p_ramping;
 	w[OW_P] = o.p.value; w[OW_P + 1] = o.p.target; w[OW_P + 2] = o.p.delta; w[OW_P + 3] = o.p.timer;
 	w[OW_A] = o.a.value; w[OW_A + 1] = o.a.target; w[OW_A + 2] = o.a.delta; w[OW_A + 3] = o.a.timer;
-}
-
-// What a time-sliced launch staged for the voice at one entry of its list, for the commit: every entry is
-// written in every batch, by exactly one wavefront - the slice that walked the voice if it had something
-// moving, the last slice otherwise.
-DEV void stage_mark(unsigned char *m, bool mine, bool settled, bool last_slice, bool walker)
-{
-	if(mine && !settled) {
-		if(walker)
-			*m = A2D_STAGED_FULL;
-	} else if(last_slice)
-		*m = mine ? A2D_STAGED_PHASES : A2D_STAGED_NONE;
 }
 
 #define OSC1_WPE 4
@@ -1026,13 +993,17 @@ void k_leaf_osc2pan(const A2DParams *__restrict__ pp, const int *__restrict__ li
 		const int16_t *__restrict__ wavepool, const A2DWave *__restrict__ waves,
 		const uint32_t *__restrict__ ptab, int *__restrict__ busmem, const int *__restrict__ wavecoef,
 		unsigned char *__restrict__ staged, int vmajor, int lds_taps, const int *__restrict__ wavecoef4, int tame,
-		unsigned long long *__restrict__ tame_count)
+		unsigned long long *__restrict__ tame_count, const unsigned char *__restrict__ taken)
 {
 	const A2DParams &p = *pp;
 	const int wv = rfl((int)(threadIdx.x >> 6));	// (wave-uniform, and known to the compiler as such)
 	const int lane = threadIdx.x & 63;
 	const int first = (blockIdx.x * FAST_WPB + wv) * vpw;
 	if(first >= nlist)
+		return;
+	// (the hand-over: k_leaf_osc2tame, launched in front of this kernel with the same shape, rendered this wavefront's
+	// voices in every slice and left their state - a2amd_osc2tame.hip; null: it was not launched)
+	if(taken && taken[blockIdx.x * FAST_WPB + wv])
 		return;
 	const int nv = min(vpw, nlist - first);
 	const int nfrags = p.nfrags;
@@ -3485,13 +3456,11 @@ int a2d_launch_leaf_oscpan(const A2DParams *dparams, const A2DParams &hp, const 
 
 int a2d_launch_leaf_osc2pan(const A2DParams *dparams, const A2DParams &hp, const int *dlist, int nlist,
 		int vpw, int ysplit, int *ustage, unsigned char *staged, void *stream, A2DCommit *defer, int voice_major, int lds_taps,
-		int tame, unsigned long long *tame_count, int *ysplit_used)
+		int tame, unsigned long long *tame_count, int *ysplit_used, const unsigned char *taken)
 {
 	if(nlist <= 0)
 		return 0;
-	vpw = vpw < 1 ? 1 : (vpw > 64 ? 64 : vpw);
-	if(ysplit < 1 || !ustage || !staged)
-		ysplit = 1;
+	a2d_osc2_shape(&vpw, &ysplit, ustage && staged);
 	if(ysplit_used)
 		*ysplit_used = ysplit;
 	int nwaves = (nlist + vpw - 1) / vpw;
@@ -3501,12 +3470,12 @@ int a2d_launch_leaf_osc2pan(const A2DParams *dparams, const A2DParams &hp, const
 		hipLaunchKernelGGL(k_leaf_osc2pan<true>, dim3(nblocks, ysplit), dim3(64 * FAST_WPB), 0, (hipStream_t)stream,
 				dparams, dlist, nlist, vpw, ysplit, hp.voices, (const int *)hp.ustate,
 				ysplit > 1 ? ustage : hp.ustate, hp.wavepool, hp.waves, hp.ptab, hp.busmem, hp.wavecoef, staged, voice_major, lds_taps,
-				hp.wavecoef4, 1, tame_count);
+				hp.wavecoef4, 1, tame_count, taken);
 	else
 		hipLaunchKernelGGL(k_leaf_osc2pan<false>, dim3(nblocks, ysplit), dim3(64 * FAST_WPB), 0, (hipStream_t)stream,
 				dparams, dlist, nlist, vpw, ysplit, hp.voices, (const int *)hp.ustate,
 				ysplit > 1 ? ustage : hp.ustate, hp.wavepool, hp.waves, hp.ptab, hp.busmem, hp.wavecoef, staged, voice_major, lds_taps,
-				(const int *)nullptr, 0, (unsigned long long *)nullptr);
+				(const int *)nullptr, 0, (unsigned long long *)nullptr, taken);
 	if(ysplit > 1) {
 		A2DCommit cm = { dlist, nlist, 2, ustage, staged };
 		if(defer)

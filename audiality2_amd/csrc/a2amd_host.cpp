@@ -94,6 +94,8 @@ int a2amd_open(const a2amd_config *cfg, a2amd_ctx **out)
 	}
 	OPENCHK(hipMalloc((void **)&c->d_tame_count, sizeof(unsigned long long)));
 	OPENCHK(hipMemset(c->d_tame_count, 0, sizeof(unsigned long long)));
+	OPENCHK(hipMalloc((void **)&c->d_taken_count, sizeof(unsigned long long)));
+	OPENCHK(hipMemset(c->d_taken_count, 0, sizeof(unsigned long long)));
 #undef OPENCHK
 	*out = c;
 	return A2AMD_OK;
@@ -136,7 +138,7 @@ void a2amd_close(a2amd_ctx *c)
 	for(int k = 0; k < 5; ++k)
 		if(c->win_ev[k])
 			hipEventDestroy(c->win_ev[k]);
-	hipFree(c->d_waves.d); hipFree(c->d_wavepool.d); hipFree(c->d_wavecoef.d); hipFree(c->d_wavecoef4.d); hipFree(c->d_tame_count); hipFree(c->d_busmem.d);
+	hipFree(c->d_waves.d); hipFree(c->d_wavepool.d); hipFree(c->d_wavecoef.d); hipFree(c->d_wavecoef4.d); hipFree(c->d_tame_count); hipFree(c->d_taken_count); hipFree(c->d_osc2_taken.d); hipFree(c->d_busmem.d);
 	vm_close(c);
 	hipFree(c->capture.d); hipFree(c->capture.d_fragpos); hipFree(c->d_wavepost.d);
 	hipFree(c->d_fbdmem.d); hipFree(c->d_fmstate.d); hipFree(c->d_xio.d); hipFree(c->d_fmsine); hipFree(c->d_list.d); hipFree(c->d_staged.d); hipFree(c->d_scatter.d); hipFree(c->d_ptab); hipFree(c->d_blob.d);

@@ -544,6 +544,8 @@ struct a2amd_ctx {
 	// 3 x wtosc-filter12-panmix voices (CLS_OSC3FILTPAN): likewise, the segment's voices by who renders them this batch
 	uint32_t n_o3f_quiet = 0, n_o3f_gliding = 0, n_o3f_records = 0;
 	a2amd_osc3filt_batch_info last_osc3filt = {};	// a2amd_last_batch_osc3filt()
+	bool osc2quiet_hold = false;	// a2amd_osc2quiet_hold(): k_leaf_osc2tame is not launched
+	a2amd_osc2quiet_batch_info last_osc2quiet = {};	// a2amd_last_batch_osc2quiet(): k_leaf_osc2tame's launch; taken_total is read when asked for
 	a2amd_osc2_batch_info last_osc2 = {};	// a2amd_last_batch_osc2(): the launch; the walks are counted when asked for
 	a2amd_fbdpan_batch_info last_fbdpan = {};	// a2amd_last_batch_fbdpan(): upload() counts, launch_depth() sets launched
 	a2amd_bus_windows_info last_buswin = {};	// a2amd_last_batch_bus_windows(): likewise, reset by every upload()
@@ -592,6 +594,7 @@ struct a2amd_ctx {
 	DevBuf<int32_t> d_wavecoef4;	// ... and 4 words each: the fused steps' entries (a2amd_taps.h: Coef4x), kept beside it until the
 					// pool outgrows the footprint policy's entries or the policy is forced to raw taps (coef4_wanted), then
 					// dropped for good
+	unsigned long long *d_taken_count = nullptr;	// wavefronts k_leaf_osc2tame took, summed over its launches (a2amd_last_batch_osc2quiet)
 	unsigned long long *d_tame_count = nullptr;	// voices k_leaf_osc2pan gave the tame bit, summed over its launches (a2amd_osc2_tame_voices)
 	DevBuf<int32_t> d_busmem;
 	DevBuf<int32_t> d_fbdmem;	// cap in buffer pairs
@@ -599,6 +602,7 @@ struct a2amd_ctx {
 	DevBuf<int32_t> d_xio;		// cap in slots of A2D_XIO_SLOT words
 	uint32_t *d_fmsine = nullptr;
 	DevBuf<int> d_list;
+	DevBuf<unsigned char> d_osc2_taken;	// per wavefront of k_leaf_osc2pan's launch list: 1 k_leaf_osc2tame rendered it (at most one per list entry)
 	DevBuf<unsigned char> d_staged;	// per entry of d_list: what a time-sliced leaf kernel staged there (A2D_STAGED_*)
 	DevBuf<int> d_scatter;	// idx[k] then A2DRun[k] for k_scatter_runs
 	uint32_t *d_ptab = nullptr;

@@ -573,6 +573,29 @@ int a2amd_osc2_tame_voices(a2amd_ctx *c, uint64_t *out)
 	return A2AMD_OK;
 }
 
+int a2amd_last_batch_osc2quiet(a2amd_ctx *c, a2amd_osc2quiet_batch_info *out)
+{
+	if(!c || !out)
+		return A2AMD_EINVAL;
+	use_device(c);
+	unsigned long long n = 0;
+	HIPCHK(c, hipStreamSynchronize(c->stream));
+	HIPCHK(c, hipMemcpy(&n, c->d_taken_count, sizeof(n), hipMemcpyDeviceToHost));
+	*out = c->last_osc2quiet;
+	out->taken_total = n;
+	return A2AMD_OK;
+}
+
+int a2amd_osc2quiet_hold(a2amd_ctx *c, int hold)
+{
+	if(!c)
+		return A2AMD_EINVAL;
+	if(c->osc2quiet_hold != (hold != 0))
+		drop_graphs(c);
+	c->osc2quiet_hold = hold != 0;
+	return A2AMD_OK;
+}
+
 int a2amd_last_batch_fbdpan(const a2amd_ctx *c, a2amd_fbdpan_batch_info *out)
 {
 	if(!c || !out)

@@ -423,6 +423,19 @@ static ListRange append_range(std::vector<int> &to, const std::vector<int> &l)
 	return r;
 }
 
+// Is k_leaf_osc2tame launched in front of k_leaf_osc2pan for a batch of these fragments (include/a2amd_osc2tame_kernel.h):
+// where the walk it holds exists at all - the fused steps (bit 18 clear, the 16 byte table there) and the voice-major walk
+// (the switch of value 16 clear) on, every super-chunk of every slice whole - the class is large enough to pay for a second
+// launch (or bit 20), and neither bit 19 nor a2amd_osc2quiet_hold() says no.  No fragment is longer than A2D_FRAG, so
+// "whole" does not depend on the slices: one slice is asked.  The one statement of the rule: launch_depth() launches by it,
+// and upload() keeps a captured graph only while it gives the same answer.
+static bool osc2_pair_wanted(const a2amd_ctx *c, const unsigned *frames, int nfrags)
+{
+	const int n = c->leaf[LEAF_OSC2PAN].count;
+	return n && !(c->sw.debug & ((1 << 18) | 16 | (1 << 19))) && c->hparams.wavecoef4 && !c->osc2quiet_hold &&
+			(n >= A2D_OSC2TAME_MIN || (c->sw.debug & (1 << 20))) && a2d_osc2_all_whole(frames, nfrags, 1);
+}
+
 int upload(a2amd_ctx *c)
 {
 	// (voices the device VM took over during this batch: the host's interpreter carries them to its
@@ -502,7 +515,10 @@ int upload(a2amd_ctx *c)
 				HIPCHK(c, hipEventRecord(c->blob_ev[bi], c->stream));
 				c->blob_busy[bi] = true;
 				c->hparams = p;
-				if(c->nfrags != c->blob_nfrags) {
+				// (... and while k_leaf_osc2tame is, as in the batch before, launched or not: a context whose class of
+				// `wtosc; wtosc; panmix` voices is too small for it, or has it switched off, keeps its graphs as before)
+				if(c->nfrags != c->blob_nfrags ||
+						osc2_pair_wanted(c, c->fragframes, c->nfrags) != osc2_pair_wanted(c, c->blob_frames, c->nfrags)) {
 					drop_graphs(c);
 					c->quiet_streak = 0;
 				} else
@@ -934,6 +950,7 @@ int upload(a2amd_ctx *c)
 		}
 		if(int r = grow(c, c->d_list, c->list_all.size() + 64, 1, false)) return r;
 		if(int r = grow(c, c->d_staged, c->d_list.cap, 1, false)) return r;	// (one marker per list entry)
+		if(int r = grow(c, c->d_osc2_taken, c->d_list.cap, 1, false)) return r;	// (one per wavefront of a list: no more than its entries)
 		if(!c->list_all.empty())
 			HIPCHK(c, hipMemcpyAsync(c->d_list.d, c->list_all.data(), c->list_all.size() * sizeof(int),
 					hipMemcpyHostToDevice, c->stream));
@@ -1910,13 +1927,26 @@ static int launch_leaves(a2amd_ctx *c, LeafPass &lp)
 		const int lds_taps = !(c->sw.debug & (1 << 17));
 		// (... bit 18: no voice takes the fused steps of tame levels - include/a2amd_osc2tame.h)
 		const int tame = !(c->sw.debug & (1 << 18));
+		// Whole wavefronts of settled, tame voices are k_leaf_osc2tame's, launched in front with the same shape
+		// (osc2_pair_wanted; the shape is fixed here so that both launches count the same wavefronts)
+		a2d_osc2_shape(&vpw, &ysplit, c->d_ustage.d && c->d_staged.d);
+		const bool pair = osc2_pair_wanted(c, c->fragframes, c->nfrags);
+		if(pair) {
+			if(a2d_launch_leaf_osc2tame(c->d_params, c->hparams, list + osc2pan.first, osc2pan.count, vpw, ysplit, c->d_ustage.d,
+					c->d_staged.d + osc2pan.first, c->stream, lds_taps, c->d_tame_count, c->d_osc2_taken.d, c->d_taken_count))
+				return c->fail(A2AMD_EHIP, "2-osc tame leaf launch failed: %s", hipGetErrorString(hipGetLastError()));
+			++c->stats.launches;
+			c->last_osc2quiet.launched = 1;
+			c->last_osc2quiet.wavefronts = (uint32_t)((osc2pan.count + vpw - 1) / vpw);
+		}
 		if(a2d_launch_leaf_osc2pan(c->d_params, c->hparams, list + osc2pan.first, osc2pan.count,
-				vpw, ysplit, c->d_ustage.d, c->d_staged.d + osc2pan.first, c->stream, &pend.c[pend.n], voice_major, lds_taps, tame, c->d_tame_count, &ysplit))
+				vpw, ysplit, c->d_ustage.d, c->d_staged.d + osc2pan.first, c->stream, &pend.c[pend.n], voice_major, lds_taps, tame, c->d_tame_count, &ysplit,
+				pair ? c->d_osc2_taken.d : nullptr))
 			return c->fail(A2AMD_EHIP, "2-osc leaf launch failed: %s", hipGetErrorString(hipGetLastError()));
 		// (a2amd_last_batch_osc2(): the launch as it went out; the walks follow from it and the batch's fragment lengths)
 		c->last_osc2.launched = 1;
 		c->last_osc2.voices = (uint32_t)osc2pan.count;
-		c->last_osc2.vpw = (uint32_t)std::min(std::max(vpw, 1), 64);
+		c->last_osc2.vpw = (uint32_t)vpw;
 		c->last_osc2.ysplit = (uint32_t)ysplit;
 		c->last_osc2.voice_major = (uint32_t)voice_major;
 		if(pend.c[pend.n].nlist)
@@ -2101,6 +2131,7 @@ static int issue_leaf_phase(a2amd_ctx *c, bool consume, bool consume_sub, hipEve
 	c->last_osc3filt.gliding_voices = c->n_o3f_gliding;
 	c->last_osc3filt.record_voices = c->n_o3f_records;
 	c->last_osc2 = a2amd_osc2_batch_info{};
+	c->last_osc2quiet = a2amd_osc2quiet_batch_info{};
 	// The batch's other leaf kernels - the quiet kernels of the classes, the records kernels where the window kernels
 	// are not in use, the general kernel - as a block that runs once: normally behind the window kernels, and
 	// (round 6) from INSIDE issue_windows, between its control passes and its render passes, when a speculative VM

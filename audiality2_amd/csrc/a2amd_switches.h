@@ -21,7 +21,7 @@ static inline int within(const char *name, int lo, int hi) { const int v = num(n
 	X(bool, cls_check, a2sw::set("A2AMD_CLS_CHECK"))	/* unset. Set: every rebuild of the launch lists classifies every voice anew and fails on a remembered class that no longer holds */ \
 	X(int, coef_cache_mb, a2sw::full("A2AMD_COEF_CACHE_MB", 192))	/* 192 ("" too): MB of Hermite entries beyond which waves of 4 096 samples or more play from their samples */ \
 	X(int, dbg_walk, a2sw::num("A2AMD_DBG_WALK", 0))	/* 0. Bits: 1 a2amd_voice_process() never takes its short path, 2 ... never reports the default window (debugging the walk) */ \
-	X(int, debug, a2sw::num("A2AMD_DEBUG", 0))		/* 0. A2DParams::debug, ablations: 1 no bus atomics (breaks the audio on purpose), 4 no shadow lanes in the FM kernel, 8 k_leaf_oscfiltpan's wavefronts add to the bus themselves, not through the workgroup's LDS sums, 16 k_leaf_osc2pan walks no super-chunk voice by voice (a launch argument; include/a2amd_osc2.h), 1 << 17 that walk stages no mip level in LDS (a launch argument; include/a2amd_osc2lds.h), 1 << 18 that walk takes the fused multiply-add steps for no voice (a launch argument; include/a2amd_osc2tame.h) */ \
+	X(int, debug, a2sw::num("A2AMD_DEBUG", 0))		/* 0. A2DParams::debug, ablations: 1 no bus atomics (breaks the audio on purpose), 4 no shadow lanes in the FM kernel, 8 k_leaf_oscfiltpan's wavefronts add to the bus themselves, not through the workgroup's LDS sums, 16 k_leaf_osc2pan walks no super-chunk voice by voice (a launch argument; include/a2amd_osc2.h), 1 << 17 that walk stages no mip level in LDS (a launch argument; include/a2amd_osc2lds.h), 1 << 18 that walk takes the fused multiply-add steps for no voice (a launch argument; include/a2amd_osc2tame.h), 1 << 19 k_leaf_osc2tame is never launched in front of k_leaf_osc2pan, 1 << 20 it is whatever the class's size (the host's launch rule; include/a2amd_osc2tame_kernel.h) */ \
 	X(bool, debug_noise, a2sw::set("A2AMD_DEBUG_NOISE"))	/* unset. Set: trace the noise oscillators' seeds (debugging aid) */ \
 	X(int, f2vpw, a2sw::num("A2AMD_F2VPW", 0))		/* 0 = the launcher's own choice: voices per workgroup of k_leaf_osc2filtpan; and, clamped to 1..64, of k_leaf_osc3filtpan (0: by count) */ \
 	X(bool, fmvpw_set, a2sw::set("A2AMD_FMVPW")) X(int, fmvpw, a2sw::num("A2AMD_FMVPW", 0))	/* unset = by count: voices per wavefront of k_leaf_fmpan. Set: no one-launch FM path */ \

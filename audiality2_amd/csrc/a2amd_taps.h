@@ -8,6 +8,7 @@
 #include "a2amd_device.h"
 #include "a2amd_dsp.h"
 #include "a2amd_fm.h"
+#include "a2amd_settled.h"
 
 #define FAST_WPB   4		// wavefronts per workgroup
 #define FAST_FCH   A2D_FAST_FCH	// fragments whose bus sums stay in registers at a time
@@ -351,3 +352,36 @@ DEV void flush_tile(int *busmem, int off, int nch, int f0, int nf, int nrows, in
 	}
 }
 
+// ---- the time-sliced settled kernels' prologue and epilogue (k_leaf_oscpan, k_leaf_osc2pan, k_leaf_osc2tame) ----
+// The four words DV_MM .. DV_DOFF (k_leaf_osc2pan's OD_MM .. OD_DOFF) of an oscillator at a constant pitch on wave w:
+// mip level, increment there, that level's size and place in the pool.  False: no wave for the settled paths - or
+// 'settled' was false already, and then the descriptor's test words are not read (k_leaf_osc2pan's second oscillator).
+// periodic: A2DWave::periodic's bit of that level (k_leaf_osc2pan: may the level be copied to LDS)
+// tame: A2DWave::tame's bit of it (k_leaf_osc2pan: may the level's taps take the fused steps)
+DEV bool settled_wave(const A2DWave *w, unsigned dphase, int *d, bool settled = true, unsigned *periodic = nullptr,
+		unsigned *tame = nullptr)
+{
+	unsigned dph;
+	const unsigned mm = a2s_mip(dphase, w->period, &dph);
+	d[0] = (int)mm;
+	d[1] = (int)dph;
+	d[2] = (int)w->size[mm];
+	d[3] = (int)w->off[mm];
+	if(periodic)
+		*periodic = (w->periodic >> mm) & 1u;
+	if(tame)
+		*tame = (w->tame >> mm) & 1u;
+	return settled && a2s_wave_ok(w->size[0], w->flags, dph);
+}
+
+// What a time-sliced launch staged for the voice at one entry of its list, for the commit: every entry is
+// written in every batch, by exactly one wavefront - the slice that walked the voice if it had something
+// moving, the last slice otherwise.
+DEV void stage_mark(unsigned char *m, bool mine, bool settled, bool last_slice, bool walker)
+{
+	if(mine && !settled) {
+		if(walker)
+			*m = A2D_STAGED_FULL;
+	} else if(last_slice)
+		*m = mine ? A2D_STAGED_PHASES : A2D_STAGED_NONE;
+}

@@ -144,6 +144,14 @@ class a2amd_osc2_batch_info(C.Structure):
         return "osc2_batch_info(" + ", ".join(f"{n}={getattr(self, n)}" for n, _ in self._fields_) + ")"
 
 
+class a2amd_osc2quiet_batch_info(C.Structure):
+    """include/a2amd_osc2tame_kernel.h: k_leaf_osc2tame's launch in front of k_leaf_osc2pan in the most recent batch"""
+    _fields_ = [("launched", C.c_uint32), ("wavefronts", C.c_uint32), ("taken_total", C.c_uint64)]
+
+    def __repr__(self):
+        return "osc2quiet_batch_info(" + ", ".join(f"{n}={getattr(self, n)}" for n, _ in self._fields_) + ")"
+
+
 class a2amd_fbdpan_batch_info(C.Structure):
     """include/a2amd_fbdpan.h: who rendered the pan-tailed delay chains (inline; fbdelay x 1..4; panmix >) of the most recent batch"""
     _fields_ = [(n, C.c_uint32) for n in ("launched", "class_voices", "quiet_voices", "gliding_voices", "record_voices",
@@ -254,6 +262,10 @@ class Backend:
         self._last_batch_osc2 = None
         if hasattr(lib, prefix + "last_batch_osc2"):
             self._last_batch_osc2 = fn("last_batch_osc2", i32, vp, C.POINTER(a2amd_osc2_batch_info))
+        self._last_batch_osc2quiet = None
+        if hasattr(lib, prefix + "last_batch_osc2quiet"):
+            self._last_batch_osc2quiet = fn("last_batch_osc2quiet", i32, vp, C.POINTER(a2amd_osc2quiet_batch_info))
+            self._osc2quiet_hold = fn("osc2quiet_hold", i32, vp, i32)
         # include/a2amd_osc2lds.h: pure functions, no context (the product library only)
         self._osc2_stage_rule = self._wave_level_periodic = None
         if hasattr(lib, prefix + "osc2_stage_rule"):
@@ -460,6 +472,22 @@ class Backend:
         bi = a2amd_osc2_batch_info()
         self._chk(self._last_batch_osc2(self.ctx, C.byref(bi)), "last_batch_osc2")
         return bi
+
+    def last_batch_osc2quiet(self):
+        """a2amd_last_batch_osc2quiet: whether k_leaf_osc2tame was launched in front of k_leaf_osc2pan for the most recent
+        batch, the wavefronts of that launch list, and the wavefronts it took, summed over its launches so far (read
+        from the device: waits for the stream)"""
+        if self._last_batch_osc2quiet is None:
+            raise RuntimeError(f"this library has no {self.prefix}last_batch_osc2quiet")
+        bi = a2amd_osc2quiet_batch_info()
+        self._chk(self._last_batch_osc2quiet(self.ctx, C.byref(bi)), "last_batch_osc2quiet")
+        return bi
+
+    def osc2quiet_hold(self, hold):
+        """a2amd_osc2quiet_hold: from the next batch on k_leaf_osc2pan alone (hold), or the pair by its rule again"""
+        if self._last_batch_osc2quiet is None:
+            raise RuntimeError(f"this library has no {self.prefix}osc2quiet_hold")
+        self._chk(self._osc2quiet_hold(self.ctx, int(bool(hold))), "osc2quiet_hold")
 
     def osc2_stage_rule(self, size0, periodic0, size1, periodic1):
         """a2amd_osc2_stage_rule: the mask of a settled `wtosc; wtosc; panmix` voice's oscillators whose taps

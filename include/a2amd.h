@@ -467,6 +467,8 @@ int  a2amd_last_batch(const a2amd_ctx *ctx, a2amd_batch_info *bi);
 #include "a2amd_osc2lds.h"
 /* ... and which of them take the interpolation's fused multiply-add steps: a2amd_wave_level_tame(), a2amd_osc2_tame_rule(). */
 #include "a2amd_osc2tame.h"
+/* ... and the kernel that holds the walk of whole wavefronts of them, in front of k_leaf_osc2pan: a2amd_last_batch_osc2quiet(). */
+#include "a2amd_osc2tame_kernel.h"
 /* The quiet kernel of three-oscillator subtractive leads: a2amd_last_batch_osc3filt(). */
 #include "a2amd_osc3filt.h"
 /* What the host has done with the wave pool and its tables - growth, the footprint policy, reuse: a2amd_wave_pool_info(). */
