@@ -661,6 +661,16 @@ class Backend:
         n = self._chk(self._render(self.ctx, phases, ptrs, capacity_frames), "render")
         return out[:, :n]
 
+    def render_kept(self, capacity_frames):
+        """render() with A2AMD_RENDER_KEEP: the batch stays recorded and uploaded, for replay() or another render()"""
+        return self.render(capacity_frames, phases=15 | 16)
+
+    def replay(self, steps):
+        """a2amd_replay: the kept batch `steps` times more, unheard (eight steps to a graph, the rest one by one)"""
+        f = getattr(self.lib, self.prefix + "replay")
+        f.restype, f.argtypes = C.c_int, [C.c_void_p, C.c_uint]
+        return self._chk(f(self.ctx, steps), "replay")
+
     def set_pitch_table(self, tab):
         tab = np.ascontiguousarray(tab, dtype=np.uint32)
         return self._chk(self._set_pt(self.ctx, tab.ctypes.data_as(C.POINTER(C.c_uint32))), "set_pt")

@@ -32,6 +32,12 @@ typedef struct a2amd_osc2quiet_batch_info {
 	                         * read from a device word after waiting for the context's stream, as a2amd_osc2_tame_voices()
 	                         * reads its own (the difference over a batch is the number it took in that batch) */
 } a2amd_osc2quiet_batch_info;
+/* A batch that ran from a captured graph - a quiet batch recorded again, a step of a2amd_replay() - reports launched and
+ * wavefronts as they were when its graph was captured: the capture goes through the same launch code and sets them, a
+ * replay leaves them alone.  They are that batch's own all the same: a graph does not outlive the launch decision it
+ * was captured under (a change of the rule's answer, of the hold, of the class drops it), so a replay runs the pair
+ * exactly when the capture did.  taken_total is a device word and counts the wavefronts taken in replays as in any
+ * other launch.  A batch launched without the pair, directly or into a new graph, reports 0 and 0. */
 int a2amd_last_batch_osc2quiet(struct a2amd_ctx *ctx, a2amd_osc2quiet_batch_info *out);
 
 /* hold != 0: from the next batch on this context launches k_leaf_osc2pan alone, as under bit 19; 0: by the rule above
