@@ -69,7 +69,7 @@ def build_lib(force=False):
     deps = srcs + [os.path.join(csrc, "a2amd_host.h"), os.path.join(csrc, "a2amd_switches.h"), os.path.join(csrc, "a2amd_device.h"), os.path.join(csrc, "a2amd_dsp.h"),
                    os.path.join(csrc, "a2amd_fm.h"), os.path.join(csrc, "a2amd_vmcore.h"), os.path.join(csrc, "a2amd_taps.h"), os.path.join(csrc, "a2amd_winctl.h"), os.path.join(csrc, "a2amd_vmdev.h"), os.path.join(csrc, "a2amd_noisemap.h"), os.path.join(csrc, "a2amd_noisevoice.h"), os.path.join(csrc, "a2amd_settled.h"), os.path.join(csrc, "a2amd_quiet.h"), os.path.join(csrc, "a2amd_cutsweep.h"), os.path.join(csrc, "a2amd_filt.h"), os.path.join(csrc, "a2amd_wavepads.h"), os.path.join(csrc, "a2amd_wavetame.h"), os.path.join(ROOT, "include", "a2amd.h"),
                    os.path.join(ROOT, "include", "a2amd_noise.h"), os.path.join(ROOT, "include", "a2amd_noisepan.h"), os.path.join(ROOT, "include", "a2amd_noisefilt.h"), os.path.join(ROOT, "include", "a2amd_sweep.h"), os.path.join(ROOT, "include", "a2amd_wavepost.h"),
-                   os.path.join(ROOT, "include", "a2amd_bus.h"), os.path.join(ROOT, "include", "a2amd_oscbare.h"), os.path.join(ROOT, "include", "a2amd_osc3filt.h"), os.path.join(ROOT, "include", "a2amd_fbdpan.h"), os.path.join(ROOT, "include", "a2amd_buswin.h"), os.path.join(ROOT, "include", "a2amd_vmbatch.h"), os.path.join(ROOT, "include", "a2amd_osc2.h"), os.path.join(ROOT, "include", "a2amd_osc2lds.h"), os.path.join(ROOT, "include", "a2amd_osc2tame.h"), os.path.join(ROOT, "include", "a2amd_osc2tame_kernel.h"), os.path.join(ROOT, "include", "a2amd_wavepool.h"), os.path.join(ROOT, "include", "a2amd_vm.h")]
+                   os.path.join(ROOT, "include", "a2amd_bus.h"), os.path.join(ROOT, "include", "a2amd_oscbare.h"), os.path.join(ROOT, "include", "a2amd_osc3filt.h"), os.path.join(ROOT, "include", "a2amd_osc3win.h"),os.path.join(ROOT, "include", "a2amd_fbdpan.h"), os.path.join(ROOT, "include", "a2amd_buswin.h"), os.path.join(ROOT, "include", "a2amd_vmbatch.h"), os.path.join(ROOT, "include", "a2amd_osc2.h"), os.path.join(ROOT, "include", "a2amd_osc2lds.h"), os.path.join(ROOT, "include", "a2amd_osc2tame.h"), os.path.join(ROOT, "include", "a2amd_osc2tame_kernel.h"), os.path.join(ROOT, "include", "a2amd_wavepool.h"), os.path.join(ROOT, "include", "a2amd_vm.h")]
     out = os.path.join(HERE, "liba2amd.so")
     flags = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-Wno-unused-value"]
     want = source_hash(deps, flags)
@@ -83,7 +83,7 @@ def build_units(force=False):
     src = os.path.join(HERE, "csrc", "a2amd_units.c")
     deps = [src, os.path.join(ROOT, "include", "a2amd.h"), os.path.join(ROOT, "include", "a2amd_noise.h"), os.path.join(ROOT, "include", "a2amd_noisepan.h"),
             os.path.join(ROOT, "include", "a2amd_noisefilt.h"), os.path.join(ROOT, "include", "a2amd_sweep.h"), os.path.join(ROOT, "include", "a2amd_bus.h"),
-            os.path.join(ROOT, "include", "a2amd_wavepost.h"), os.path.join(ROOT, "include", "a2amd_oscbare.h"), os.path.join(ROOT, "include", "a2amd_osc3filt.h"), os.path.join(ROOT, "include", "a2amd_fbdpan.h"), os.path.join(ROOT, "include", "a2amd_buswin.h"), os.path.join(ROOT, "include", "a2amd_vmbatch.h"), os.path.join(ROOT, "include", "a2amd_osc2.h"), os.path.join(ROOT, "include", "a2amd_osc2lds.h"), os.path.join(ROOT, "include", "a2amd_osc2tame.h"), os.path.join(ROOT, "include", "a2amd_osc2tame_kernel.h"), os.path.join(ROOT, "include", "a2amd_wavepool.h"), os.path.join(ROOT, "include", "a2amd_plugin.h"),
+            os.path.join(ROOT, "include", "a2amd_wavepost.h"), os.path.join(ROOT, "include", "a2amd_oscbare.h"), os.path.join(ROOT, "include", "a2amd_osc3filt.h"), os.path.join(ROOT, "include", "a2amd_osc3win.h"),os.path.join(ROOT, "include", "a2amd_fbdpan.h"), os.path.join(ROOT, "include", "a2amd_buswin.h"), os.path.join(ROOT, "include", "a2amd_vmbatch.h"), os.path.join(ROOT, "include", "a2amd_osc2.h"), os.path.join(ROOT, "include", "a2amd_osc2lds.h"), os.path.join(ROOT, "include", "a2amd_osc2tame.h"), os.path.join(ROOT, "include", "a2amd_osc2tame_kernel.h"), os.path.join(ROOT, "include", "a2amd_wavepool.h"), os.path.join(ROOT, "include", "a2amd_plugin.h"),
             os.path.join(ROOT, "include", "a2amd_walk.h"), os.path.join(ROOT, "include", "a2amd_vm.h")]
     out = os.path.join(HERE, "liba2amd_units.so")
     flags = ["-O2", "-Wall", "-fPIC", "-shared"]

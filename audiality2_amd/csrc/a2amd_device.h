@@ -440,6 +440,9 @@ int a2d_launch_leaf_oscbare(const A2DParams *dparams, const A2DParams &hp, const
 // a2amd_osc3filtpan.hip: k_leaf_osc3filtpan, the quiet kernel of 3 x wtosc -> filter12 -> panmix voices: the voices of the list
 // without a run this batch, gliding or not; a workgroup per 'vpg' (at most 64) voices, its filter wavefront lane = voice
 int a2d_launch_leaf_osc3filtpan(const A2DParams *dparams, const A2DParams &hp, const int *dlist, int nlist, int vpg, void *stream);
+// ... and k_leaf_osc3filtpan_win, its windows launch: the voices of the list WITH a run - windows only and a tiling, the host
+// has checked both (seg_rows) - every ramper stepped window by window; the same workgroup
+int a2d_launch_leaf_osc3filtpan_win(const A2DParams *dparams, const A2DParams &hp, const int *dlist, int nlist, int vpg, void *stream);
 
 // a2amd_vm.hip: the count pass (emit = 0) or the emit pass of the VM kernel
 int a2d_launch_vm(const A2DVmParams &vp, int emit, void *stream);

@@ -232,13 +232,15 @@ enum { CLS_GENERIC = 0, CLS_OSCPAN, CLS_OSCFILTPAN, CLS_BUSDRIVER, CLS_BUSGENERI
 // The quiet kernels skip a voice whose runs[] entry is non-zero; those voices are this batch's exceptions, shipped in the
 // blob (d_dyn), laid out the same way:
 //   [ wtosc-panmix | 2 x wtosc-panmix | wtosc-filter12-panmix | 2 x wtosc-filter12-panmix | the general kernel's |
-//     per depth: bus owners with records ]
+//     3 x wtosc-filter12-panmix with windows only | per depth: bus owners with records ]
 // a2amd_ctx::dyn[DYN_*] (the first four: the records / window kernels' lists) and depth_ranges[d].dyn are OFFSETS into
 // d_dyn, which moves when the blob grows (a2amd_vm.cpp).
 struct ListRange { int first = 0, count = 0; };
 enum { LEAF_OSCPAN = 0, LEAF_OSC2PAN, LEAF_OSCFILTPAN, LEAF_FMPAN, LEAF_GENERIC, LEAF_OSC2FILTPAN, LEAF_NOISEPAN, LEAF_NOISEFILTPAN,
 	LEAF_OSCBARE, LEAF_OSC3FILTPAN, LEAF_N };	// (a new segment goes last: the others' offsets in d_list stay)
-enum { DYN_OSC1 = 0, DYN_OSC2, DYN_FILT, DYN_FILT2, DYN_REST, DYN_N };
+// (DYN_OSC3WIN: this batch's 3 x wtosc-filter12-panmix voices whose run is windows only and tiles its fragments - they keep
+// the run, stand on no other exception list, and are k_leaf_osc3filtpan's windows launch; include/a2amd_osc3win.h)
+enum { DYN_OSC1 = 0, DYN_OSC2, DYN_FILT, DYN_FILT2, DYN_REST, DYN_OSC3WIN, DYN_N };
 // (ramp: in d_dyn, this batch's driver chains without records whose volume or pan may still glide - k_bus_driver's
 // second launch of the depth, one workgroup a voice)
 // (fbdpan: the delay chains that end in a wired panmix, k_bus_fbdpan's - filled in upload(), read in launch_depth())
@@ -259,7 +261,8 @@ static const struct { int8_t leaf, dyn; } cls_lists[CLS_N] = {
 	// inline; fbdelay x 1..4; panmix wired and adding: a bus owner, on its depth's list for k_bus_fbdpan
 	{ -1, -1 },
 	// 3 x wtosc-filter12-panmix: a segment of its own for k_leaf_osc3filtpan, which takes its voices without a run, gliding or
-	// not; with a run it is the general kernel's, as it was before the class had a kernel
+	// not; with a run it is the general kernel's, as it was before the class had a kernel - but for a run of windows only
+	// that tiles the fragments: DYN_OSC3WIN, upload() decides
 	{ LEAF_OSC3FILTPAN, DYN_REST } };
 // wtosc (noise)-filter12-panmix voices without a record in a batch from which k_leaf_noisefiltpan takes them (A2Switches::nzf_min,
 // A2AMD_NZF_MIN, 64): a launch lasts as long as its filter wavefront's chain through the batch however few of its lanes are
@@ -544,6 +547,9 @@ struct a2amd_ctx {
 	// 3 x wtosc-filter12-panmix voices (CLS_OSC3FILTPAN): likewise, the segment's voices by who renders them this batch
 	uint32_t n_o3f_quiet = 0, n_o3f_gliding = 0, n_o3f_records = 0;
 	a2amd_osc3filt_batch_info last_osc3filt = {};	// a2amd_last_batch_osc3filt()
+	// ... and those whose windows-only run goes to the windows launch (dyn[DYN_OSC3WIN]): upload() resets and counts,
+	// launch_leaves() fills in the launch
+	a2amd_osc3filt_windows_info last_osc3win = {};	// a2amd_last_batch_osc3filt_windows()
 	bool osc2quiet_hold = false;	// a2amd_osc2quiet_hold(): k_leaf_osc2tame is not launched
 	a2amd_osc2quiet_batch_info last_osc2quiet = {};	// a2amd_last_batch_osc2quiet(): k_leaf_osc2tame's launch; taken_total is read when asked for
 	a2amd_osc2_batch_info last_osc2 = {};	// a2amd_last_batch_osc2(): the launch; the walks are counted when asked for

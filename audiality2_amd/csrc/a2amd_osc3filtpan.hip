@@ -293,3 +293,378 @@ int a2d_launch_leaf_osc3filtpan(const A2DParams *dparams, const A2DParams &hp, c
 			hp.ustate, hp.waves, hp.ptab, hp.wavecoef, hp.nfrags, hp.busmem);
 	return hipGetLastError() != hipSuccess;
 }
+
+// ---------------------------------------------------------------------------
+// k_leaf_osc3filtpan_win: the windows launch.  The same voices in the batches in which their only records are R_SEG windows
+// that tile the fragments (a parent's VM woke inside a fragment: include/a2amd_osc3win.h) - every ramper stepped window by
+// window, as the reference's Process(offset, frames) calls would.  Workgroup, tiles, stages and helpers are
+// k_leaf_osc3filtpan's; what differs:
+//   The voices.  Those of its list that HAVE a run (runs[slot].count != 0): the host lists a voice here only where
+//             seg_rows() (a2amd_sched.cpp) has found the run windows only and a tiling, and on no other list.
+//   The windows.  Read in place: lane = voice keeps a cursor into its run per stage, and a fragment's windows are a mask over
+//             its frames - bit a: a window starts at frame a; it ends where the next one starts, or at the fragment's end (the
+//             tiling).  A fragment without a record is the default window (0, n): bit 0.  No table, so no cap on the windows of
+//             a voice.  Every wavefront reads the same words and comes to the same windows.
+//   K/A(f)    over the window index k, up to the most windows a voice of the wavefront has in the fragment (wave-uniform: a
+//             ballot): lane = voice, osc_window_v() on the three oscillators of the voices that have a k-th window (a, m);
+//             lane = frame, for each such voice lanes a <= lane < a + m render frame lane - a of that window's words.  The
+//             row ends up holding the whole fragment; lanes beyond n hold 0.
+//   B(f - 1)  the q ramper prepared and run once per window.  Lanes have different windows: the wavefront walks the segments
+//             between the union of its voices' cut frames, filt_row over each (d1 / d2 and the running q carry across), and a
+//             lane re-prepares q where one of its own windows starts.  Where every voice's q is at rest - timer == 0 - the
+//             fragment is filtered whole, as in k_leaf_osc3filtpan: a2_PrepareRamper without a timer (a2_dsp.h:130-134) sets
+//             value = target and delta = 0 whatever 'frames' is and leaves the timer 0, and a2_RunRamper (:152-155) then adds
+//             0 - the same q in every frame and the same words left, however the fragment is cut.
+//   C(f - 2)  over k likewise: panmix_process12's head per window, the clamp flag chosen per window in front of the prepare
+//             (as k_bus_fbdpan_win does); a lane's frame takes the gains, or value + delta * (lane - a), of the window it
+//             lies in.  A pass over k has bus runs of its own (the sums are wrapping adds: their order is free).
+// D and the state stores are k_leaf_osc3filtpan's: either kernel of the class, or k_voices, takes the voice up next batch.
+// A listed voice that failed 'ok' would be rendered by nobody, so the host must list none.  What excludes each case there
+// (upload(), a2amd_sched.cpp):
+//   - five units, a bus of two channels or more: only voices classified CLS_OSC3FILTPAN (is_osc3filtpan_chain(), the classes
+//     fresh where the list is made) are listed;
+//   - an oscillator neither on a mip-mapped wave nor off: noise is not of the class, a 'w' write to noise is a record (the run
+//     is then not windows only) and afterwards every window carries its R_NOISESEED record or, in a device-seeded stretch,
+//     the voice is marked (noise_run) and not listed; any other wave kind played in the batch sets mode_mix: not listed;
+//   - a coefficient ramp pending: a filter12 cutoff ramp leaves R_F1SET / R_F1RAMP records in every window it spans - such a
+//     run is not windows only - the filter step that ends a ramp clears the flag, and a voice with a filter in the batch's
+//     sweep table is marked (cut_run) and not listed.
+// ---------------------------------------------------------------------------
+
+// One fragment's windows of a voice, lane = voice: the records of fragment f at the run's cursor (cur .. end) as a mask of
+// the frames at which a window starts, below n; bit 0 is always set (a fragment without a record: the default window).
+// The cursor passes every record up to fragment f: it never stalls, whatever the run holds.
+DEV unsigned long long o3w_cuts(const A2DRec *__restrict__ recs, int &cur, int end, int f, int n)
+{
+	unsigned long long m = 1ull;
+	while(cur < end) {
+		const unsigned head = recs[cur].head;
+		if((int)A2D_RFRAG(head) > f)
+			break;
+		if((int)A2D_RFRAG(head) == f)
+			m |= 1ull << (recs[cur].dur & 63u);
+		++cur;
+	}
+	return n >= 64 ? m : m & ((1ull << n) - 1ull);
+}
+
+// the next window of a mask of window starts (not empty): its first frame, and - taken off the mask - its frames
+DEV void o3w_next(unsigned long long &rem, int n, int &a, int &m)
+{
+	a = (int)__builtin_ctzll(rem);
+	rem &= rem - 1;
+	m = (rem ? (int)__builtin_ctzll(rem) : n) - a;
+}
+
+__global__ __launch_bounds__(64 * QUIET_WAVES)
+void k_leaf_osc3filtpan_win(const A2DParams *__restrict__ pp, const int *__restrict__ list, int nlist, int vpg,
+		const A2DVoice *__restrict__ voices, const A2DRun *__restrict__ runs, const A2DRec *__restrict__ recs, int *ustate,
+		const A2DWave *__restrict__ waves, const uint32_t *__restrict__ ptab, const int *__restrict__ wavecoef,
+		int nfrags, int *__restrict__ busmem)
+{
+	extern __shared__ __attribute__((aligned(16))) int o3_tiles[];	// 3 x [vpg][QUIET_PITCH]
+	__shared__ PTab s_ptab;
+	__shared__ QuietBus o3_acc;
+	for(int k = (int)threadIdx.x; k < 128; k += 64 * QUIET_WAVES)
+		s_ptab[k] = ptab[k];
+	quiet_bus_clear(o3_acc, (int)threadIdx.x, 64 * QUIET_WAVES);
+	__syncthreads();
+	const int wv = rfl((int)(threadIdx.x >> 6));
+	const int lane = threadIdx.x & 63;
+	const int first = (int)blockIdx.x * vpg;
+	const int nv = min(vpg, nlist - first);
+	if(nv <= 0)
+		return;		// (the whole workgroup: the grid has none such)
+	const int tsize = vpg * QUIET_PITCH;
+
+	// lane v: voice v of this workgroup, in every wavefront
+	int uo0 = 0, uo1 = 0, uo2 = 0, uf = 0, up = 0, my_off = -1, my_nch = 2;
+	int lp_l = 0, bp_l = 0, hp_l = 0;
+	int rfirst = 0, rend = 0;	// the voice's run
+	bool ok = false;
+	if(lane < nv) {
+		const int slot = list[first + lane];
+		const A2DRun run = runs[slot];
+		if(run.count != 0) {
+			const A2DVoice &vc = voices[slot];
+			uo0 = vc.unit[0]; uo1 = vc.unit[1]; uo2 = vc.unit[2];
+			uf = vc.unit[3];
+			up = vc.unit[4];
+			my_off = vc.out_off;
+			my_nch = vc.out_nch;
+			const int m0 = ustate[(size_t)uo0 * A2D_USTATE + OW_MODE], m1 = ustate[(size_t)uo1 * A2D_USTATE + OW_MODE],
+					m2 = ustate[(size_t)uo2 * A2D_USTATE + OW_MODE];
+			const int *wf = ustate + (size_t)uf * A2D_USTATE;
+			lp_l = wf[FW_LP]; bp_l = wf[FW_BP]; hp_l = wf[FW_HP];
+			ok = vc.nunits == 5 && my_off >= 0 && my_nch >= 2 && !wf[FW_RAMP] &&
+					(m0 == A2D_OSC_MIPWAVE || m0 == A2D_OSC_OFF) && (m1 == A2D_OSC_MIPWAVE || m1 == A2D_OSC_OFF) &&
+					(m2 == A2D_OSC_MIPWAVE || m2 == A2D_OSC_OFF);
+			if(ok) {
+				rfirst = run.first;
+				rend = run.first + run.count;
+			}
+		}
+	}
+	const QuietWg wg = quiet_wg(ok, bp_l, hp_l, my_off, my_nch);
+	if(!wg.todo)
+		return;		// (the whole workgroup)
+	const bool lpraw = wg.lpraw, wgbus = wg.wgbus;
+	const int nsteps = nfrags + 3;
+
+	if(wv == 0) {
+		// ================= the filter wavefront: lane = voice =================
+		Ramp q = { 0, 0, 0, 0 };
+		int ff_l = 0, d1_l = 0, d2_l = 0;
+		if(ok) {
+			const int *wf = ustate + (size_t)uf * A2D_USTATE;
+			q = ramp_load(wf + FW_Q);
+			ff_l = wf[FW_F1] >> 12;		// f12_process's f, filter12.c:99 (no coefficient ramp: df = 0)
+			d1_l = wf[FW_D1A];
+			d2_l = wf[FW_D2A];
+		}
+		int cur = rfirst;
+		__builtin_amdgcn_s_setprio(3);
+		for(int st = 0; st < nsteps; ++st) {
+			const int f = st - 1;
+			if(f >= 0 && f < nfrags) {
+				const int n = min((int)pp->fragframes[f], A2D_FRAG);
+				const unsigned long long cuts = o3w_cuts(recs, cur, rend, f, n);
+				if(n > 0) {
+					const unsigned long long mycuts = ok ? cuts : 0ull;
+					// (q at rest in the whole wavefront: a window changes nothing - the header comment - and the fragment is one
+					// segment, one window)
+					const bool allrest = __all(!ok || q.timer == 0);
+					unsigned long long u = 1ull;	// the union of the voices' window starts
+					if(!allrest)
+						for(;;) {
+							const unsigned long long more = __ballot((mycuts & ~u) != 0);
+							if(!more)
+								break;
+							const int v = (int)__builtin_ctzll(more);
+							u |= (unsigned long long)(unsigned)rdl((int)(unsigned)mycuts, v) |
+									((unsigned long long)(unsigned)rdl((int)(unsigned)(mycuts >> 32), v) << 32);
+						}
+					int *row = o3_tiles + (f % 3) * tsize + lane * QUIET_PITCH;
+					int qv = q.value, qd = 0;
+					while(u) {
+						int s0, len;
+						o3w_next(u, n, s0, len);
+						// f12_process's head, filter12.c:86-96, where a window of this voice starts
+						if(ok && (allrest || ((mycuts >> s0) & 1ull))) {
+							unsigned long long own = allrest ? 1ull : mycuts >> s0;
+							int a, m;
+							o3w_next(own, n - s0, a, m);
+							ramp_prepare_v(q, m);
+							qv = q.value;
+							qd = q.delta;
+							ramp_run(q, m);
+						}
+						const bool qrest = __all(!ok || qd == 0);
+						if(ok) {
+							if(qrest) {
+								if(lpraw)
+									filt_row<true, true>(row + s0, len, ff_l, lp_l, bp_l, hp_l, d1_l, d2_l, qv, 0);
+								else
+									filt_row<false, true>(row + s0, len, ff_l, lp_l, bp_l, hp_l, d1_l, d2_l, qv, 0);
+							} else {
+								if(lpraw)
+									filt_row<true, false>(row + s0, len, ff_l, lp_l, bp_l, hp_l, d1_l, d2_l, qv, qd);
+								else
+									filt_row<false, false>(row + s0, len, ff_l, lp_l, bp_l, hp_l, d1_l, d2_l, qv, qd);
+							}
+						}
+					}
+				}
+			}
+			filt_barrier();
+		}
+		// state out: the filter's words as f12_process / ctl_store leave them
+		if(ok) {
+			int *wf = ustate + (size_t)uf * A2D_USTATE;
+			ramp_store(wf + FW_Q, q);
+			wf[FW_D1A] = d1_l;
+			wf[FW_D2A] = d2_l;
+		}
+		return;
+	}
+
+	// ================= workers: a range of the workgroup's voices each =================
+	const unsigned long long mine = quiet_worker_voices(wv, nv, wg.todo);	// (wavefront 4: none)
+	const bool mylane = (mine >> lane) & 1ull;
+
+	// lane v, my voices only: the three oscillators as ctl_load loads them, the panmix's rampers
+	OscV o0, o1, o2;
+	oscv_clear(o0);
+	oscv_clear(o1);
+	oscv_clear(o2);
+	Ramp vol = { 0, 0, 0, 0 }, pan = { 0, 0, 0, 0 };
+	if(mylane) {
+		oscv_load(o0, ustate + (size_t)uo0 * A2D_USTATE);
+		oscv_load(o1, ustate + (size_t)uo1 * A2D_USTATE);
+		oscv_load(o2, ustate + (size_t)uo2 * A2D_USTATE);
+		const int *wp = ustate + (size_t)up * A2D_USTATE;
+		vol = ramp_load(wp + PW_VOL);
+		pan = ramp_load(wp + PW_PAN);
+	}
+	const CoefRsrc rs = coef_rsrc(wavecoef);
+	int curA = rfirst, curC = rfirst;	// the run's cursor of either stage
+
+	const QuietOut out = { busmem, &o3_acc, wgbus, lane };
+
+	for(int st = 0; st < nsteps; ++st) {
+		// ---- D(st - 3): the workgroup's sum of a fragment, complete since the last barrier ----
+		if(wv == 4 && wgbus && st >= 3) {
+			const int f = st - 3;
+			if((int)pp->fragframes[f] > 0)
+				quiet_bus_flush(o3_acc, busmem, wg.wg_off, f, lane);
+		}
+		// ---- K/A(st) ----
+		if(st < nfrags && mine) {
+			const int f = st;
+			const int n = min((int)pp->fragframes[f], A2D_FRAG);
+			const unsigned long long cuts = o3w_cuts(recs, curA, rend, f, n);
+			if(n > 0) {
+				unsigned long long rem = mylane ? cuts : 0ull;
+				int *tile = o3_tiles + (f % 3) * tsize;
+				for(int k = 0;; ++k) {
+					// control, lane = voice: the k-th window of the voices that have one - its words of each oscillator
+					int w0[6] = { 0, 0, 0, 0, 0, 0 }, w1[6] = { 0, 0, 0, 0, 0, 0 }, w2[6] = { 0, 0, 0, 0, 0, 0 };
+					int md0 = WM_SILENT, md1 = WM_SILENT, md2 = WM_SILENT, a_l = 0, m_l = 1;
+					const bool has = rem != 0;
+					if(has) {
+						o3w_next(rem, n, a_l, m_l);
+						md0 = osc_window_v(waves, s_ptab, o0, m_l, w0);
+						md1 = osc_window_v(waves, s_ptab, o1, m_l, w1);
+						md2 = osc_window_v(waves, s_ptab, o2, m_l, w2);
+					}
+					unsigned long long m = __ballot(has);
+					if(!m)
+						break;
+					const unsigned long long t0 = __ballot(md0 == WM_TAPS), t1 = __ballot(md1 == WM_TAPS), t2 = __ballot(md2 == WM_TAPS);
+					// render, lane = frame: frame lane - a of the window (lanes outside it: its nearest frame's address, not stored)
+					auto issue = [&](int v, OscTaps &A, OscTaps &B, OscTaps &C, unsigned &fl, bool &in) __attribute__((always_inline)) {
+						const int a = rdl(a_l, v), mm = rdl(m_l, v);
+						fl = (unsigned)min(max(lane - a, 0), mm - 1);
+						in = lane >= a && lane < a + mm;
+						if((t0 >> v) & 1ull) osctaps_issue(w0, v, rs, fl, A); else osctaps_clear(A);
+						if((t1 >> v) & 1ull) osctaps_issue(w1, v, rs, fl, B); else osctaps_clear(B);
+						if((t2 >> v) & 1ull) osctaps_issue(w2, v, rs, fl, C); else osctaps_clear(C);
+					};
+					// (the fragment's first pass: every voice has a window, and the lanes beyond the fragment store their 0)
+					const bool beyond = k == 0 && lane >= n;
+					int v = (int)__builtin_ctzll(m);
+					m &= m - 1;
+					OscTaps A0, B0, C0;
+					unsigned fl0;
+					bool in0;
+					issue(v, A0, B0, C0, fl0, in0);
+					for(;;) {
+						const int vn = m ? (int)__builtin_ctzll(m) : -1;
+						OscTaps A1, B1, C1;
+						unsigned fl1 = 0;
+						bool in1 = false;
+						if(vn >= 0)
+							issue(vn, A1, B1, C1, fl1, in1);
+						// wtosc_do_fragment replacing, then twice adding (A2_PROCADD: wrapping)
+						const int x = wadd(wadd(osctaps_finish(A0, fl0), osctaps_finish(B0, fl0)), osctaps_finish(C0, fl0));
+						if(in0 || beyond)
+							tile[v * QUIET_PITCH + lane] = in0 ? x >> 5 : 0;
+						if(vn < 0)
+							break;
+						m &= m - 1;
+						v = vn;
+						A0 = A1; B0 = B1; C0 = C1;
+						fl0 = fl1; in0 = in1;
+					}
+				}
+			}
+		}
+		// ---- C(st - 2) ----
+		if(st >= 2 && st - 2 < nfrags && mine) {
+			const int f = st - 2;
+			const int n = min((int)pp->fragframes[f], A2D_FRAG);
+			const unsigned long long cuts = o3w_cuts(recs, curC, rend, f, n);
+			if(n > 0) {
+				unsigned long long rem = mylane ? cuts : 0ull;
+				const int *tile = o3_tiles + (f % 3) * tsize;
+				for(;;) {
+					// control, lane = voice: panmix_process12's head, panmix.c:84-95, for the voice's next window (the clamp
+					// variant chosen in front of a2_PrepareRamper), the rampers stepped over it
+					int pv = 0, pdv = 0, ppn = 0, pdp = 0, g0 = 0, g1 = 0, a_l = 0, m_l = 0;
+					bool pcl = false;
+					const bool has = rem != 0;
+					if(has) {
+						o3w_next(rem, n, a_l, m_l);
+						pcl = a2s_pan_over(pan.target) || a2s_pan_over(pan.value);
+						ramp_prepare_v(vol, m_l);
+						ramp_prepare_v(pan, m_l);
+						pv = vol.value; pdv = vol.delta;
+						ppn = pan.value; pdp = pan.delta;
+						// (volume and pan at rest: the window's two gains)
+						a2s_pan_gains(pv, ppn, pcl, &g0, &g1);
+						ramp_run(vol, m_l);
+						ramp_run(pan, m_l);
+					}
+					const unsigned long long mk = __ballot(has);
+					if(!mk)
+						break;
+					const unsigned long long mramp = __ballot((pdv | pdp) != 0), mclamp = __ballot(pcl);
+					// lane = frame: the voices whose window holds this frame
+					BusRun run = busrun_begin();
+					for(unsigned long long m = mk; m; m &= m - 1) {
+						const int v = (int)__builtin_ctzll(m);
+						busrun_voice(run, out, f, my_off, my_nch, v);
+						const int wk = lane - rdl(a_l, v);
+						const bool in = wk >= 0 && wk < rdl(m_l, v);
+						int y = tile[v * QUIET_PITCH + lane];
+						if(lpraw)
+							y = wmul(y, rdl(lp_l, v)) >> 3;	// (filt_step: the row holds l)
+						int v0 = rdl(g0, v), v1 = rdl(g1, v);
+						if((mramp >> v) & 1ull) {
+							// win_pan's arithmetic for a window in which volume or pan moves
+							const int vk = wadd(rdl(pv, v), wmul(rdl(pdv, v), wk));
+							const int pk = wadd(rdl(ppn, v), wmul(rdl(pdp, v), wk));
+							const int vp = mul64s(pk, vk, 24);
+							v0 = wsub(vk, vp);
+							v1 = wadd(vk, vp);
+							if((mclamp >> v) & 1ull) {
+								const int lim = wshl(vk, 1);
+								if(v0 > lim) v0 = lim;
+								if(v1 > lim) v1 = lim;
+							}
+						}
+						if(in) {
+							run.acc0 = wadd(run.acc0, mul64s(y, v0, 24));
+							run.acc1 = wadd(run.acc1, mul64s(y, v1, 24));
+						}
+					}
+					busrun_end(run, out, f);
+				}
+			}
+		}
+		filt_barrier();
+	}
+
+	// state out: ctl_store's words of the oscillators and the panmix
+	if(mylane) {
+		oscv_store(ustate + (size_t)uo0 * A2D_USTATE, o0);
+		oscv_store(ustate + (size_t)uo1 * A2D_USTATE, o1);
+		oscv_store(ustate + (size_t)uo2 * A2D_USTATE, o2);
+		int *wp = ustate + (size_t)up * A2D_USTATE;
+		ramp_store(wp + PW_VOL, vol);
+		ramp_store(wp + PW_PAN, pan);
+	}
+}
+
+// the windows launch: the same shape
+int a2d_launch_leaf_osc3filtpan_win(const A2DParams *dparams, const A2DParams &hp, const int *dlist, int nlist, int vpg, void *stream)
+{
+	if(nlist <= 0)
+		return 0;
+	vpg = vpg < 1 ? 1 : vpg > QUIET_MAXV ? QUIET_MAXV : vpg;
+	const dim3 grid((nlist + vpg - 1) / vpg), block(64 * QUIET_WAVES);
+	const size_t dyn = (size_t)3 * vpg * QUIET_PITCH * sizeof(int);
+	hipLaunchKernelGGL(k_leaf_osc3filtpan_win, grid, block, dyn, (hipStream_t)stream, dparams, dlist, nlist, vpg, hp.voices, hp.runs,
+			hp.recs, hp.ustate, hp.waves, hp.ptab, hp.wavecoef, hp.nfrags, hp.busmem);
+	return hipGetLastError() != hipSuccess;
+}

@@ -508,6 +508,14 @@ int a2amd_last_batch_osc3filt(const a2amd_ctx *c, a2amd_osc3filt_batch_info *out
 	return A2AMD_OK;
 }
 
+int a2amd_last_batch_osc3filt_windows(const a2amd_ctx *c, a2amd_osc3filt_windows_info *out)
+{
+	if(!c || !out)
+		return A2AMD_EINVAL;
+	*out = c->last_osc3win;
+	return A2AMD_OK;
+}
+
 int a2amd_last_batch_osc2(const a2amd_ctx *c, a2amd_osc2_batch_info *out)
 {
 	if(!c || !out)

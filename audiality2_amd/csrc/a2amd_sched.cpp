@@ -457,6 +457,8 @@ int upload(a2amd_ctx *c)
 	// (a2amd_last_batch_bus_windows(): a quiet batch has no record, so no windows)
 	c->last_buswin = a2amd_bus_windows_info{};
 	c->last_buswin.window_cap = FBW_MAXWIN;
+	// (a2amd_last_batch_osc3filt_windows(): likewise)
+	c->last_osc3win = a2amd_osc3filt_windows_info{};
 	if(c->sw.hosttiming) {
 		// (A2AMD_HOSTTIMING: why a batch did not take the quiet path - first reason that applies)
 		const int why = !c->blob_quiet ? 0 : !c->with_recs.empty() ? 1 : !c->prev_with_recs.empty() ? 2 :
@@ -993,6 +995,26 @@ int upload(a2amd_ctx *c)
 				// kernel's, which renders the voices on its exception list; k_leaf_oscbare skips a voice that has a run.
 				// 3 x wtosc-filter12-panmix likewise: records of its own, the stand-in of a cutoff in the batch's sweep table or of
 				// a noise oscillator - k_leaf_osc3filtpan skips it)
+				// But for a lead whose run is windows only and tiles its fragments (seg_rows(); the classes are fresh here): it
+				// keeps the run and its class - k_leaf_osc3filtpan's windows launch steps every ramper window by window
+				// (include/a2amd_osc3win.h).  It stands on no other list: the whole-fragment launch skips it for its run, the
+				// general kernel never sees it.  What the kernel's own test of the voice relies on (a2amd_osc3filtpan.hip):
+				// mode_mix - no oscillator off the mip-mapped waves in this batch; a filter with a column of the batch's sweep
+				// table or a noise oscillator in a device-seeded stretch (cut_run / noise_run, marked above) is the general
+				// kernel's as before; a cutoff ramp leaves R_F1* records, so such a run is not windows only.
+				if(v.cls == CLS_OSC3FILTPAN && !(c->sw.no_fast & 2048) && v.vm < 0 && v.resolved && !v.mode_mix &&
+						v.cut_run != c->serial_base && v.noise_run != c->serial_base) {
+					const int rows = seg_rows(v.recs.data(), v.recs.size(), c->fragframes, c->nfrags);
+					a2amd_osc3filt_windows_info &ow = c->last_osc3win;
+					if(rows > 0) {
+						dyn[DYN_OSC3WIN].push_back(vi);
+						++ow.window_voices;
+						ow.gliding_voices += v.moving_until > c->vm.batch_time;
+						ow.windows += (uint32_t)rows;
+						continue;
+					}
+					ow.refused_tiling += rows < 0;
+				}
 				dyn[DYN_REST].push_back(vi);
 			} else if((v.cls == CLS_BUSDRIVER || v.cls == CLS_FBDCHAIN || v.cls == CLS_FBDPAN) && v.depth < (int)dyn_bus.size()) {
 				// A pan-tailed delay chain whose run is windows only and tiles its fragments (seg_rows(); the classes are fresh
@@ -1913,6 +1935,18 @@ static int launch_leaves(a2amd_ctx *c, LeafPass &lp)
 		c->last_osc3filt.launched = 1;
 		c->last_osc3filt.vpg = (uint32_t)vpg;
 		c->last_osc3filt.workgroups = (uint32_t)((o3f.count + vpg - 1) / vpg);
+	}
+	// ... and those of the class whose run is windows only (upload(): dyn[DYN_OSC3WIN]): the windows launch, the same
+	// workgroup and the same rule for its size, over this batch's list of them
+	const ListRange o3w = c->dyn[DYN_OSC3WIN];
+	if(o3w.count) {
+		const int vpg = std::min(std::max(c->sw.f2vpw ? c->sw.f2vpw : (o3w.count + 255) / 256, 1), 64);
+		if(a2d_launch_leaf_osc3filtpan_win(c->d_params, c->hparams, c->d_dyn + o3w.first, o3w.count, vpg, c->stream))
+			return c->fail(A2AMD_EHIP, "3-osc filter leaf windows launch failed: %s", hipGetErrorString(hipGetLastError()));
+		++c->stats.launches;
+		c->last_osc3win.launched = 1;
+		c->last_osc3win.vpg = (uint32_t)vpg;
+		c->last_osc3win.workgroups = (uint32_t)((o3w.count + vpg - 1) / vpg);
 	}
 	const ListRange osc2pan = c->leaf[LEAF_OSC2PAN];
 	if(osc2pan.count && none_quiet(1, osc2pan.count))

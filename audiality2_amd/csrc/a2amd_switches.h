@@ -23,13 +23,13 @@ static inline int within(const char *name, int lo, int hi) { const int v = num(n
 	X(int, dbg_walk, a2sw::num("A2AMD_DBG_WALK", 0))	/* 0. Bits: 1 a2amd_voice_process() never takes its short path, 2 ... never reports the default window (debugging the walk) */ \
 	X(int, debug, a2sw::num("A2AMD_DEBUG", 0))		/* 0. A2DParams::debug, ablations: 1 no bus atomics (breaks the audio on purpose), 4 no shadow lanes in the FM kernel, 8 k_leaf_oscfiltpan's wavefronts add to the bus themselves, not through the workgroup's LDS sums, 16 k_leaf_osc2pan walks no super-chunk voice by voice (a launch argument; include/a2amd_osc2.h), 1 << 17 that walk stages no mip level in LDS (a launch argument; include/a2amd_osc2lds.h), 1 << 18 that walk takes the fused multiply-add steps for no voice (a launch argument; include/a2amd_osc2tame.h), 1 << 19 k_leaf_osc2tame is never launched in front of k_leaf_osc2pan, 1 << 20 it is whatever the class's size (the host's launch rule; include/a2amd_osc2tame_kernel.h) */ \
 	X(bool, debug_noise, a2sw::set("A2AMD_DEBUG_NOISE"))	/* unset. Set: trace the noise oscillators' seeds (debugging aid) */ \
-	X(int, f2vpw, a2sw::num("A2AMD_F2VPW", 0))		/* 0 = the launcher's own choice: voices per workgroup of k_leaf_osc2filtpan; and, clamped to 1..64, of k_leaf_osc3filtpan (0: by count) */ \
+	X(int, f2vpw, a2sw::num("A2AMD_F2VPW", 0))		/* 0 = the launcher's own choice: voices per workgroup of k_leaf_osc2filtpan; and, clamped to 1..64, of k_leaf_osc3filtpan and its windows launch (0: by count) */ \
 	X(bool, fmvpw_set, a2sw::set("A2AMD_FMVPW")) X(int, fmvpw, a2sw::num("A2AMD_FMVPW", 0))	/* unset = by count: voices per wavefront of k_leaf_fmpan. Set: no one-launch FM path */ \
 	X(bool, fvpw_set, a2sw::set("A2AMD_FVPW")) X(int, fvpw, a2sw::num("A2AMD_FVPW", 0))	/* unset = by count: voices per wavefront of k_leaf_oscfiltpan */ \
 	X(bool, hosttiming, a2sw::set("A2AMD_HOSTTIMING")) X(int, hosttiming_level, a2sw::num("A2AMD_HOSTTIMING", 0))	/* unset: host timing counters and their dump at exit; the level (2, 3) adds per-batch traces */ \
 	X(bool, noise_quiet, a2sw::on("A2AMD_NOISE_QUIET"))	/* on. 0: no launch classes for wtosc (noise)-[filter12-]panmix voices - they are wtosc-[filter12-]panmix voices, and every noise voice of a device-seeded batch gets the stand-in record (A/B) */ \
 	X(bool, no_direct, a2sw::set("A2AMD_NO_DIRECT"))	/* unset. Set: the root never stores the master bus straight into the host's buffer */ \
-	X(int, no_fast, a2sw::num("A2AMD_NO_FAST", 0))		/* 0. Bit mask of classes sent to the general kernel: 1 wtosc-panmix, 2 wtosc-filter12-panmix, 4 driver chains, 8 2 x wtosc-panmix, 16 fm-panmix, 32 fbdelay chains, 64 no records kernel, 128 2 x wtosc-filter12-panmix, 256 bare wtosc, 512 pan-tailed fbdelay chains (debugging / A-B tests) */ \
+	X(int, no_fast, a2sw::num("A2AMD_NO_FAST", 0))		/* 0. Bit mask of classes sent to the general kernel: 1 wtosc-panmix, 2 wtosc-filter12-panmix, 4 driver chains, 8 2 x wtosc-panmix, 16 fm-panmix, 32 fbdelay chains, 64 no records kernel, 128 2 x wtosc-filter12-panmix, 256 bare wtosc, 512 pan-tailed fbdelay chains, 1024 3 x wtosc-filter12-panmix, 2048 no windows launch for that class - a voice of it whose run is windows only goes to the general kernel, as any other run of it does (include/a2amd_osc3win.h) (debugging / A-B tests) */ \
 	X(bool, no_graph, a2sw::set("A2AMD_NO_GRAPH"))		/* unset. Set: no batch is captured into or replayed from a graph */ \
 	X(bool, no_moving, a2sw::set("A2AMD_NO_MOVING"))	/* unset. Set: gliding voices get no stand-in record (they stay the quiet kernels') */ \
 	X(bool, no_selfclean, a2sw::set("A2AMD_NO_SELFCLEAN"))	/* unset. Set: bus owners never count as clearing their own buses */ \

@@ -135,6 +135,16 @@ class a2amd_osc3filt_batch_info(C.Structure):
         return "osc3filt_batch_info(" + ", ".join(f"{n}={getattr(self, n)}" for n, _ in self._fields_) + ")"
 
 
+class a2amd_osc3filt_windows_info(C.Structure):
+    """include/a2amd_osc3win.h: the 3 x wtosc-filter12-panmix voices whose only records of the most recent batch were cut
+    windows - those the class's windows launch rendered, and those refused"""
+    _fields_ = [(n, C.c_uint32) for n in ("launched", "window_voices", "gliding_voices", "windows", "refused_tiling",
+                                          "vpg", "workgroups", "reserved")]
+
+    def __repr__(self):
+        return "osc3filt_windows_info(" + ", ".join(f"{n}={getattr(self, n)}" for n, _ in self._fields_) + ")"
+
+
 class a2amd_osc2_batch_info(C.Structure):
     """include/a2amd_osc2.h: how k_leaf_osc2pan walked the settled voices of the most recent batch"""
     _fields_ = [(n, C.c_uint32) for n in ("launched", "voices", "vpw", "ysplit", "voice_major", "superchunks_voice_major",
@@ -259,6 +269,9 @@ class Backend:
         self._last_batch_osc3filt = None
         if hasattr(lib, prefix + "last_batch_osc3filt"):
             self._last_batch_osc3filt = fn("last_batch_osc3filt", i32, vp, C.POINTER(a2amd_osc3filt_batch_info))
+        self._last_batch_osc3filt_windows = None
+        if hasattr(lib, prefix + "last_batch_osc3filt_windows"):
+            self._last_batch_osc3filt_windows = fn("last_batch_osc3filt_windows", i32, vp, C.POINTER(a2amd_osc3filt_windows_info))
         self._last_batch_osc2 = None
         if hasattr(lib, prefix + "last_batch_osc2"):
             self._last_batch_osc2 = fn("last_batch_osc2", i32, vp, C.POINTER(a2amd_osc2_batch_info))
@@ -462,6 +475,16 @@ class Backend:
         bi = a2amd_osc3filt_batch_info()
         self._chk(self._last_batch_osc3filt(self.ctx, C.byref(bi)), "last_batch_osc3filt")
         return bi
+
+    def last_batch_osc3filt_windows(self):
+        """a2amd_last_batch_osc3filt_windows: whether k_leaf_osc3filtpan_win, the windows launch, ran for the most recent
+        batch, the voices of the class whose windows-only run it rendered (of which still gliding), their windows, the
+        windows-only runs refused for not tiling, its voices per workgroup and its workgroups"""
+        if self._last_batch_osc3filt_windows is None:
+            raise RuntimeError(f"this library has no {self.prefix}last_batch_osc3filt_windows")
+        wi = a2amd_osc3filt_windows_info()
+        self._chk(self._last_batch_osc3filt_windows(self.ctx, C.byref(wi)), "last_batch_osc3filt_windows")
+        return wi
 
     def last_batch_osc2(self):
         """a2amd_last_batch_osc2: whether k_leaf_osc2pan was launched for the most recent batch, the voices on its list,

@@ -433,7 +433,8 @@ typedef struct a2amd_batch_info {
 	uint32_t win_slabs;        /* slabs the window kernels cut the batch into (0: not launched)         */
 	uint32_t n_moving_listed;  /* voices given the stand-in record: gliding ones, and the device-seeded noise voices
 	                            * that k_leaf_noisepan does not render (a2amd_noisepan.h: standin_voices)          */
-	uint32_t general_voices;   /* record-carrying leaf voices sent to the general kernel                */
+	uint32_t general_voices;   /* record-carrying leaf voices sent to the general kernel (not: the three-oscillator leads of
+	                            * k_leaf_osc3filtpan's windows launch, a2amd_osc3win.h - they carry records and are not sent there) */
 } a2amd_batch_info;
 int  a2amd_last_batch(const a2amd_ctx *ctx, a2amd_batch_info *bi);
 
@@ -471,6 +472,8 @@ int  a2amd_last_batch(const a2amd_ctx *ctx, a2amd_batch_info *bi);
 #include "a2amd_osc2tame_kernel.h"
 /* The quiet kernel of three-oscillator subtractive leads: a2amd_last_batch_osc3filt(). */
 #include "a2amd_osc3filt.h"
+/* ... and its windows launch, for the leads whose only records are cut windows: a2amd_last_batch_osc3filt_windows(). */
+#include "a2amd_osc3win.h"
 /* What the host has done with the wave pool and its tables - growth, the footprint policy, reuse: a2amd_wave_pool_info(). */
 #include "a2amd_wavepool.h"
 

@@ -8,17 +8,24 @@ time with profiling on (a2amd_set_profiling: no graphs then).
 Cells:
   r64, r1024, r16384   that many voices under the root, 64 fragments a batch: a player's 4 096-frame buffer
   g16384               16 384 voices under 256 delay groups of 64, 256 fragments a batch
+  c6, c64, c1024, c16384   that many voices in one stereo group, 64 fragments a batch of which the first is cut in two -
+                       (0, 31) (31, 33), walked by calls, the group once per window; the other 63 repeated: every lead's
+                       run is windows only in every batch.  k_leaf_osc3filtpan_win renders them (include/a2amd_osc3win.h); with
+                       A2AMD_NO_FAST=2048 the general kernel, as before that launch existed - window_voices must then be 0
 
 usage: [A2AMD_NO_FAST=1024] tools/osc3filt_timing.py CELL [batches] [warm-up batches]   -> one JSON line
-       tools/osc3filt_timing.py all OUT.jsonl [repeats]    every cell, class on and off interleaved `repeats` (3) times,
-                                                           one process each; the lines to OUT.jsonl, a table to stdout"""
+       tools/osc3filt_timing.py all OUT.jsonl [repeats]    every r and g cell, class on and off interleaved `repeats` (3)
+                                                           times, one process each; the lines to OUT.jsonl, a table to stdout
+       tools/osc3filt_timing.py cut OUT.jsonl [repeats]    the c cells likewise, the windows launch on and off (2048)"""
 import ctypes, json, os, subprocess, sys, time
 
 CELLS = ("r64", "r1024", "r16384", "g16384")
+CUT_CELLS = ("c6", "c64", "c1024", "c16384")
 OFF = "1024"
+CUT_OFF = "2048"
 
 
-def run_all(path, repeats):
+def run_all(path, repeats, CELLS=CELLS, OFF=OFF):
     rows = []
     with open(path, "w") as out:
         for _rep in range(repeats):
@@ -48,8 +55,9 @@ def run_all(path, repeats):
               f"{on[len(on) // 2] - off[len(off) // 2]:+.3f} |")
 
 
-if len(sys.argv) > 1 and sys.argv[1] == "all":
-    run_all(sys.argv[2], int(sys.argv[3]) if len(sys.argv) > 3 else 3)
+if len(sys.argv) > 1 and sys.argv[1] in ("all", "cut"):
+    cut = sys.argv[1] == "cut"
+    run_all(sys.argv[2], int(sys.argv[3]) if len(sys.argv) > 3 else 3, CUT_CELLS if cut else CELLS, CUT_OFF if cut else OFF)
     sys.exit(0)
 
 cell = sys.argv[1] if len(sys.argv) > 1 else "r1024"
@@ -73,25 +81,52 @@ bfrags = 256 if cell[0] == "g" else 64
 be = audiality2_amd.open_backend(max_batch=bfrags)
 sc = synth.Scene(be)
 sc.root()
+cutg = None
 if cell[0] == "g":
     for g in range(256):
         sc.add_voices(nvoices // 256, "osc3-filter-pan", group=sc.add_group(preset="fmtest4"), total=nvoices)
+elif cell[0] == "c":
+    cutg = sc.add_bus_group()
+    sc.add_voices(nvoices, "osc3-filter-pan", group=cutg, total=nvoices)
 else:
     sc.add_voices(nvoices, "osc3-filter-pan", total=nvoices)
 
+
+def walk_cut(g, windows=((0, 31), (31, 33))):
+    """one 64-frame fragment in which the group g, and every lead in it, is walked once per window (Scene.walk otherwise)"""
+    be.fragment(64)
+    be.unit_process(sc.rootv[0], 0, 64)
+    for a, m in windows:
+        be.unit_process(g["units"][0], a, m)
+        for units in g["leaves"]:
+            for u in units:
+                be.unit_process(u, a, m)
+        be.inline_end(g["units"][0])
+        for u in g["units"][1:]:
+            be.unit_process(u, a, m)
+    be.inline_end(sc.rootv[0])
+    be.unit_process(sc.rootv[1], 0, 64)
+    be.unit_process(sc.rootv[2], 0, 64)
+
+
 sc.walk(64)
 be.render(64)
-rows, infos = [], []
+rows, infos, winfos = [], [], []
 for b in range(warm + batches):
     if b == warm:
         be.lib.a2amd_set_profiling(be.ctx, 1)
-    be.fragment_repeat(64, bfrags)
+    if cutg:
+        walk_cut(cutg)
+        be.fragment_repeat(64, bfrags - 1)
+    else:
+        be.fragment_repeat(64, bfrags)
     t1 = time.perf_counter()
     out = be.render(64 * bfrags)
     t2 = time.perf_counter()
     if b >= warm:
         rows.append(t2 - t1)
         infos.append(be.last_batch_osc3filt())
+        winfos.append(be.last_batch_osc3filt_windows())
 st = Stats()
 be.lib.a2amd_get_stats(be.ctx, ctypes.byref(st))
 rec = np.array(rows) * 1e3
@@ -104,5 +139,7 @@ print(json.dumps({"cell": cell, "no_fast": os.environ.get("A2AMD_NO_FAST", "0"),
                   "launched": sorted({int(i.launched) for i in infos}), "class_voices": sorted({int(i.class_voices) for i in infos}),
                   "quiet_voices": sorted({int(i.quiet_voices) for i in infos}), "record_voices": sorted({int(i.record_voices) for i in infos}),
                   "vpg": sorted({int(i.vpg) for i in infos}), "workgroups": sorted({int(i.workgroups) for i in infos}),
+                  "window_voices": sorted({int(w.window_voices) for w in winfos}), "windows": sorted({int(w.windows) for w in winfos}),
+                  "window_vpg": sorted({int(w.vpg) for w in winfos}), "window_workgroups": sorted({int(w.workgroups) for w in winfos}),
                   "peak": int(np.abs(out).max()), "sum": int(out.astype(np.int64).sum())}))
 be.close()
