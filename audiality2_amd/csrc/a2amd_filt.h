@@ -1,5 +1,6 @@
 // a2amd_filt.h - filter12's recurrence, lane = voice: what the filter wavefront of k_leaf_oscfiltpan / k_leaf_osc2filtpan
-// (a2amd_fast.hip) and of k_leaf_noisefiltpan (a2amd_noisefiltpan.hip) runs along a voice's row of an LDS tile.
+// (a2amd_fast.hip), of k_leaf_noisefiltpan (a2amd_noisefiltpan.hip) and of k_leaf_osc3filtpan / k_leaf_osc3filtpan_win
+// (a2amd_osc3filtpan.hip) runs along a voice's row of an LDS tile.
 #pragma once
 #include "a2amd_device.h"
 #include "a2amd_dsp.h"
@@ -57,6 +58,24 @@ DEV void filt_row(int *row, int n, int ff, int lp, int bp, int hp, int &d1, int 
 		row[s] = filt_step<LPRAW>(row[s], qv >> 12, ff, lp, bp, hp, d1, d2);
 		if(!QREST)
 			qv = wadd(qv, qdelta);
+	}
+}
+
+// filt_row for a row format and a q ramper that only the running wavefront knows (lpraw, qrest: wave-uniform; qdelta is
+// not read where q rests): the quiet kernels' one statement of the four instantiations.  (k_leaf_oscfiltpan and
+// k_leaf_osc2filtpan choose for themselves, a2amd_fast.hip.)
+DEV void filt_row_pick(bool lpraw, bool qrest, int *row, int n, int ff, int lp, int bp, int hp, int &d1, int &d2, int &qv, int qdelta)
+{
+	if(qrest) {
+		if(lpraw)
+			filt_row<true, true>(row, n, ff, lp, bp, hp, d1, d2, qv, 0);
+		else
+			filt_row<false, true>(row, n, ff, lp, bp, hp, d1, d2, qv, 0);
+	} else {
+		if(lpraw)
+			filt_row<true, false>(row, n, ff, lp, bp, hp, d1, d2, qv, qdelta);
+		else
+			filt_row<false, false>(row, n, ff, lp, bp, hp, d1, d2, qv, qdelta);
 	}
 }
 

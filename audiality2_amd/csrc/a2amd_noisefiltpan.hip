@@ -105,10 +105,7 @@ void k_leaf_noisefiltpan(const A2DParams *__restrict__ pp, const int *__restrict
 				if(n > 0 && ok) {
 					int *row = nf_tiles + (f % 3) * tsize + lane * QUIET_PITCH;
 					int qv = qt_l;
-					if(lpraw)
-						filt_row<true, true>(row, n, ff_l, lp_l, bp_l, hp_l, d1_l, d2_l, qv, 0);
-					else
-						filt_row<false, true>(row, n, ff_l, lp_l, bp_l, hp_l, d1_l, d2_l, qv, 0);
+					filt_row_pick(lpraw, true, row, n, ff_l, lp_l, bp_l, hp_l, d1_l, d2_l, qv, 0);
 				}
 			}
 			filt_barrier();
@@ -177,9 +174,7 @@ void k_leaf_noisefiltpan(const A2DParams *__restrict__ pp, const int *__restrict
 				for(unsigned long long m = mine; m; m &= m - 1) {
 					const int v = (int)__builtin_ctzll(m);
 					busrun_voice(run, out, f, my_off, my_nch, v);
-					int y = tile[v * QUIET_PITCH + lane];
-					if(lpraw)
-						y = wmul(y, rdl(lp_l, v)) >> 3;	// (filt_step: the row holds l)
+					const int y = quiet_row(tile, v, lane, lpraw, lp_l);
 					if(lane < n) {
 						run.acc0 = wadd(run.acc0, mul64s(y, rdl(cfirst ? pg.v0 : pg.v0r, v), 24));
 						run.acc1 = wadd(run.acc1, mul64s(y, rdl(cfirst ? pg.v1 : pg.v1r, v), 24));
@@ -197,15 +192,8 @@ void k_leaf_noisefiltpan(const A2DParams *__restrict__ pp, const int *__restrict
 		noisev_store(nz, total_frames, ustate + (size_t)u0 * A2D_USTATE, ustate + (size_t)u2 * A2D_USTATE);
 }
 
-// voices per workgroup: at most QUIET_MAXV (one per lane of the filter wavefront)
 int a2d_launch_leaf_noisefiltpan(const A2DParams *dparams, const A2DParams &hp, const int *dlist, int nlist, int vpg, void *stream)
 {
-	if(nlist <= 0)
-		return 0;
-	vpg = vpg < 1 ? 1 : vpg > QUIET_MAXV ? QUIET_MAXV : vpg;
-	const dim3 grid((nlist + vpg - 1) / vpg), block(64 * QUIET_WAVES);
-	const size_t dyn = (size_t)3 * vpg * QUIET_PITCH * sizeof(int);
-	hipLaunchKernelGGL(k_leaf_noisefiltpan, grid, block, dyn, (hipStream_t)stream, dparams, dlist, nlist, vpg, hp.voices, hp.runs,
-			hp.ustate, hp.nseed, hp.nslot, hp.nnoise, hp.nfrags, hp.busmem);
-	return hipGetLastError() != hipSuccess;
+	return quiet_launch(k_leaf_noisefiltpan, dparams, dlist, nlist, vpg, stream, hp.voices, hp.runs, hp.ustate, hp.nseed, hp.nslot,
+			hp.nnoise, hp.nfrags, hp.busmem);
 }

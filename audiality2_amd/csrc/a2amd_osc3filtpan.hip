@@ -39,6 +39,154 @@
 #include "a2amd_filt.h"
 #include "a2amd_quiet.h"
 
+// ---- What k_leaf_osc3filtpan and k_leaf_osc3filtpan_win (the windows launch, below) share, each stated once.  A window
+// is (a, m): m frames from frame a of the fragment; k_leaf_osc3filtpan's only window is the fragment, (0, n). ----
+
+// Lane = voice: a voice of the workgroup as every wavefront reads it - its five units, its output bus, its filter's three
+// gains, its run's bounds (with_run only) - and whether it is this launch's to render (ok): the ONE statement of the
+// class's rule.  with_run: the launch of the voices that HAVE a run this batch (k_leaf_osc3filtpan_win), or of those that
+// have none.  A voice that fails is left untouched: every word 0, no bus.
+struct O3Voice { int uo0, uo1, uo2, uf, up, off, nch, lp, bp, hp, rfirst, rend; bool ok; };
+
+DEV O3Voice o3_voice(bool with_run, bool listed, const int *list, int at, const A2DVoice *voices, const A2DRun *runs, const int *ustate)
+{
+	O3Voice V = { 0, 0, 0, 0, 0, -1, 2, 0, 0, 0, 0, 0, false };
+	if(listed) {
+		const int slot = list[at];
+		const A2DRun run = runs[slot];
+		if((run.count != 0) == with_run) {
+			const A2DVoice &vc = voices[slot];
+			V.uo0 = vc.unit[0]; V.uo1 = vc.unit[1]; V.uo2 = vc.unit[2];
+			V.uf = vc.unit[3];
+			V.up = vc.unit[4];
+			V.off = vc.out_off;
+			V.nch = vc.out_nch;
+			const int m0 = ustate[(size_t)V.uo0 * A2D_USTATE + OW_MODE], m1 = ustate[(size_t)V.uo1 * A2D_USTATE + OW_MODE],
+					m2 = ustate[(size_t)V.uo2 * A2D_USTATE + OW_MODE];
+			const int *wf = ustate + (size_t)V.uf * A2D_USTATE;
+			V.lp = wf[FW_LP]; V.bp = wf[FW_BP]; V.hp = wf[FW_HP];
+			V.ok = vc.nunits == 5 && V.off >= 0 && V.nch >= 2 && !wf[FW_RAMP] &&
+					(m0 == A2D_OSC_MIPWAVE || m0 == A2D_OSC_OFF) && (m1 == A2D_OSC_MIPWAVE || m1 == A2D_OSC_OFF) &&
+					(m2 == A2D_OSC_MIPWAVE || m2 == A2D_OSC_OFF);
+			if(with_run && V.ok) {
+				V.rfirst = run.first;
+				V.rend = run.first + run.count;
+			}
+		}
+	}
+	return V;
+}
+
+// The filter wavefront's state, lane = voice: the q ramper, f12_process's f and the two delays
+struct O3Filt { Ramp q; int ff, d1, d2; };
+
+DEV O3Filt o3_filt_load(const O3Voice &V, const int *ustate)
+{
+	O3Filt F = { { 0, 0, 0, 0 }, 0, 0, 0 };
+	if(V.ok) {
+		const int *wf = ustate + (size_t)V.uf * A2D_USTATE;
+		F.q = ramp_load(wf + FW_Q);
+		F.ff = wf[FW_F1] >> 12;		// f12_process's f, filter12.c:99 (no coefficient ramp: df = 0)
+		F.d1 = wf[FW_D1A];
+		F.d2 = wf[FW_D2A];
+	}
+	return F;
+}
+
+// state out: the filter's words as f12_process / ctl_store leave them
+DEV void o3_filt_store(const O3Voice &V, int *ustate, const O3Filt &F)
+{
+	if(V.ok) {
+		int *wf = ustate + (size_t)V.uf * A2D_USTATE;
+		ramp_store(wf + FW_Q, F.q);
+		wf[FW_D1A] = F.d1;
+		wf[FW_D2A] = F.d2;
+	}
+}
+
+// A worker's state, lane = voice, its own voices only (mylane): the three oscillators as ctl_load loads them, the
+// panmix's rampers.  (Five objects, not one struct of them: as members of one the compiler pairs the oscillators' words
+// differently, and the kernels come out 5 - 9 VGPRs larger - profiles/osc3_shared_stages.md.)
+DEV void o3_work_load(OscV &o0, OscV &o1, OscV &o2, Ramp &vol, Ramp &pan, const O3Voice &V, const int *ustate, bool mylane)
+{
+	oscv_clear(o0);
+	oscv_clear(o1);
+	oscv_clear(o2);
+	vol = pan = Ramp{ 0, 0, 0, 0 };
+	if(mylane) {
+		oscv_load(o0, ustate + (size_t)V.uo0 * A2D_USTATE);
+		oscv_load(o1, ustate + (size_t)V.uo1 * A2D_USTATE);
+		oscv_load(o2, ustate + (size_t)V.uo2 * A2D_USTATE);
+		const int *wp = ustate + (size_t)V.up * A2D_USTATE;
+		vol = ramp_load(wp + PW_VOL);
+		pan = ramp_load(wp + PW_PAN);
+	}
+}
+
+// state out: ctl_store's words of the oscillators and the panmix
+DEV void o3_work_store(const O3Voice &V, int *ustate, const OscV &o0, const OscV &o1, const OscV &o2, const Ramp &vol, const Ramp &pan, bool mylane)
+{
+	if(mylane) {
+		oscv_store(ustate + (size_t)V.uo0 * A2D_USTATE, o0);
+		oscv_store(ustate + (size_t)V.uo1 * A2D_USTATE, o1);
+		oscv_store(ustate + (size_t)V.uo2 * A2D_USTATE, o2);
+		int *wp = ustate + (size_t)V.up * A2D_USTATE;
+		ramp_store(wp + PW_VOL, vol);
+		ramp_store(wp + PW_PAN, pan);
+	}
+}
+
+// Stage C (the header comment), one pass: a window (a, m) of each voice of mk (lane = voice: has, a, m; mk: the voices
+// that have one), summed into the buses of fragment f.  Lane = voice: panmix_process12's head for the window, the rampers
+// stepped over it.  Lane = frame: the voices whose window holds this frame, at frame lane - a of it.  WIN: (a, m) are
+// read out of the voices' lanes; else they are the same in every lane - the fragment, (0, n) - and cost no lane read.
+template<bool WIN>
+DEV void o3_pan_pass(const int *tile, const O3Voice &V, Ramp &vol, Ramp &pan, bool has, int a, int m, unsigned long long mk, bool lpraw,
+		const QuietOut &out, int f, int lane)
+{
+	int pv = 0, pdv = 0, ppn = 0, pdp = 0, g0 = 0, g1 = 0;
+	bool pcl = false;
+	if(has) {
+		// panmix.c:84-95: the clamp variant chosen in front of a2_PrepareRamper
+		pcl = a2s_pan_over(pan.target) || a2s_pan_over(pan.value);
+		ramp_prepare_v(vol, m);
+		ramp_prepare_v(pan, m);
+		pv = vol.value; pdv = vol.delta;
+		ppn = pan.value; pdp = pan.delta;
+		a2s_pan_gains(pv, ppn, pcl, &g0, &g1);	// (volume and pan at rest: the window's two gains)
+		ramp_run(vol, m);
+		ramp_run(pan, m);
+	}
+	const unsigned long long mramp = __ballot((pdv | pdp) != 0), mclamp = __ballot(pcl);
+	BusRun run = busrun_begin();
+	for(unsigned long long rest = mk; rest; rest &= rest - 1) {
+		const int v = (int)__builtin_ctzll(rest);
+		busrun_voice(run, out, f, V.off, V.nch, v);
+		const int wk = lane - (WIN ? rdl(a, v) : a);
+		const bool in = wk >= 0 && wk < (WIN ? rdl(m, v) : m);
+		const int y = quiet_row(tile, v, lane, lpraw, V.lp);
+		int v0 = rdl(g0, v), v1 = rdl(g1, v);
+		if((mramp >> v) & 1ull) {
+			// win_pan's arithmetic for a window in which volume or pan moves
+			const int vk = wadd(rdl(pv, v), wmul(rdl(pdv, v), wk));
+			const int pk = wadd(rdl(ppn, v), wmul(rdl(pdp, v), wk));
+			const int vp = mul64s(pk, vk, 24);
+			v0 = wsub(vk, vp);
+			v1 = wadd(vk, vp);
+			if((mclamp >> v) & 1ull) {
+				const int lim = wshl(vk, 1);
+				if(v0 > lim) v0 = lim;
+				if(v1 > lim) v1 = lim;
+			}
+		}
+		if(in) {
+			run.acc0 = wadd(run.acc0, mul64s(y, v0, 24));
+			run.acc1 = wadd(run.acc1, mul64s(y, v1, 24));
+		}
+	}
+	busrun_end(run, out, f);
+}
+
 __global__ __launch_bounds__(64 * QUIET_WAVES)
 void k_leaf_osc3filtpan(const A2DParams *__restrict__ pp, const int *__restrict__ list, int nlist, int vpg,
 		const A2DVoice *__restrict__ voices, const A2DRun *__restrict__ runs, int *ustate,
@@ -63,28 +211,8 @@ void k_leaf_osc3filtpan(const A2DParams *__restrict__ pp, const int *__restrict_
 	const int tsize = vpg * QUIET_PITCH;
 
 	// lane v: voice v of this workgroup, in every wavefront
-	int uo0 = 0, uo1 = 0, uo2 = 0, uf = 0, up = 0, my_off = -1, my_nch = 2;
-	int lp_l = 0, bp_l = 0, hp_l = 0;
-	bool ok = false;
-	if(lane < nv) {
-		const int slot = list[first + lane];
-		if(runs[slot].count == 0) {
-			const A2DVoice &vc = voices[slot];
-			uo0 = vc.unit[0]; uo1 = vc.unit[1]; uo2 = vc.unit[2];
-			uf = vc.unit[3];
-			up = vc.unit[4];
-			my_off = vc.out_off;
-			my_nch = vc.out_nch;
-			const int m0 = ustate[(size_t)uo0 * A2D_USTATE + OW_MODE], m1 = ustate[(size_t)uo1 * A2D_USTATE + OW_MODE],
-					m2 = ustate[(size_t)uo2 * A2D_USTATE + OW_MODE];
-			const int *wf = ustate + (size_t)uf * A2D_USTATE;
-			lp_l = wf[FW_LP]; bp_l = wf[FW_BP]; hp_l = wf[FW_HP];
-			ok = vc.nunits == 5 && my_off >= 0 && my_nch >= 2 && !wf[FW_RAMP] &&
-					(m0 == A2D_OSC_MIPWAVE || m0 == A2D_OSC_OFF) && (m1 == A2D_OSC_MIPWAVE || m1 == A2D_OSC_OFF) &&
-					(m2 == A2D_OSC_MIPWAVE || m2 == A2D_OSC_OFF);
-		}
-	}
-	const QuietWg wg = quiet_wg(ok, bp_l, hp_l, my_off, my_nch);
+	const O3Voice V = o3_voice(false, lane < nv, list, first + lane, voices, runs, ustate);
+	const QuietWg wg = quiet_wg(V.ok, V.bp, V.hp, V.off, V.nch);
 	if(!wg.todo)
 		return;		// (the whole workgroup)
 	const bool lpraw = wg.lpraw, wgbus = wg.wgbus;
@@ -92,15 +220,7 @@ void k_leaf_osc3filtpan(const A2DParams *__restrict__ pp, const int *__restrict_
 
 	if(wv == 0) {
 		// ================= the filter wavefront: lane = voice =================
-		Ramp q = { 0, 0, 0, 0 };
-		int ff_l = 0, d1_l = 0, d2_l = 0;
-		if(ok) {
-			const int *wf = ustate + (size_t)uf * A2D_USTATE;
-			q = ramp_load(wf + FW_Q);
-			ff_l = wf[FW_F1] >> 12;		// f12_process's f, filter12.c:99 (no coefficient ramp: df = 0)
-			d1_l = wf[FW_D1A];
-			d2_l = wf[FW_D2A];
-		}
+		O3Filt F = o3_filt_load(V, ustate);
 		__builtin_amdgcn_s_setprio(3);
 		for(int st = 0; st < nsteps; ++st) {
 			const int f = st - 1;
@@ -108,57 +228,29 @@ void k_leaf_osc3filtpan(const A2DParams *__restrict__ pp, const int *__restrict_
 				const int n = min((int)pp->fragframes[f], A2D_FRAG);
 				if(n > 0) {
 					// f12_process's head, filter12.c:86-96
-					if(ok)
-						ramp_prepare_v(q, n);
-					const bool qrest = __all(!ok || q.delta == 0);
-					if(ok) {
+					if(V.ok)
+						ramp_prepare_v(F.q, n);
+					const bool qrest = __all(!V.ok || F.q.delta == 0);
+					if(V.ok) {
 						int *row = o3_tiles + (f % 3) * tsize + lane * QUIET_PITCH;
-						int qv = q.value;
-						if(qrest) {
-							if(lpraw)
-								filt_row<true, true>(row, n, ff_l, lp_l, bp_l, hp_l, d1_l, d2_l, qv, 0);
-							else
-								filt_row<false, true>(row, n, ff_l, lp_l, bp_l, hp_l, d1_l, d2_l, qv, 0);
-						} else {
-							if(lpraw)
-								filt_row<true, false>(row, n, ff_l, lp_l, bp_l, hp_l, d1_l, d2_l, qv, q.delta);
-							else
-								filt_row<false, false>(row, n, ff_l, lp_l, bp_l, hp_l, d1_l, d2_l, qv, q.delta);
-						}
-						ramp_run(q, n);
+						int qv = F.q.value;
+						filt_row_pick(lpraw, qrest, row, n, F.ff, V.lp, V.bp, V.hp, F.d1, F.d2, qv, F.q.delta);
+						ramp_run(F.q, n);
 					}
 				}
 			}
 			filt_barrier();
 		}
-		// state out: the filter's words as f12_process / ctl_store leave them
-		if(ok) {
-			int *wf = ustate + (size_t)uf * A2D_USTATE;
-			ramp_store(wf + FW_Q, q);
-			wf[FW_D1A] = d1_l;
-			wf[FW_D2A] = d2_l;
-		}
+		o3_filt_store(V, ustate, F);
 		return;
 	}
 
 	// ================= workers: a range of the workgroup's voices each =================
 	const unsigned long long mine = quiet_worker_voices(wv, nv, wg.todo);	// (wavefront 4: none)
 	const bool mylane = (mine >> lane) & 1ull;
-
-	// lane v, my voices only: the three oscillators as ctl_load loads them, the panmix's rampers
 	OscV o0, o1, o2;
-	oscv_clear(o0);
-	oscv_clear(o1);
-	oscv_clear(o2);
-	Ramp vol = { 0, 0, 0, 0 }, pan = { 0, 0, 0, 0 };
-	if(mylane) {
-		oscv_load(o0, ustate + (size_t)uo0 * A2D_USTATE);
-		oscv_load(o1, ustate + (size_t)uo1 * A2D_USTATE);
-		oscv_load(o2, ustate + (size_t)uo2 * A2D_USTATE);
-		const int *wp = ustate + (size_t)up * A2D_USTATE;
-		vol = ramp_load(wp + PW_VOL);
-		pan = ramp_load(wp + PW_PAN);
-	}
+	Ramp vol, pan;
+	o3_work_load(o0, o1, o2, vol, pan, V, ustate, mylane);
 	const CoefRsrc rs = coef_rsrc(wavecoef);
 
 	const QuietOut out = { busmem, &o3_acc, wgbus, lane };
@@ -214,91 +306,29 @@ void k_leaf_osc3filtpan(const A2DParams *__restrict__ pp, const int *__restrict_
 				}
 			}
 		}
-		// ---- C(st - 2) ----
+		// ---- C(st - 2): one pass, every voice's window the fragment ----
 		if(st >= 2 && st - 2 < nfrags && mine) {
 			const int f = st - 2;
 			const int n = min((int)pp->fragframes[f], A2D_FRAG);
-			if(n > 0) {
-				// control, lane = voice: panmix_process12's head, panmix.c:84-95 (the clamp variant chosen in front of
-				// a2_PrepareRamper), the rampers stepped over the window
-				int pv = 0, pdv = 0, ppn = 0, pdp = 0, g0 = 0, g1 = 0;
-				bool pcl = false;
-				if(mylane) {
-					pcl = a2s_pan_over(pan.target) || a2s_pan_over(pan.value);
-					ramp_prepare_v(vol, n);
-					ramp_prepare_v(pan, n);
-					pv = vol.value; pdv = vol.delta;
-					ppn = pan.value; pdp = pan.delta;
-					// (volume and pan at rest: the window's two gains)
-					a2s_pan_gains(pv, ppn, pcl, &g0, &g1);
-					ramp_run(vol, n);
-					ramp_run(pan, n);
-				}
-				const unsigned long long mramp = __ballot((pdv | pdp) != 0), mclamp = __ballot(pcl);
-				// lane = frame
-				const int *tile = o3_tiles + (f % 3) * tsize;
-				const bool in = lane < n;
-				BusRun run = busrun_begin();
-				for(unsigned long long m = mine; m; m &= m - 1) {
-					const int v = (int)__builtin_ctzll(m);
-					busrun_voice(run, out, f, my_off, my_nch, v);
-					int y = tile[v * QUIET_PITCH + lane];
-					if(lpraw)
-						y = wmul(y, rdl(lp_l, v)) >> 3;	// (filt_step: the row holds l)
-					int v0 = rdl(g0, v), v1 = rdl(g1, v);
-					if((mramp >> v) & 1ull) {
-						// win_pan's arithmetic for a window in which volume or pan moves
-						const int vk = wadd(rdl(pv, v), wmul(rdl(pdv, v), lane));
-						const int pk = wadd(rdl(ppn, v), wmul(rdl(pdp, v), lane));
-						const int vp = mul64s(pk, vk, 24);
-						v0 = wsub(vk, vp);
-						v1 = wadd(vk, vp);
-						if((mclamp >> v) & 1ull) {
-							const int lim = wshl(vk, 1);
-							if(v0 > lim) v0 = lim;
-							if(v1 > lim) v1 = lim;
-						}
-					}
-					if(in) {
-						run.acc0 = wadd(run.acc0, mul64s(y, v0, 24));
-						run.acc1 = wadd(run.acc1, mul64s(y, v1, 24));
-					}
-				}
-				busrun_end(run, out, f);
-			}
+			if(n > 0)
+				o3_pan_pass<false>(o3_tiles + (f % 3) * tsize, V, vol, pan, mylane, 0, n, mine, lpraw, out, f, lane);
 		}
 		filt_barrier();
 	}
-
-	// state out: ctl_store's words of the oscillators and the panmix
-	if(mylane) {
-		oscv_store(ustate + (size_t)uo0 * A2D_USTATE, o0);
-		oscv_store(ustate + (size_t)uo1 * A2D_USTATE, o1);
-		oscv_store(ustate + (size_t)uo2 * A2D_USTATE, o2);
-		int *wp = ustate + (size_t)up * A2D_USTATE;
-		ramp_store(wp + PW_VOL, vol);
-		ramp_store(wp + PW_PAN, pan);
-	}
+	o3_work_store(V, ustate, o0, o1, o2, vol, pan, mylane);
 }
 
-// voices per workgroup: at most QUIET_MAXV (one per lane of the filter wavefront)
 int a2d_launch_leaf_osc3filtpan(const A2DParams *dparams, const A2DParams &hp, const int *dlist, int nlist, int vpg, void *stream)
 {
-	if(nlist <= 0)
-		return 0;
-	vpg = vpg < 1 ? 1 : vpg > QUIET_MAXV ? QUIET_MAXV : vpg;
-	const dim3 grid((nlist + vpg - 1) / vpg), block(64 * QUIET_WAVES);
-	const size_t dyn = (size_t)3 * vpg * QUIET_PITCH * sizeof(int);
-	hipLaunchKernelGGL(k_leaf_osc3filtpan, grid, block, dyn, (hipStream_t)stream, dparams, dlist, nlist, vpg, hp.voices, hp.runs,
-			hp.ustate, hp.waves, hp.ptab, hp.wavecoef, hp.nfrags, hp.busmem);
-	return hipGetLastError() != hipSuccess;
+	return quiet_launch(k_leaf_osc3filtpan, dparams, dlist, nlist, vpg, stream, hp.voices, hp.runs, hp.ustate, hp.waves, hp.ptab,
+			hp.wavecoef, hp.nfrags, hp.busmem);
 }
 
 // ---------------------------------------------------------------------------
 // k_leaf_osc3filtpan_win: the windows launch.  The same voices in the batches in which their only records are R_SEG windows
 // that tile the fragments (a parent's VM woke inside a fragment: include/a2amd_osc3win.h) - every ramper stepped window by
-// window, as the reference's Process(offset, frames) calls would.  Workgroup, tiles, stages and helpers are
-// k_leaf_osc3filtpan's; what differs:
+// window, as the reference's Process(offset, frames) calls would.  Workgroup, tiles and stages are k_leaf_osc3filtpan's,
+// and so is every piece above; what differs:
 //   The voices.  Those of its list that HAVE a run (runs[slot].count != 0): the host lists a voice here only where
 //             seg_rows() (a2amd_sched.cpp) has found the run windows only and a tiling, and on no other list.
 //   The windows.  Read in place: lane = voice keeps a cursor into its run per stage, and a fragment's windows are a mask over
@@ -315,12 +345,12 @@ int a2d_launch_leaf_osc3filtpan(const A2DParams *dparams, const A2DParams &hp, c
 //             fragment is filtered whole, as in k_leaf_osc3filtpan: a2_PrepareRamper without a timer (a2_dsp.h:130-134) sets
 //             value = target and delta = 0 whatever 'frames' is and leaves the timer 0, and a2_RunRamper (:152-155) then adds
 //             0 - the same q in every frame and the same words left, however the fragment is cut.
-//   C(f - 2)  over k likewise: panmix_process12's head per window, the clamp flag chosen per window in front of the prepare
-//             (as k_bus_fbdpan_win does); a lane's frame takes the gains, or value + delta * (lane - a), of the window it
-//             lies in.  A pass over k has bus runs of its own (the sums are wrapping adds: their order is free).
+//   C(f - 2)  over k likewise, an o3_pan_pass() each: the head per window, the clamp flag chosen per window in front of the
+//             prepare (as k_bus_fbdpan_win does).  A pass has bus runs of its own (the sums are wrapping adds: their order
+//             is free).
 // D and the state stores are k_leaf_osc3filtpan's: either kernel of the class, or k_voices, takes the voice up next batch.
-// A listed voice that failed 'ok' would be rendered by nobody, so the host must list none.  What excludes each case there
-// (upload(), a2amd_sched.cpp):
+// A listed voice that failed 'ok' - o3_voice(), the rule both launches share - would be rendered by nobody, so the host
+// must list none.  What excludes each case there (upload(), a2amd_sched.cpp):
 //   - five units, a bus of two channels or more: only voices classified CLS_OSC3FILTPAN (is_osc3filtpan_chain(), the classes
 //     fresh where the list is made) are listed;
 //   - an oscillator neither on a mip-mapped wave nor off: noise is not of the class, a 'w' write to noise is a record (the run
@@ -378,34 +408,8 @@ void k_leaf_osc3filtpan_win(const A2DParams *__restrict__ pp, const int *__restr
 	const int tsize = vpg * QUIET_PITCH;
 
 	// lane v: voice v of this workgroup, in every wavefront
-	int uo0 = 0, uo1 = 0, uo2 = 0, uf = 0, up = 0, my_off = -1, my_nch = 2;
-	int lp_l = 0, bp_l = 0, hp_l = 0;
-	int rfirst = 0, rend = 0;	// the voice's run
-	bool ok = false;
-	if(lane < nv) {
-		const int slot = list[first + lane];
-		const A2DRun run = runs[slot];
-		if(run.count != 0) {
-			const A2DVoice &vc = voices[slot];
-			uo0 = vc.unit[0]; uo1 = vc.unit[1]; uo2 = vc.unit[2];
-			uf = vc.unit[3];
-			up = vc.unit[4];
-			my_off = vc.out_off;
-			my_nch = vc.out_nch;
-			const int m0 = ustate[(size_t)uo0 * A2D_USTATE + OW_MODE], m1 = ustate[(size_t)uo1 * A2D_USTATE + OW_MODE],
-					m2 = ustate[(size_t)uo2 * A2D_USTATE + OW_MODE];
-			const int *wf = ustate + (size_t)uf * A2D_USTATE;
-			lp_l = wf[FW_LP]; bp_l = wf[FW_BP]; hp_l = wf[FW_HP];
-			ok = vc.nunits == 5 && my_off >= 0 && my_nch >= 2 && !wf[FW_RAMP] &&
-					(m0 == A2D_OSC_MIPWAVE || m0 == A2D_OSC_OFF) && (m1 == A2D_OSC_MIPWAVE || m1 == A2D_OSC_OFF) &&
-					(m2 == A2D_OSC_MIPWAVE || m2 == A2D_OSC_OFF);
-			if(ok) {
-				rfirst = run.first;
-				rend = run.first + run.count;
-			}
-		}
-	}
-	const QuietWg wg = quiet_wg(ok, bp_l, hp_l, my_off, my_nch);
+	const O3Voice V = o3_voice(true, lane < nv, list, first + lane, voices, runs, ustate);
+	const QuietWg wg = quiet_wg(V.ok, V.bp, V.hp, V.off, V.nch);
 	if(!wg.todo)
 		return;		// (the whole workgroup)
 	const bool lpraw = wg.lpraw, wgbus = wg.wgbus;
@@ -413,27 +417,19 @@ void k_leaf_osc3filtpan_win(const A2DParams *__restrict__ pp, const int *__restr
 
 	if(wv == 0) {
 		// ================= the filter wavefront: lane = voice =================
-		Ramp q = { 0, 0, 0, 0 };
-		int ff_l = 0, d1_l = 0, d2_l = 0;
-		if(ok) {
-			const int *wf = ustate + (size_t)uf * A2D_USTATE;
-			q = ramp_load(wf + FW_Q);
-			ff_l = wf[FW_F1] >> 12;		// f12_process's f, filter12.c:99 (no coefficient ramp: df = 0)
-			d1_l = wf[FW_D1A];
-			d2_l = wf[FW_D2A];
-		}
-		int cur = rfirst;
+		O3Filt F = o3_filt_load(V, ustate);
+		int cur = V.rfirst;
 		__builtin_amdgcn_s_setprio(3);
 		for(int st = 0; st < nsteps; ++st) {
 			const int f = st - 1;
 			if(f >= 0 && f < nfrags) {
 				const int n = min((int)pp->fragframes[f], A2D_FRAG);
-				const unsigned long long cuts = o3w_cuts(recs, cur, rend, f, n);
+				const unsigned long long cuts = o3w_cuts(recs, cur, V.rend, f, n);
 				if(n > 0) {
-					const unsigned long long mycuts = ok ? cuts : 0ull;
+					const unsigned long long mycuts = V.ok ? cuts : 0ull;
 					// (q at rest in the whole wavefront: a window changes nothing - the header comment - and the fragment is one
 					// segment, one window)
-					const bool allrest = __all(!ok || q.timer == 0);
+					const bool allrest = __all(!V.ok || F.q.timer == 0);
 					unsigned long long u = 1ull;	// the union of the voices' window starts
 					if(!allrest)
 						for(;;) {
@@ -445,69 +441,40 @@ void k_leaf_osc3filtpan_win(const A2DParams *__restrict__ pp, const int *__restr
 									((unsigned long long)(unsigned)rdl((int)(unsigned)(mycuts >> 32), v) << 32);
 						}
 					int *row = o3_tiles + (f % 3) * tsize + lane * QUIET_PITCH;
-					int qv = q.value, qd = 0;
+					int qv = F.q.value, qd = 0;
 					while(u) {
 						int s0, len;
 						o3w_next(u, n, s0, len);
 						// f12_process's head, filter12.c:86-96, where a window of this voice starts
-						if(ok && (allrest || ((mycuts >> s0) & 1ull))) {
+						if(V.ok && (allrest || ((mycuts >> s0) & 1ull))) {
 							unsigned long long own = allrest ? 1ull : mycuts >> s0;
 							int a, m;
 							o3w_next(own, n - s0, a, m);
-							ramp_prepare_v(q, m);
-							qv = q.value;
-							qd = q.delta;
-							ramp_run(q, m);
+							ramp_prepare_v(F.q, m);
+							qv = F.q.value;
+							qd = F.q.delta;
+							ramp_run(F.q, m);
 						}
-						const bool qrest = __all(!ok || qd == 0);
-						if(ok) {
-							if(qrest) {
-								if(lpraw)
-									filt_row<true, true>(row + s0, len, ff_l, lp_l, bp_l, hp_l, d1_l, d2_l, qv, 0);
-								else
-									filt_row<false, true>(row + s0, len, ff_l, lp_l, bp_l, hp_l, d1_l, d2_l, qv, 0);
-							} else {
-								if(lpraw)
-									filt_row<true, false>(row + s0, len, ff_l, lp_l, bp_l, hp_l, d1_l, d2_l, qv, qd);
-								else
-									filt_row<false, false>(row + s0, len, ff_l, lp_l, bp_l, hp_l, d1_l, d2_l, qv, qd);
-							}
-						}
+						const bool qrest = __all(!V.ok || qd == 0);
+						if(V.ok)
+							filt_row_pick(lpraw, qrest, row + s0, len, F.ff, V.lp, V.bp, V.hp, F.d1, F.d2, qv, qd);
 					}
 				}
 			}
 			filt_barrier();
 		}
-		// state out: the filter's words as f12_process / ctl_store leave them
-		if(ok) {
-			int *wf = ustate + (size_t)uf * A2D_USTATE;
-			ramp_store(wf + FW_Q, q);
-			wf[FW_D1A] = d1_l;
-			wf[FW_D2A] = d2_l;
-		}
+		o3_filt_store(V, ustate, F);
 		return;
 	}
 
 	// ================= workers: a range of the workgroup's voices each =================
 	const unsigned long long mine = quiet_worker_voices(wv, nv, wg.todo);	// (wavefront 4: none)
 	const bool mylane = (mine >> lane) & 1ull;
-
-	// lane v, my voices only: the three oscillators as ctl_load loads them, the panmix's rampers
 	OscV o0, o1, o2;
-	oscv_clear(o0);
-	oscv_clear(o1);
-	oscv_clear(o2);
-	Ramp vol = { 0, 0, 0, 0 }, pan = { 0, 0, 0, 0 };
-	if(mylane) {
-		oscv_load(o0, ustate + (size_t)uo0 * A2D_USTATE);
-		oscv_load(o1, ustate + (size_t)uo1 * A2D_USTATE);
-		oscv_load(o2, ustate + (size_t)uo2 * A2D_USTATE);
-		const int *wp = ustate + (size_t)up * A2D_USTATE;
-		vol = ramp_load(wp + PW_VOL);
-		pan = ramp_load(wp + PW_PAN);
-	}
+	Ramp vol, pan;
+	o3_work_load(o0, o1, o2, vol, pan, V, ustate, mylane);
 	const CoefRsrc rs = coef_rsrc(wavecoef);
-	int curA = rfirst, curC = rfirst;	// the run's cursor of either stage
+	int curA = V.rfirst, curC = V.rfirst;	// the run's cursor of either stage
 
 	const QuietOut out = { busmem, &o3_acc, wgbus, lane };
 
@@ -522,7 +489,7 @@ void k_leaf_osc3filtpan_win(const A2DParams *__restrict__ pp, const int *__restr
 		if(st < nfrags && mine) {
 			const int f = st;
 			const int n = min((int)pp->fragframes[f], A2D_FRAG);
-			const unsigned long long cuts = o3w_cuts(recs, curA, rend, f, n);
+			const unsigned long long cuts = o3w_cuts(recs, curA, V.rend, f, n);
 			if(n > 0) {
 				unsigned long long rem = mylane ? cuts : 0ull;
 				int *tile = o3_tiles + (f % 3) * tsize;
@@ -579,92 +546,33 @@ void k_leaf_osc3filtpan_win(const A2DParams *__restrict__ pp, const int *__restr
 				}
 			}
 		}
-		// ---- C(st - 2) ----
+		// ---- C(st - 2): a pass per window index (bus runs of its own: the sums are wrapping adds, their order is free) ----
 		if(st >= 2 && st - 2 < nfrags && mine) {
 			const int f = st - 2;
 			const int n = min((int)pp->fragframes[f], A2D_FRAG);
-			const unsigned long long cuts = o3w_cuts(recs, curC, rend, f, n);
+			const unsigned long long cuts = o3w_cuts(recs, curC, V.rend, f, n);
 			if(n > 0) {
 				unsigned long long rem = mylane ? cuts : 0ull;
-				const int *tile = o3_tiles + (f % 3) * tsize;
 				for(;;) {
-					// control, lane = voice: panmix_process12's head, panmix.c:84-95, for the voice's next window (the clamp
-					// variant chosen in front of a2_PrepareRamper), the rampers stepped over it
-					int pv = 0, pdv = 0, ppn = 0, pdp = 0, g0 = 0, g1 = 0, a_l = 0, m_l = 0;
-					bool pcl = false;
+					int a_l = 0, m_l = 0;
 					const bool has = rem != 0;
-					if(has) {
-						o3w_next(rem, n, a_l, m_l);
-						pcl = a2s_pan_over(pan.target) || a2s_pan_over(pan.value);
-						ramp_prepare_v(vol, m_l);
-						ramp_prepare_v(pan, m_l);
-						pv = vol.value; pdv = vol.delta;
-						ppn = pan.value; pdp = pan.delta;
-						// (volume and pan at rest: the window's two gains)
-						a2s_pan_gains(pv, ppn, pcl, &g0, &g1);
-						ramp_run(vol, m_l);
-						ramp_run(pan, m_l);
-					}
 					const unsigned long long mk = __ballot(has);
 					if(!mk)
 						break;
-					const unsigned long long mramp = __ballot((pdv | pdp) != 0), mclamp = __ballot(pcl);
-					// lane = frame: the voices whose window holds this frame
-					BusRun run = busrun_begin();
-					for(unsigned long long m = mk; m; m &= m - 1) {
-						const int v = (int)__builtin_ctzll(m);
-						busrun_voice(run, out, f, my_off, my_nch, v);
-						const int wk = lane - rdl(a_l, v);
-						const bool in = wk >= 0 && wk < rdl(m_l, v);
-						int y = tile[v * QUIET_PITCH + lane];
-						if(lpraw)
-							y = wmul(y, rdl(lp_l, v)) >> 3;	// (filt_step: the row holds l)
-						int v0 = rdl(g0, v), v1 = rdl(g1, v);
-						if((mramp >> v) & 1ull) {
-							// win_pan's arithmetic for a window in which volume or pan moves
-							const int vk = wadd(rdl(pv, v), wmul(rdl(pdv, v), wk));
-							const int pk = wadd(rdl(ppn, v), wmul(rdl(pdp, v), wk));
-							const int vp = mul64s(pk, vk, 24);
-							v0 = wsub(vk, vp);
-							v1 = wadd(vk, vp);
-							if((mclamp >> v) & 1ull) {
-								const int lim = wshl(vk, 1);
-								if(v0 > lim) v0 = lim;
-								if(v1 > lim) v1 = lim;
-							}
-						}
-						if(in) {
-							run.acc0 = wadd(run.acc0, mul64s(y, v0, 24));
-							run.acc1 = wadd(run.acc1, mul64s(y, v1, 24));
-						}
-					}
-					busrun_end(run, out, f);
+					if(has)
+						o3w_next(rem, n, a_l, m_l);
+					o3_pan_pass<true>(o3_tiles + (f % 3) * tsize, V, vol, pan, has, a_l, m_l, mk, lpraw, out, f, lane);
 				}
 			}
 		}
 		filt_barrier();
 	}
-
-	// state out: ctl_store's words of the oscillators and the panmix
-	if(mylane) {
-		oscv_store(ustate + (size_t)uo0 * A2D_USTATE, o0);
-		oscv_store(ustate + (size_t)uo1 * A2D_USTATE, o1);
-		oscv_store(ustate + (size_t)uo2 * A2D_USTATE, o2);
-		int *wp = ustate + (size_t)up * A2D_USTATE;
-		ramp_store(wp + PW_VOL, vol);
-		ramp_store(wp + PW_PAN, pan);
-	}
+	o3_work_store(V, ustate, o0, o1, o2, vol, pan, mylane);
 }
 
 // the windows launch: the same shape
 int a2d_launch_leaf_osc3filtpan_win(const A2DParams *dparams, const A2DParams &hp, const int *dlist, int nlist, int vpg, void *stream)
 {
-	if(nlist <= 0)
-		return 0;
-	vpg = vpg < 1 ? 1 : vpg > QUIET_MAXV ? QUIET_MAXV : vpg;
-	const dim3 grid((nlist + vpg - 1) / vpg), block(64 * QUIET_WAVES);
-	const size_t dyn = (size_t)3 * vpg * QUIET_PITCH * sizeof(int);
-	hipLaunchKernelGGL(k_leaf_osc3filtpan_win, grid, block, dyn, (hipStream_t)stream, dparams, dlist, nlist, vpg, hp.voices, hp.runs,
-			hp.recs, hp.ustate, hp.waves, hp.ptab, hp.wavecoef, hp.nfrags, hp.busmem);
-	return hipGetLastError() != hipSuccess;
+	return quiet_launch(k_leaf_osc3filtpan_win, dparams, dlist, nlist, vpg, stream, hp.voices, hp.runs, hp.recs, hp.ustate, hp.waves,
+			hp.ptab, hp.wavecoef, hp.nfrags, hp.busmem);
 }

@@ -1,9 +1,11 @@
 // a2amd_quiet.h - the skeleton the quiet leaf kernels share: k_leaf_noisepan (a2amd_noisepan.hip), k_leaf_noisefiltpan
-// (a2amd_noisefiltpan.hip), k_leaf_oscbare (a2amd_oscbare.hip) and k_leaf_osc3filtpan (a2amd_osc3filtpan.hip).  The one
-// statement of: how the filter kernels' workgroup deals its voices to its worker wavefronts (for a host compiler too:
-// tests/test_quiet_header.py pins it), the facts every wavefront of such a workgroup derives from the same words, where
-// a worker's bus sums go and how a walk over the bus-sorted list cuts them into runs, and one oscillator's pair of
-// window taps.  The stages themselves differ from kernel to kernel and stay in the kernels.
+// (a2amd_noisefiltpan.hip), k_leaf_oscbare (a2amd_oscbare.hip) and k_leaf_osc3filtpan / k_leaf_osc3filtpan_win
+// (a2amd_osc3filtpan.hip).  The one statement of: how the filter kernels' workgroup deals its voices to its worker
+// wavefronts (for a host compiler too: tests/test_quiet_header.py pins it), the shape their launchers launch
+// (quiet_launch), the facts every wavefront of such a workgroup derives from the same words, how the pan stage reads a
+// filtered row (quiet_row), where a worker's bus sums go and how a walk over the bus-sorted list cuts them into runs, and
+// one oscillator's pair of window taps.  The stages themselves differ from kernel to kernel and stay in the kernels;
+// the stages the two three-oscillator kernels share with each other alone stand once in a2amd_osc3filtpan.hip.
 #pragma once
 #include <stdint.h>
 #include "a2amd_settled.h"	// (A2S: for the host and the device alike)
@@ -57,6 +59,20 @@ DEV unsigned long long quiet_worker_voices(int wv, int nv, unsigned long long to
 	return (unsigned long long)(unsigned)rfl((int)(unsigned)mine) | ((unsigned long long)(unsigned)rfl((int)(unsigned)(mine >> 32)) << 32);
 }
 
+// The filter kernels' launch over a list of nlist voices: vpg voices per workgroup, at most QUIET_MAXV (one per lane of
+// the filter wavefront); the ring of three [vpg][QUIET_PITCH] tiles is the dynamic LDS.  Every such kernel's arguments
+// begin (params, list, nlist, vpg); rest: the ones behind them.  Returns nonzero where the launch failed.
+template<typename Kernel, typename... Rest>
+static inline int quiet_launch(Kernel kernel, const A2DParams *dparams, const int *dlist, int nlist, int vpg, void *stream, Rest... rest)
+{
+	if(nlist <= 0)
+		return 0;
+	vpg = vpg < 1 ? 1 : vpg > QUIET_MAXV ? QUIET_MAXV : vpg;
+	hipLaunchKernelGGL(kernel, dim3((nlist + vpg - 1) / vpg), dim3(64 * QUIET_WAVES), (size_t)3 * vpg * QUIET_PITCH * sizeof(int),
+			(hipStream_t)stream, dparams, dlist, nlist, vpg, rest...);
+	return hipGetLastError() != hipSuccess;
+}
+
 // What every wavefront of the workgroup derives from the same words, lane = voice (ok: the voice is this kernel's; bp, hp:
 // its filter's band and high pass gains; off, nch: its output bus): the voices to render; the row format of the batch
 // (filt_step) - pure low pass filters in the whole workgroup leave l in the rows and the pan stage applies lp, 12
@@ -73,6 +89,14 @@ DEV QuietWg quiet_wg(bool ok, int bp, int hp, int off, int nch)
 		g.wgbus = __all(!ok || (off == g.wg_off && nch == 2));
 	}
 	return g;
+}
+
+// The pan stage's read of voice v's filtered row, lane = frame (lp: lane v's low pass gain): where the row holds l (lpraw,
+// filt_step) the scaling the filter wavefront left out
+DEV int quiet_row(const int *tile, int v, int lane, bool lpraw, int lp)
+{
+	const int y = tile[v * QUIET_PITCH + lane];
+	return lpraw ? wmul(y, rdl(lp, v)) >> 3 : y;
 }
 
 // ---- Bus sums, lane = frame ----

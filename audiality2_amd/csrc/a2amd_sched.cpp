@@ -1926,27 +1926,28 @@ static int launch_leaves(a2amd_ctx *c, LeafPass &lp)
 	// segment's voices are all the general kernel's - no launch).  A workgroup keeps its voices - at most 64, the lanes of
 	// its filter wavefront - for the whole batch, as k_leaf_noisefiltpan's does: spread first (one workgroup per CU, 256),
 	// then fill.  A2AMD_F2VPW forces the voices per workgroup.
+	auto o3_vpg = [&](int count) { return std::min(std::max(c->sw.f2vpw ? c->sw.f2vpw : (count + 255) / 256, 1), 64); };
+	auto o3_launched = [&](auto &info, int count, int vpg) {	// (either launch's info struct)
+		++c->stats.launches;
+		info.launched = 1;
+		info.vpg = (uint32_t)vpg;
+		info.workgroups = (uint32_t)((count + vpg - 1) / vpg);
+	};
 	const ListRange o3f = c->leaf[LEAF_OSC3FILTPAN];
 	if(o3f.count && c->n_o3f_quiet) {
-		const int vpg = std::min(std::max(c->sw.f2vpw ? c->sw.f2vpw : (o3f.count + 255) / 256, 1), 64);
+		const int vpg = o3_vpg(o3f.count);
 		if(a2d_launch_leaf_osc3filtpan(c->d_params, c->hparams, list + o3f.first, o3f.count, vpg, c->stream))
 			return c->fail(A2AMD_EHIP, "3-osc filter leaf launch failed: %s", hipGetErrorString(hipGetLastError()));
-		++c->stats.launches;
-		c->last_osc3filt.launched = 1;
-		c->last_osc3filt.vpg = (uint32_t)vpg;
-		c->last_osc3filt.workgroups = (uint32_t)((o3f.count + vpg - 1) / vpg);
+		o3_launched(c->last_osc3filt, o3f.count, vpg);
 	}
 	// ... and those of the class whose run is windows only (upload(): dyn[DYN_OSC3WIN]): the windows launch, the same
 	// workgroup and the same rule for its size, over this batch's list of them
 	const ListRange o3w = c->dyn[DYN_OSC3WIN];
 	if(o3w.count) {
-		const int vpg = std::min(std::max(c->sw.f2vpw ? c->sw.f2vpw : (o3w.count + 255) / 256, 1), 64);
+		const int vpg = o3_vpg(o3w.count);
 		if(a2d_launch_leaf_osc3filtpan_win(c->d_params, c->hparams, c->d_dyn + o3w.first, o3w.count, vpg, c->stream))
 			return c->fail(A2AMD_EHIP, "3-osc filter leaf windows launch failed: %s", hipGetErrorString(hipGetLastError()));
-		++c->stats.launches;
-		c->last_osc3win.launched = 1;
-		c->last_osc3win.vpg = (uint32_t)vpg;
-		c->last_osc3win.workgroups = (uint32_t)((o3w.count + vpg - 1) / vpg);
+		o3_launched(c->last_osc3win, o3w.count, vpg);
 	}
 	const ListRange osc2pan = c->leaf[LEAF_OSC2PAN];
 	if(osc2pan.count && none_quiet(1, osc2pan.count))

@@ -130,3 +130,17 @@ def test_the_header_is_the_only_statement():
         assert not re.search(PAIR, code), name
         assert code.count("atomicAdd") == (2 if name == "a2amd_oscbare.hip" else 0), name
     assert len(re.findall(PAIR, _code(HEADER))) == 1
+    # the quiet kernels name no filt_row instantiation: a2amd_filt.h picks it (a2amd_fast.hip's kernels choose for themselves)
+    assert {os.path.basename(p) for p in paths if re.search(r"\bfilt_row\s*<", _code(p))} == {"a2amd_filt.h", "a2amd_fast.hip"}
+    # the launch shape of the filter kernels - grid, block, the three tiles of dynamic LDS - stands in the header alone
+    assert {os.path.basename(p) for p in paths if re.search(r"3\s*\*\s*vpg\s*\*\s*QUIET_PITCH", _code(p))} == {"a2amd_quiet.h"}
+    assert {os.path.basename(p) for p in paths if re.search(r"QUIET_MAXV\s*\?", _code(p))} == {"a2amd_quiet.h"}
+    # the three-oscillator class: both kernels' rule of which voice is theirs - the mode test of the three oscillators -
+    # stands in one function, and so does the panmix head's clamp flag
+    o3 = _code(os.path.join(CSRC, "a2amd_osc3filtpan.hip"))
+    assert o3.count("__global__") == 2
+    modes = [m.start() for m in re.finditer(r"==\s*A2D_OSC_MIPWAVE\b", o3)]
+    assert len(modes) == 3 and o3.count("OW_MODE") == 3
+    body = o3[o3.rindex("\n{\n", 0, modes[0]):modes[-1]]        # from the function's opening brace to its last mode test
+    assert body.count("OW_MODE") == 3 and "\n}\n" not in body
+    assert len(re.findall(r"a2s_pan_over\s*\(\s*pan\.target\s*\)", o3)) == 1 and o3.count("a2s_pan_over") == 2
